@@ -63,6 +63,9 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=64, help="upper bound of the CPU baseline's thread sweep (8 / 16 / 32 / 64)")
     ap.add_argument("--dry-run", action="store_true", help="CPU-only plumbing check (gloo): no GPU work, fake step")
     ap.add_argument("--per-op", default="", help="write per-op timing table to this path")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all; "
+                         "bench_out/ is git-ignored)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="default run only: skip the short extra legs (RT-DETR / BiSeNetFormer training step, MaskFormer / BiSeNetFormer inference) "
                          "reported under `other_configs` of the one JSON line")
@@ -356,6 +359,34 @@ def _wgrad_roofline(nn_, stepper, imgs, targets, family="fai_detr"):
             "note": "events bracket the wgrad launch + its slab-sum/unpack pass of every conv layer in one extra step run with the weight gradients on the main stream (in the timed steps they run on a side stream, concurrently with the input-gradient chain)"}
 
 
+DUMP_LIMIT_BYTES = 60 << 20   # under the 64 MB of the --dump-outputs contract, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: tensor} as <path>/<name>.npy, floating point as float32 and integers as float64 (exact up to 2**53), so
+    that two builds can be compared output for output.  An array that would take the total over DUMP_LIMIT_BYTES is replaced by a fixed,
+    seeded sample of its flattened elements (`<name>.npy`, with the sampled flat indices in `<name>.index.npy`)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())     # small arrays first: the large ones share what is left
+    for i, (name, t) in enumerate(items):
+        t = t.detach().cpu()
+        a = (t.float() if t.is_floating_point() else t.double()).numpy()
+        budget = (DUMP_LIMIT_BYTES - total) // (len(items) - i)
+        if a.nbytes > budget:
+            n = budget // (a.itemsize + 8)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            np.save(os.path.join(path, f"{name}.index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            total += idx.size * 8
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_LIMIT_BYTES, total
+    return total
+
+
 def synth_train_targets(family, rank, it, B, S, K, dev):
     """The synthetic targets of training step ``it`` on ``rank`` (seed = rank*1000 + it): RT-DETR - T_i ~ U{1..20} boxes per image, centres in
     [0.2, 0.8], sizes in [0.05, 0.35], labels U{0..K-1}; mask families - 5-15 random rectangular masks per image.  Module-level so that the
@@ -436,6 +467,9 @@ def train_measure(args, world, rank, local, with_roofline=True):
         losses = stepper.step(imgs, all_targets[max(args.warmup, 1) + it])
     barrier(world, False)
     dt = max_over_ranks(time.perf_counter() - t0, world, False)
+    if rank == 0 and with_roofline and args.dump_outputs:
+        # the last timed step's losses and the fp32 master weights it produced
+        dump_outputs(args.dump_outputs, {**{k: v.reshape(-1) for k, v in losses.items()}, "master_weights": stepper.opt.flat_p})
     total = float(sum(v.detach().float() for v in losses.values()))
     value = world * B * args.steps / dt
     fwd = (ALG_GFLOP_PER_IMAGE_BF_1024 * (S / 1024.0) ** 2 if bf else
@@ -685,6 +719,10 @@ def infer_measure(args, world, rank, local, light=False):
     barrier(world, False)
     dt = max_over_ranks(time.perf_counter() - t0, world, False)
     ms_step = 1e3 * dt / args.steps
+    if rank == 0 and not light and args.dump_outputs:
+        # what a caller receives from the last timed step: the packed results copied to the host (the lane of the last ticket when pipelined)
+        last = hosts[(pipe.tickets - 1) % depth] if (pipe is not None and depth > 1) else host
+        dump_outputs(args.dump_outputs, last)
     value = world * B * args.steps / dt
 
     single = None
