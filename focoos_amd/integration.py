@@ -125,7 +125,8 @@ def _publish(cls):
     return cls
 
 
-_FACTORIES = {"EngineFAIDetr": "make_engine_class", "EngineFAIMaskFormer": "make_mf_engine_class", "EngineBisenetFormer": "make_bf_engine_class"}
+_FACTORIES = {"EngineFAIDetr": "make_engine_class", "EngineFAIMaskFormer": "make_mf_engine_class", "EngineBisenetFormer": "make_bf_engine_class",
+              "EngineFAIClassification": "make_cls_engine_class"}
 
 
 def __getattr__(name):
@@ -331,6 +332,46 @@ def make_bf_engine_class():
     return _publish(EngineBisenetFormer)
 
 
+def make_cls_engine_class():
+    """Adapter for the image classifiers (fai-cls-*): reference FAIClassification whose eval forward is the gfx950 engine.  The reference
+    model receives images its processor has already normalised (fai_cls/processor.py:98-99); the engine fuses the normalisation into its
+    stem, so the adapter maps them back to the 0..255 scale (x * std + mean, fp32) and runs the engine's float32 input path.  The reference's
+    ClassificationProcessor post-processes the CPU logits as they are: no processor adapter."""
+    if "EngineFAIClassification" in _CLASSES:
+        return _CLASSES["EngineFAIClassification"]
+    from focoos.models.fai_cls.modelling import FAIClassification as RefFAIClassification
+    from focoos.models.fai_cls.ports import ClassificationModelOutput
+
+    from .engine_cls import ClsEngine
+
+    class EngineFAIClassification(_FxAdapterState, RefFAIClassification):
+        def __init__(self, config):
+            super().__init__(config)
+            self._fx_engine: Optional[ClsEngine] = None
+            self._fx_version = None
+
+        def _fx_sync(self):
+            ver = _fx_version_key(self)
+            if self._fx_engine is None or str(self._fx_engine.dev) != str(self.device):
+                self._fx_engine = ClsEngine(_config_to_dict(self.config), self.state_dict(), str(self.device))
+            elif ver != self._fx_version:
+                self._fx_engine.load_state_dict(self.state_dict())
+            self._fx_version = ver
+
+        def forward(self, images, targets=[]):
+            if self._fx_exporting():
+                raise NotImplementedError("export of the classifier through the engine adapter is not built (use the reference's own model)")
+            if self.training or (targets is not None and len(targets) > 0):
+                raise NotImplementedError("classification training is not built: the engine runs the classifier's inference path")
+            _require_engine_input(images, 1)
+            x = (images.float() * self.pixel_std + self.pixel_mean).permute(0, 2, 3, 1).contiguous()
+            self._fx_sync()
+            pl = self._fx_engine.forward(x)
+            return ClassificationModelOutput(logits=pl.logits.clone(), loss=None)
+
+    return _publish(EngineFAIClassification)
+
+
 def make_processor_classes():
     """Engine-backed processors for the reference's ProcessorManager (processor/processor_manager.py:13-18, seam B1/B3): subclasses of
     the reference processors (pre-process, training targets, export paths untouched) whose ``postprocess`` on GPU tensors runs the
@@ -377,16 +418,17 @@ def make_processor_classes():
 
 
 def register() -> None:
-    """Re-register the DETR, MaskFormer and BiSeNetFormer families with the engine-backed model classes (last registration wins,
-    model_manager.py:93-105)."""
+    """Re-register the DETR, MaskFormer, BiSeNetFormer and image-classifier families with the engine-backed model classes (last registration
+    wins, model_manager.py:93-105)."""
     from focoos.model_manager import ModelManager
     from focoos.ports import ModelFamily
 
     import focoos.models.bisenetformer as family_bf
+    import focoos.models.fai_cls as family_cls
     import focoos.models.fai_detr as family
     import focoos.models.fai_mf as family_mf
 
-    for fam in (family, family_mf, family_bf):
+    for fam in (family, family_mf, family_bf, family_cls):
         for name in dir(fam):  # the family's own _register(): config + processor (+ stock model) registries
             if name.startswith("_register") and callable(getattr(fam, name)):
                 getattr(fam, name)()
@@ -396,6 +438,8 @@ def register() -> None:
     ModelManager.register_model(ModelFamily.MASKFORMER, lambda: cls_mf)
     cls_bf = make_bf_engine_class()
     ModelManager.register_model(ModelFamily.BISENETFORMER, lambda: cls_bf)
+    cls_cls = make_cls_engine_class()
+    ModelManager.register_model(ModelFamily.IMAGE_CLASSIFIER, lambda: cls_cls)
     # processors: ``model.infer()`` of a dropped-in model then post-processes on the device too
     from focoos.processor.processor_manager import ProcessorManager
 

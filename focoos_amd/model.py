@@ -4,6 +4,7 @@
   FocoosModel.__call__/infer focoos/models/focoos_model.py:370-416,575-621
   FAIDetr (BaseModelNN)     focoos/models/fai_detr/modelling.py:1273-1358, focoos/models/base_model.py:17-143
   FAIMaskFormer             focoos/models/fai_mf/modelling.py:633-725
+  FAIClassification         focoos/models/fai_cls/modelling.py:201-261 (inference only)
 
 Same names, argument meaning and error behaviour; the compute is the HIP engine (engine.py).
 ``FocoosModel.train`` drives the HIP training step (trainer.py; RT-DETR and BiSeNetFormer families); ``.export()`` is out of scope and raises
@@ -21,9 +22,10 @@ import torch
 
 from .engine import DetrEngine
 from .engine_bf import BfEngine
+from .engine_cls import ClsEngine
 from .engine_mf import MfEngine
-from .ports import MODELS_DIR, BisenetFormerOutput, DETRModelOutput, FocoosDetections, InferLatency, MaskFormerModelOutput, ModelInfo
-from .processor import BisenetFormerProcessor, DETRProcessor, MaskFormerProcessor
+from .ports import MODELS_DIR, BisenetFormerOutput, ClassificationModelOutput, DETRModelOutput, FocoosDetections, InferLatency, MaskFormerModelOutput, ModelInfo
+from .processor import BisenetFormerProcessor, ClassificationProcessor, DETRProcessor, MaskFormerProcessor
 from .registry import ModelRegistry
 from .state_spec import state_spec
 from .synth import synth_state_dict
@@ -193,11 +195,36 @@ class BisenetFormer(FAIMaskFormer):
     __call__ = forward
 
 
+class FAIClassification(_EngineModel):
+    """Engine-backed image classifier (focoos/models/fai_cls/modelling.py:201-261).  ``forward`` returns the reference's
+    ``ClassificationModelOutput`` with the f32 logits [B, num_classes] (one D2H-able buffer; the sigmoid is the processor's)."""
+
+    family = "fai_cls"
+
+    def _make_engine(self):
+        return ClsEngine(self.config, self._state, str(self._device))
+
+    def forward(self, images: torch.Tensor, targets: list = [], use_graph: bool = True) -> ClassificationModelOutput:
+        if self.training or (targets is not None and len(targets) > 0):
+            raise NotImplementedError("classification training is not built: the engine-backed module is the classifier's inference graph")
+        pl = self.engine.forward(self._to_nhwc(images), use_graph=use_graph)
+        self.last_plan = pl
+        return ClassificationModelOutput(logits=pl.logits.clone(), loss=None)
+
+    __call__ = forward
+
+    def detect(self, images: torch.Tensor, sizes: Optional[torch.Tensor] = None, threshold: Optional[float] = None):
+        pl = self.engine.forward(self._to_nhwc(images))
+        self.last_plan = pl
+        return pl
+
+
 class ProcessorManager:
     """focoos/processor/processor_manager.py:8-46 — family -> processor class registry (seam B1) with lazy loaders."""
 
     _PROCESSOR_MAPPING: Dict[str, Callable[[], Type]] = {
-        "fai_detr": lambda: DETRProcessor, "fai_mf": lambda: MaskFormerProcessor, "bisenetformer": lambda: BisenetFormerProcessor}
+        "fai_detr": lambda: DETRProcessor, "fai_mf": lambda: MaskFormerProcessor, "bisenetformer": lambda: BisenetFormerProcessor,
+        "fai_cls": lambda: ClassificationProcessor}
 
     @classmethod
     def register_processor(cls, model_family, processor_loader: Callable[[], Type]):
@@ -236,7 +263,9 @@ class FocoosModel:
         pl = self.model.detect(images, sizes=sizes, threshold=thr)
         torch.cuda.current_stream(self.model.device).synchronize()
         t2 = perf_counter()
-        if self.model.family in ("fai_mf", "bisenetformer"):
+        if self.model.family == "fai_cls":
+            out = self.processor.pack_detections(pl.logits.cpu(), self.model_info.classes, thr)   # the one D2H copy of the batch's logits
+        elif self.model.family in ("fai_mf", "bisenetformer"):
             out = self.processor.pack_detections(pl, self.model_info.classes)
         else:
             out = self.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, self.model_info.classes)
@@ -254,6 +283,9 @@ class FocoosModel:
         from collections import deque
 
         thr = threshold or self.processor.threshold
+        if self.model.family == "fai_cls":
+            yield from self._infer_stream_cls(batches, thr, depth)
+            return
         mask_family = self.model.family in ("fai_mf", "bisenetformer")
         pipe, pending = None, deque()
 
@@ -281,6 +313,35 @@ class FocoosModel:
         while pending:
             yield finish()
 
+    def _infer_stream_cls(self, batches, thr: float, depth: Optional[int]):
+        """infer_stream of the classifiers: a pipeline is reused only when (B, H, W, input dtype) all match - a uint8 batch and a resized
+        float32 batch of one shape run on different plans (the input buffer's dtype is part of the plan).  Each lane's logits are copied
+        into a pinned host buffer on the lane's stream; the sigmoid / threshold run on them on the host."""
+        from collections import deque
+
+        pipe, key, pending = None, None, deque()
+
+        def finish():
+            ticket, host = pending.popleft()
+            pipe.wait(ticket)
+            return self.processor.pack_detections(host["logits"], self.model_info.classes, thr)
+
+        for inputs in batches:
+            images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
+            x = self.model._to_nhwc(images)
+            B, H, W, _ = x.shape
+            k = (B, H, W, x.dtype)
+            if pipe is None or key != k:
+                while pending:
+                    yield finish()
+                pipe, key = self.model.engine.pipeline(B, H, W, depth, x.dtype == torch.float32), k
+            if len(pending) >= pipe.depth:      # the lane about to be reused still holds an unread result
+                yield finish()
+            host = {"logits": torch.empty(B, self.model.num_classes, dtype=torch.float32, pin_memory=True)}
+            pending.append((pipe.submit(x, None, thr, host), host))
+        while pending:
+            yield finish()
+
     def __call__(self, inputs, **kwargs) -> FocoosDetections:
         lst = inputs if isinstance(inputs, list) else [inputs]
         return self.infer_batch(lst, threshold=kwargs.get("threshold"))[0]
@@ -297,6 +358,8 @@ class FocoosModel:
     def train(self, args, data_train, data_val=None, hub=None):
         """focoos_model.py:221-274: fine-tune on ``data_train`` (indexable, entries = ports.DatasetEntry) with ``args`` (ports.TrainerArgs):
         one process per GPU, TrainStep on every rank, artifacts in ``args.output_dir/args.run_name``, weights reloaded into the engine."""
+        if self.model.family == "fai_cls":
+            raise NotImplementedError("classification training is not built: fai-cls models run inference only on this engine")
         from .trainer import train as _train
 
         return _train(self, args, data_train, data_val, hub)
@@ -309,7 +372,8 @@ class ModelManager:
     """focoos/model_manager.py:17-155 — lazy family registry + ``get``."""
 
     _MODEL_MAPPING: Dict[str, Callable[[], Type]] = {"fai_detr": lambda: FAIDetr, "fai_mf": lambda: FAIMaskFormer,
-                                                              "bisenetformer": lambda: BisenetFormer}
+                                                              "bisenetformer": lambda: BisenetFormer,
+                                                              "fai_cls": lambda: FAIClassification}
 
     @classmethod
     def register_model(cls, model_family: str, model_loader: Callable[[], Type]):

@@ -118,6 +118,13 @@ class BisenetFormerOutput(ModelOutput):
 
 
 @dataclass
+class ClassificationModelOutput(ModelOutput):
+    """focoos/models/fai_cls/ports.py:9-12."""
+    logits: torch.Tensor  # [N, num_classes] raw logits (the sigmoid is the processor's)
+    loss: Optional[dict]   # (declared in ModelOutput: stays the FIRST field, like in the reference - construct by keyword)
+
+
+@dataclass
 class MaskFormerTargets:
     """focoos/models/fai_mf/ports.py:16-19 (BisenetFormerTargets has the same fields)."""
     labels: torch.Tensor  # [T] class ids

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check
-from .ports import DatasetEntry, DETRModelOutput, DynamicAxes, FocoosDet, FocoosDetections, MaskFormerModelOutput  # noqa: F401
+from .ports import ClassificationModelOutput, DatasetEntry, DETRModelOutput, DynamicAxes, FocoosDet, FocoosDetections, MaskFormerModelOutput  # noqa: F401
 
 try:  # PIL is optional
     from PIL import Image
@@ -502,3 +502,55 @@ class _MfDeviceResults:
         self.det_boxes = torch.zeros(B, Q, 4, dtype=torch.int32, device=dev)
         self.det_area = torch.zeros(B, Q, dtype=torch.int32, device=dev)
         self.mask_words = torch.zeros(B, Q, H, (W + 31) // 32, dtype=torch.int32, device=dev)   # rows padded to whole words
+
+
+class ClassificationProcessor(DETRProcessor):
+    """focoos/models/fai_cls/processor.py:16-158 for the engine.  ``preprocess`` is the device path of the other processors (uint8 NHWC when
+    the images already have ``im_size``, bilinearly resized float32 otherwise; the normalisation is fused into the stem kernel).  The
+    post-process runs on CPU logits in torch fp32 exactly as the reference's: ``probs = sigmoid(logits)``, ``threshold = threshold or 0.5`` (0
+    and None both mean 0.5; the config's threshold is never read), every class with ``probs > threshold`` in ascending class order becomes a
+    ``FocoosDet(conf, cls_id, label)`` with no box and no mask."""
+
+    def __init__(self, config: dict, image_size: Optional[Union[int, Tuple[int, int]]] = None):
+        super().__init__(config, image_size)
+        self.num_classes = int(config["num_classes"])
+        self.threshold = 0.5
+
+    def preprocess(self, inputs: ImageInput, device: torch.device, dtype: torch.dtype = torch.float32):
+        lst = inputs if isinstance(inputs, list) else [inputs]
+        if len(lst) > 0 and isinstance(lst[0], DatasetEntry):
+            raise NotImplementedError("classification training is not built: the engine runs the classifier's inference path")
+        return super().preprocess(inputs, device, dtype)
+
+    def eval_postprocess(self, outputs: ClassificationModelOutput, inputs: Sequence = ()) -> List[dict]:
+        """processor.py:100-111: one ``{"logits": sigmoid probabilities}`` per image."""
+        probs = torch.sigmoid(outputs.logits)
+        return [{"logits": p} for p in probs]
+
+    def postprocess(self, outputs: ClassificationModelOutput, inputs: ImageInput = None, class_names: Sequence[str] = (),
+                    threshold: Optional[float] = None) -> List[FocoosDetections]:
+        return self.pack_detections(outputs.logits, class_names, threshold)
+
+    @staticmethod
+    def pack_detections(logits: torch.Tensor, class_names: Sequence[str] = (), threshold: Optional[float] = None) -> List[FocoosDetections]:
+        """processor.py:113-158 on [B, num_classes] logits (device or host; copied to the host once)."""
+        probs = torch.sigmoid(logits.detach().cpu().to(torch.float32))
+        threshold = threshold or 0.5
+        results = []
+        for probs_i in probs:
+            dets = []
+            for cls_id in (probs_i > threshold).nonzero(as_tuple=True)[0].tolist():
+                dets.append(FocoosDet(conf=probs_i[cls_id].item(), cls_id=int(cls_id),
+                                      label=class_names[cls_id] if class_names and cls_id < len(class_names) else None))
+            results.append(FocoosDetections(detections=dets))
+        return results
+
+    def export_postprocess(self, output, inputs: ImageInput = None, class_names: Sequence[str] = (), threshold: Optional[float] = None, **kw):
+        logits = output[0]
+        if isinstance(logits, np.ndarray):
+            logits = torch.from_numpy(logits)
+        return self.pack_detections(logits, class_names, threshold)
+
+    def get_dynamic_axes(self) -> DynamicAxes:
+        return DynamicAxes(input_names=["images"], output_names=["logits"],
+                           dynamic_axes={"images": {0: "batch", 2: "height", 3: "width"}, "logits": {0: "batch"}})

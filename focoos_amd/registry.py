@@ -153,7 +153,39 @@ def _mf_entry(name: str, cfg: Dict, description: str) -> Dict:
     }
 
 
+# focoos/model_registry/fai-cls-{n,s,m}-coco.json: STDC (size preset nano / small) + pooled 1x1-conv head, multi-label sigmoid over 80 classes
+_CLS_CONFIG = {
+    "num_classes": 80,
+    "backbone_config": {"use_pretrained": False, "model_type": "stdc", "in_chans": 3, "out_features": ["res2", "res3", "res4", "res5"],
+                        "size": "small", "use_conv_last": False},
+    "resolution": 224, "pixel_mean": [123.675, 116.28, 103.53], "pixel_std": [58.395, 57.12, 57.375], "hidden_dim": 512, "dropout_rate": 0.2,
+    "features": "res4", "num_layers": 1, "dense_prediction": False, "use_focal_loss": False, "focal_alpha": 0.75, "focal_gamma": 2.0,
+    "label_smoothing": 0.0, "pos_weight": 2.0,
+}
+_CLS_N_CONFIG = copy.deepcopy(_CLS_CONFIG)
+_CLS_N_CONFIG["backbone_config"] = {"use_pretrained": False, "model_type": "stdc", "in_chans": 3, "out_features": ["res2", "res3", "res4", "res5"],
+                                    "block_type": "cat", "size": "nano", "use_conv_last": False}
+_CLS_S_CONFIG = copy.deepcopy(_CLS_CONFIG)
+_CLS_M_CONFIG = copy.deepcopy(_CLS_CONFIG)
+_CLS_M_CONFIG["backbone_config"] = {"use_pretrained": False, "backbone_url": "https://public.focoos.ai/pretrained_models/backbones/stdc_small.pth",
+                                    "model_type": "stdc", "in_chans": 3, "out_features": ["res2", "res3", "res4", "res5"], "size": "small",
+                                    "use_conv_last": False}
+_CLS_M_CONFIG["features"] = "res5"
+
+
+def _cls_entry(name: str, cfg: Dict, description: str) -> Dict:
+    cfg = copy.deepcopy(cfg)
+    return {
+        "name": name, "model_family": "fai_cls", "task": "classification", "im_size": 224,
+        "classes": [f"class_{i}" for i in range(int(cfg["num_classes"]))],
+        "config": cfg, "weights_uri": None, "description": description,
+    }
+
+
 _REGISTRY = {
+    "fai-cls-n-coco": _cls_entry("fai-cls-n-coco", _CLS_N_CONFIG, "Very tiny classification model optimized for Arduino Nicla Vision"),
+    "fai-cls-s-coco": _cls_entry("fai-cls-s-coco", _CLS_S_CONFIG, "A classification model"),
+    "fai-cls-m-coco": _cls_entry("fai-cls-m-coco", _CLS_M_CONFIG, "A classification model"),
     "bisenetformer-l-ade": _bf_entry("bisenetformer-l-ade", _BF_L_ADE_CONFIG, "BiSeNetFormer large (STDC-2), ADE20K semantic segmentation"),
     "bisenetformer-m-ade": _bf_entry("bisenetformer-m-ade", _BF_M_ADE_CONFIG, "BiSeNetFormer medium (STDC-2, 96-channel pixel decoder), ADE20K semantic segmentation"),
     "bisenetformer-s-ade": _bf_entry("bisenetformer-s-ade", _BF_S_ADE_CONFIG, "BiSeNetFormer small (STDC-1), ADE20K semantic segmentation"),

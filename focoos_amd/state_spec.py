@@ -310,6 +310,35 @@ def bf_state_spec(config: Dict) -> "OrderedDict[str, Tuple[Tuple[int, ...], str]
     return spec
 
 
+def cls_state_spec(config: Dict) -> "OrderedDict[str, Tuple[Tuple[int, ...], str]]":
+    """Ordered ``name -> (shape, kind)`` of ``FAIClassification(config).state_dict()`` (focoos/models/fai_cls/modelling.py:201-231): the STDC
+    backbone under ``backbone.`` with the layers / base its ``size`` preset selects (stdc.py:192-212) - all four stages, whatever ``features``
+    the head reads - the head's 1x1 conv(s) and the BCE criterion's ``pos_weight`` buffer; pinned against the reference's own key dump in
+    tests/golden/cls_{n,s}_state_keys.json."""
+    from .engine_stdc import resolve_stdc_size
+
+    bb = config["backbone_config"]
+    if bb.get("model_type") != "stdc" or bb.get("block_type", "cat") != "cat":
+        raise ValueError("engine state spec covers STDC (cat) backbones (fai-cls-*)")
+    layers, base = resolve_stdc_size(bb)
+    nc = int(config["num_classes"])
+    spec: "OrderedDict[str, Tuple[Tuple[int, ...], str]]" = OrderedDict()
+    chans = stdc_spec(spec, "backbone", base, layers, int(bb.get("block_num", 4)), int(bb.get("in_chans", 3)))
+    cin = chans[int(str(config.get("features", "res5"))[3]) - 2]
+    if int(config.get("num_layers", 1)) == 2:
+        hd = int(config.get("hidden_dim", 512))
+        spec["cls_head.classifier.1.weight"] = ((hd, cin, 1, 1), "conv_w")
+        spec["cls_head.classifier.1.bias"] = ((hd,), "lin_b")
+        spec["cls_head.classifier.4.weight"] = ((nc, hd, 1, 1), "conv_w")
+        spec["cls_head.classifier.4.bias"] = ((nc,), "lin_b")
+    else:
+        spec["cls_head.classifier.2.weight"] = ((nc, cin, 1, 1), "conv_w")
+        spec["cls_head.classifier.2.bias"] = ((nc,), "lin_b")
+    if not bool(config.get("use_focal_loss", False)):
+        spec["criterion.ce_loss.pos_weight"] = ((nc,), "pos_weight")
+    return spec
+
+
 def state_spec(config: Dict, family: str = "fai_detr"):
     if family == "fai_detr":
         return detr_state_spec(config)
@@ -317,4 +346,6 @@ def state_spec(config: Dict, family: str = "fai_detr"):
         return mf_state_spec(config)
     if family == "bisenetformer":
         return bf_state_spec(config)
+    if family == "fai_cls":
+        return cls_state_spec(config)
     raise ValueError(f"engine has no state spec for model family {family!r}")

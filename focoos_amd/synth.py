@@ -75,6 +75,8 @@ def synth_state_dict(config: Dict, seed: int = 0, family: str = "fai_detr") -> "
             a = (0.05 * rs.standard_normal(shape)).astype(np.float32)
         elif kind == "emb":
             a = rs.standard_normal(shape).astype(np.float32)
+        elif kind == "pos_weight":   # BCEWithLogitsLoss(pos_weight=pos_weight * ones) of the classifier's criterion (fai_cls/modelling.py:112)
+            a = np.full(shape, float(config.get("pos_weight", 10.0)), dtype=np.float32)
         elif kind == "buf":
             a = np.ones(shape, dtype=np.float32)
             a[-1] = 0.1

@@ -29,7 +29,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 8
+#define FX_ABI_VERSION 9
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -143,6 +143,23 @@ int fx_stem_conv3x3s2(const void* x, int in_f32, const float* w, const float* bi
  * The [B,H/2,W/2,32] conv1_1 activation is never written; bit-identical to fx_stem_conv3x3s2 followed by fx_conv2d_nhwc_bf16 (act = ReLU). */
 int fx_stem_conv12_u8_bf16(const void* x_u8, const float* w1, const float* b1, const float* mean, const float* inv_std, const void* w2_frag,
                            const float* b2, void* y, int ldy, int B, int H, int W, fx_stream_t stream);
+
+/* ---- STDC-nano 16-channel layers (ABI 9; csrc/stdc_nano.hip): the classifier fai-cls-n-coco's STDC base 32 backbone
+ * (focoos/nn/backbone/stdc.py:205-208 size "nano", :302-311 _make_layers) behind FAIClassification.forward (focoos/models/fai_cls/modelling.py:
+ * 234-261) and ClassificationProcessor.preprocess's normalisation (fai_cls/processor.py:98-99).
+ * fx_stem16_conv3x3s2: features.0 = ConvX(3, 16, 3, stride 2) (stdc.py:35-48): y = relu(conv3x3_s2_p1((x - mean) * inv_std) + bias) with the
+ * eval BatchNorm folded; x HWC uint8 (in_f32 = 0) or float32 on the 0..255 scale (in_f32 = 1), w f32 [3][3][3][16] (kh,kw,c,n), bias f32 [16];
+ * y bf16 [B,(H-1)/2+1,(W-1)/2+1,16] (contiguous, 16-byte aligned).  Zero padding applies to the normalised image. */
+int fx_stem16_conv3x3s2(const void* x, int in_f32, const float* w, const float* bias, const float* mean, const float* inv_std, void* y, int B,
+                        int H, int W, fx_stream_t stream);
+/* fx_conv3x3_c16_nhwc_bf16: 3x3 / pad 1 ConvX (conv + folded BN + optional ReLU) with a 16-channel side: (C, N) in {(16, 32), (16, 16),
+ * (32, 16)}, stride 1 or 2 - STDC-nano features.1 (16 -> 32, s2; stdc.py:303) and CatBottleneck conv_list.2 / conv_list.3 of the 128-channel
+ * stage (32 -> 16, 16 -> 16; stdc.py:129-151).  x bf16 NHWC [B,H,W,C] with pixel stride ldx, y bf16 [B,(H-1)/stride+1,(W-1)/stride+1,N] with
+ * pixel stride ldy (either may be a channel slice of a wider buffer: ldx, ldy multiples of 8, x / y 16-byte aligned); w_frag = the layer's
+ * weights in MFMA fragment order of ONE 32-row block, [9*C/16][64][8] with k = (kh*3 + kw)*C + c and rows >= N zero; bias f32 [N]; relu 0 / 1.
+ * Shapes outside this contract: FX_ERR_INVALID_ARGUMENT, nothing launched. */
+int fx_conv3x3_c16_nhwc_bf16(const void* x, int ldx, const void* w_frag, const float* bias, int relu, void* y, int ldy, int B, int H, int W, int C,
+                             int N, int stride, fx_stream_t stream);
 
 /* Processor.get_torch_batch resize (focoos/processor/base_processor.py:285-288):
  * F.interpolate(bilinear, align_corners=False) of one HWC uint8 image to [Ho,Wo,3] float32. */
