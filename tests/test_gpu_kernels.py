@@ -16,7 +16,7 @@ from focoos_amd import _lib  # noqa: E402
 from focoos_amd._lib import FX_ACT, FxConvDesc, check  # noqa: E402
 from oracle import detr_oracle as O  # noqa: E402
 from tests._cases import MSDA_SHAPES, msda_case_inputs  # noqa: E402
-from tests.helpers import load_golden  # noqa: E402
+from tests.helpers import assert_ulp_gate, conv_ref64, gemm_ref64, load_golden  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -99,6 +99,16 @@ def ref_conv(x_nhwc, W4, bias, stride=1, act=None, residual=None, res_after=Fals
     return y.permute(0, 2, 3, 1)
 
 
+def gate64(got, x_nhwc, W4, bias, stride=1, act=None, residual=None, res_after=False, pool2=False, out_f32=False, what=""):
+    """The per-element gate of tests/helpers.py (1 ulp + c*mag, RNE agreement) against an fp64 reference on the bf16 operands; prints the
+    measured worst values."""
+    ref, mag = conv_ref64(to_dev(bf(x_nhwc)), to_dev(bf(W4)), to_dev(bias) if bias is not None else None, stride, act,
+                          to_dev(bf(residual)) if residual is not None else None, res_after, pool2)
+    s = assert_ulp_gate(to_dev(got), ref, mag, what, fp32_out=out_f32)
+    print(f"ULP {what}: ulp_max={s['ulp_max']:.3f} c_needed={s['c_needed']:.2e} agree={s['agree']:.5f}")
+    return s
+
+
 CONV_CASES = [
     # B,H,W,C,N,k,stride,act,residual,res_after,pool2,out_f32
     (2, 20, 20, 64, 256, 1, 1, "relu", True, False, False, False),
@@ -146,6 +156,7 @@ def test_conv_igemm(lib, case):
     err = (got - ref).abs().max() / ref.abs().max()
     assert err < tol, f"rel err {err}"
     assert not torch.isnan(got).any()
+    gate64(got, x, W4, bias, stride, act, res, res_after, pool2, out_f32, what=f"conv_igemm{case}")
 
 
 def test_conv_asymmetric_identity(lib):
@@ -565,6 +576,9 @@ def test_pw_chain_matches_two_convs(lib, case):
     assert not torch.isnan(got1).any()
     tol1 = 1e-2 * r1.abs().max().item()
     assert (got1 - r1).abs().max().item() <= tol1, ((got1 - r1).abs().max().item(), tol1)
+    r64, m64 = gemm_ref64(to_dev(X), to_dev(bf(W1)), to_dev(b1), act1, to_dev(bf(res)) if has_res else None)
+    s = assert_ulp_gate(to_dev(got1), r64, m64, f"pw_chain y1 {case}")
+    print(f"ULP pw_chain-y1{case}: ulp_max={s['ulp_max']:.3f} c_needed={s['c_needed']:.2e} agree={s['agree']:.5f}")
     if N2:
         r2 = (got1 @ bf(W2).float().T + b2).relu()   # from the kernel's own (bf16) y1: isolates the second GEMM
         y2 = y2d.float().cpu()
@@ -573,6 +587,9 @@ def test_pw_chain_matches_two_convs(lib, case):
         assert not torch.isnan(got2).any()
         tol2 = 1e-2 * r2.abs().max().item()
         assert (got2 - r2).abs().max().item() <= tol2, ((got2 - r2).abs().max().item(), tol2)
+        r64, m64 = gemm_ref64(to_dev(got1), to_dev(bf(W2)), to_dev(b2), "relu")
+        s = assert_ulp_gate(to_dev(got2), r64, m64, f"pw_chain y2 {case}")
+        print(f"ULP pw_chain-y2{case}: ulp_max={s['ulp_max']:.3f} c_needed={s['c_needed']:.2e} agree={s['agree']:.5f}")
 
 
 @pytest.mark.parametrize("case", [(2, 12, 20, 64, 256, 128), (1, 8, 8, 128, 512, 256), (3, 6, 10, 64, 512, 128)])
@@ -727,6 +744,8 @@ def test_conv3x3_flat_halo_kernel(lib, case, flat_small_shapes):
     # same layer through the implicit-GEMM kernel: the two agree to bf16 rounding of the output
     igemm = run_conv(lib, x, W4, bias, 1, act, res, res_after, ldx=Cc + pad, frag=False)[..., :N]
     assert (got - igemm).abs().max() / ref.abs().max() < 1.2e-2
+    gate64(got, x, W4, bias, 1, act, res, res_after, what=f"conv3x3_flat{case}")
+    gate64(igemm, x, W4, bias, 1, act, res, res_after, what=f"conv3x3_flat-igemm{case}")
 
 
 # 3x3 / STRIDE 2 layers on the parity-plane k-plane kernel (conv3x3s2_kplane.hip): B,H,W,C,N,act,ldx pad
@@ -758,6 +777,8 @@ def test_conv3x3_stride2_kplane_kernel(lib, case, flat_small_shapes):
     assert err < 1.2e-2, f"rel err {err}"
     igemm = run_conv(lib, x, W4, bias, 2, act, None, False, ldx=Cc + pad, frag=False)[..., :N]
     assert (got - igemm).abs().max() / ref.abs().max() < 1.2e-2
+    gate64(got, x, W4, bias, 2, act, what=f"conv3x3s2{case}")
+    gate64(igemm, x, W4, bias, 2, act, what=f"conv3x3s2-igemm{case}")
 
 
 def test_conv3x3_stride2_routing(lib, flat_small_shapes):
@@ -809,6 +830,8 @@ def test_pointwise_flat_kernel(lib, case, flat_small_shapes):
     assert err < 1.2e-2, f"rel err {err}"
     igemm = run_conv(lib, x, W4, bias, 1, act, res, False, frag=False)[..., :N]
     assert (got - igemm).abs().max() / ref.abs().max() < 1.2e-2
+    gate64(got, x, W4, bias, 1, act, res, what=f"pw_flat{case}")
+    gate64(igemm, x, W4, bias, 1, act, res, what=f"pw_flat-igemm{case}")
 
 
 def test_pointwise_flat_batch_stride(lib, flat_small_shapes):
@@ -825,6 +848,64 @@ def test_pointwise_flat_batch_stride(lib, flat_small_shapes):
     assert torch.isnan(got[:, :20]).all() and torch.isnan(got[:, 20 + H * W:]).all()
     assert (got[:, 20:20 + H * W] - ref).abs().max() / ref.abs().max() < 1.2e-2
 
+
+
+# Both sides of every M threshold of the production routing (conv_route in conv_igemm.hip, c3k in conv3x3_kplane.hip, launch_pwk in
+# conv_pw_kplane.hip, fx_launch_pw_flat in conv3x3_flat.hip), reached by shapes whose natural M = B*H*W lands there - no FX_* variable
+# and no `flat_small_shapes`: the library's defaults decide, as in bench.py.  B,H,W,C,N,k,act,residual,res_after,frag,expected label
+ROUTE_EDGE_CASES = [
+    # FX_C3K_DUO256_MIN_M = 40 000: the two-workgroup conv3x3_kplane forms from M = 40 000 (B = 25 at 40x40) on, not at 38 400 (B = 24)
+    (25, 40, 40, 256, 256, 3, "silu", False, False, True, "conv3x3_kplane<256>"),
+    (24, 40, 40, 256, 256, 3, "silu", False, False, True, "conv3x3_kplane<256>"),
+    (25, 40, 40, 256, 256, 3, "silu", True, True, True, "conv3x3_kplane<256>"),      # with the LDS residual tile (FX_C3K_DUO256_RES)
+    (24, 40, 40, 256, 256, 3, "silu", True, True, True, "conv3x3_kplane<256>"),
+    # FX_C3K_SMALL_M = 16 000: 64-pixel tiles up to M = 16 000 (B = 10 at 40x40), 128-pixel tiles at 16 400 (B = 41 at 20x20)
+    (10, 40, 40, 256, 256, 3, "relu", False, False, True, "conv3x3_kplane<256>"),
+    (41, 20, 20, 256, 256, 3, "relu", False, False, True, "conv3x3_kplane<256>"),
+    # launch_pwk, K = 256 (want = FX_PWK_TARGET_WGS = 512 workgroups, 128-row tiles): groups == 1 iff mt = ceil(M/128) >= 384
+    (48, 32, 32, 256, 1024, 1, "relu", True, False, True, "pw_kplane<K256>"),           # mt = 384: one workgroup walks all four n-tiles
+    (1, 128, 383, 256, 1024, 1, "relu", True, False, True, "pw_kplane<K256>"),          # mt = 383: n-tiles spread over two workgroups
+    # launch_pwk, K = 512 (want = 256): groups == 1 iff mt >= 192
+    (6, 64, 64, 512, 2048, 1, "relu", True, False, True, "pw_kplane<K512>"),            # mt = 192
+    (1, 128, 191, 512, 2048, 1, "relu", True, False, True, "pw_kplane<K512>"),          # mt = 191
+    # FX_PWF_BM64_MAX_M = 20 000: pw_flat's 64-pixel tiles for deep-K pointwise layers up to M = 20 000 (B = 50 at 20x20), not at 20 400
+    (50, 20, 20, 1024, 256, 1, "relu", False, False, True, "pw_flat<K1024>"),
+    (51, 20, 20, 1024, 256, 1, "relu", False, False, True, "pw_flat<K1024>"),
+    # FX_SMALL_M = 16 384: the one-stage 64x64x256 tiles for layers without a fragment-ordered copy up to M = 16 384, not at 16 400
+    (16, 32, 32, 256, 256, 1, None, False, False, False, "conv_igemm<64,64,256,1stage>"),
+    (41, 20, 20, 256, 256, 1, None, False, False, False, "conv_igemm<128,128,32>"),
+    # FX_CONV3_MIN_M / FX_PW_MIN_M = 5 000: the halo / pointwise kernels from M = 5 000 on (B = 50 at 10x10), the implicit GEMM below
+    (50, 10, 10, 256, 256, 1, "relu", False, False, True, "pw_kplane<K256>"),
+    (49, 10, 10, 256, 256, 1, "relu", False, False, True, "conv_igemm<64,64,256,1stage>"),
+    (50, 10, 10, 256, 256, 3, "relu", False, False, True, "conv3x3_kplane<256>"),
+    (49, 10, 10, 256, 256, 3, "relu", False, False, True, "conv_igemm<128,128,64>"),
+]
+
+
+@pytest.mark.parametrize("case", ROUTE_EDGE_CASES)
+def test_conv_routing_threshold_edges(lib, case):
+    """Production routing on both sides of each M threshold: the library's label, the old relative gate and the per-element ulp gate."""
+    B, H, W, Cc, N, k, act, has_res, res_after, frag, label = case
+    g = torch.Generator().manual_seed(900 + ROUTE_EDGE_CASES.index(case))
+    x = torch.randn(B, H, W, Cc, generator=g) + torch.linspace(-1, 1, W)[None, None, :, None] + torch.linspace(-0.25, 0.25, Cc)
+    W4 = torch.randn(N, Cc, k, k, generator=g) / math.sqrt(Cc * k * k) + torch.linspace(-0.03, 0.03, k * k).view(1, 1, k, k)
+    bias = torch.randn(N, generator=g) * 0.5
+    res = torch.randn(B, H, W, N, generator=g) if has_res else None
+    d = FxConvDesc()
+    buf = torch.zeros(16, dtype=torch.bfloat16, device=DEV)
+    d.x = d.w = d.y = buf.data_ptr()
+    d.B, d.H, d.W, d.C, d.ldx, d.Ho, d.Wo, d.N, d.ldy = B, H, W, Cc, Cc, H, W, N, N
+    d.KH, d.KW, d.stride, d.pad, d.act = k, k, 1, (k - 1) // 2, FX_ACT[act]
+    d.residual, d.ldr, d.residual_after_act = (buf.data_ptr(), N, int(res_after)) if has_res else (None, 0, 0)
+    d.w_frag = buf.data_ptr() if frag else None
+    out = C.create_string_buffer(64)
+    check(lib.fx_conv2d_variant(C.byref(d), out, 64), "variant")
+    assert out.value.decode() == label, (out.value.decode(), label)
+    got = run_conv(lib, x, W4, bias, 1, act, res, res_after, frag=frag)[..., :N]
+    assert not torch.isnan(got).any()
+    ref = ref_conv(x, W4, bias, 1, act, res, res_after, False)
+    assert (got - ref).abs().max() / ref.abs().max() < 1.2e-2
+    gate64(got, x, W4, bias, 1, act, res, res_after, what=f"route-edge{case}")
 
 def test_row_chain_interpreter(lib):
     """fx_row_chain: every stage type of the decoder's row chains against torch (bf16 operands, fp32 accumulation, bf16 hand-over
