@@ -74,6 +74,7 @@ SIGNATURES = {
     "fx_stem_conv3x3s2": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "fx_stem16_conv3x3s2": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "fx_conv3x3_c16_nhwc_bf16": [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "fx_semseg_eval_accumulate": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "fx_resize_bilinear_u8": [_vp, _i, _i, _vp, _i, _i, _vp],
     "fx_maxpool3x3s2_nhwc_bf16": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "fx_stem_conv12_u8_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -241,7 +242,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 9   # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 10  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:

@@ -7,7 +7,8 @@
   FAIClassification         focoos/models/fai_cls/modelling.py:201-261 (inference only)
 
 Same names, argument meaning and error behaviour; the compute is the HIP engine (engine.py).
-``FocoosModel.train`` drives the HIP training step (trainer.py; RT-DETR and BiSeNetFormer families); ``.export()`` is out of scope and raises
+``FocoosModel.train`` drives the HIP training step (trainer.py; RT-DETR and BiSeNetFormer families); ``FocoosModel.eval`` evaluates the
+semantic-segmentation and classification entries (evaluation.py); ``.export()`` is out of scope and raises
 NotImplementedError (loudly — never a silent fallback)."""
 from __future__ import annotations
 
@@ -363,6 +364,16 @@ class FocoosModel:
         from .trainer import train as _train
 
         return _train(self, args, data_train, data_val, hub)
+
+    def eval(self, args, data_test, save_json: bool = True) -> dict:
+        """focoos_model.py:276-320 + trainer.py:226-286: evaluate on ``data_test`` (indexable; ports.SemanticSegmentationDatasetEntry /
+        ClassificationDatasetDict items, metadata from ``data_test.dataset.metadata`` or ``data_test.metadata``), write
+        ``args.output_dir/<run_name>_eval/{model_info,metrics}.json`` and return the results dict.  Semantic segmentation runs the fused
+        fx_semseg_eval_accumulate kernel, classification counts TP / FP / FN on the device (evaluation.py).  Detection and instance
+        segmentation raise NotImplementedError (COCO AP needs pycocotools' COCOeval)."""
+        from .evaluation import run_eval
+
+        return run_eval(self, args, data_test, save_json)
 
     def export(self, *a, **k):
         raise NotImplementedError("FocoosModel.export: the ONNX/TensorRT export path is out of scope (BASELINE north_star)")

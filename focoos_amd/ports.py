@@ -158,6 +158,8 @@ class ModelInfo:
     config: dict
     weights_uri: Optional[str] = None
     description: Optional[str] = None
+    val_metrics: Optional[dict] = None     # FocoosModel.eval: the prefixed task metrics (trainer.py:270-281)
+    val_dataset: Optional[str] = None
 
     @classmethod
     def from_json(cls, data) -> "ModelInfo":
@@ -303,6 +305,22 @@ class DatasetEntry(DictClass):
     instances: Optional[Instances] = None
     file_name: Optional[str] = None
     image_id: Optional[int] = None
+
+
+@dataclass
+class SemanticSegmentationDatasetEntry(DatasetEntry):
+    """focoos/ports.py SemanticSegmentationDatasetEntry: ``sem_seg_file_name`` is the ground-truth label image (read with PIL, as
+    load_image_into_numpy_array does); ``sem_seg`` an in-memory [H, W] label array (engine extension: synthetic or pre-loaded data)."""
+    sem_seg_file_name: Optional[str] = None
+    sem_seg: Optional[object] = None
+
+
+@dataclass
+class ClassificationDatasetDict(DatasetEntry):
+    """focoos/ports.py ClassificationDatasetDict: ``label`` = the image's class indices (multi-label); ``annotations`` with ``category_id``
+    is read when ``label`` is absent (ClassificationEvaluator.process)."""
+    label: Optional[List[int]] = None
+    annotations: Optional[list] = None
 
 
 @dataclass
