@@ -28,6 +28,21 @@ class FxConvDesc(C.Structure):
     ]
 
 
+def conv_frag_eligible(n: int, c: int, k: int, c32: bool = True) -> bool:
+    """1 iff a k x k convolution with ``n`` output and ``c`` input channels gets a weight copy in MFMA fragment order
+    (FxConvDesc.w_frag), i.e. can reach the fragment-order kernels of fx_conv2d_nhwc_bf16: 3x3 with N in {64, 128} or N % 256 == 0 and
+    C % 64 == 0 (conv3x3_kplane / conv3x3_flat / conv3x3s2_kplane), 1x1 with C, N multiples of 256 (pw_kplane / pw_flat) and, where
+    ``c32``, 3x3 with C = 32 and N in {32, 64} (the ResNet-vd stem's conv1_2 / conv1_3 on conv3x3_c32).  For an input-gradient
+    convolution ``n`` and ``c`` are those of the convolution that USES the weight image (swapped)."""
+    if k == 1:
+        return n % 256 == 0 and c % 256 == 0
+    if k != 3:
+        return False
+    if c == 32:
+        return c32 and n in (32, 64)
+    return (n in (64, 128) or n % 256 == 0) and c % 64 == 0
+
+
 class FxPackEntry(C.Structure):
     """include/focoos_amd.h fx_pack_entry"""
     _fields_ = [

@@ -218,8 +218,7 @@ bool fx_conv3x3_c32_supported(int C, int N, int W, int mode) {
   return C == 32 && (N == 32 || N == 64) && (mode == 0 || mode == 3) && 512 + 2 * W + 2 <= 1344;
 }
 
-int fx_launch_conv3x3_c32(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream) {
-  const int mode = fx_c3_epilogue_mode(c.act, c.res != nullptr, c.res_after);
+int fx_launch_conv3x3_c32(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream) {
   if (!fx_conv3x3_c32_supported(c.C, c.N, c.W, mode) || c.y_bstride) return FX_ERR_UNSUPPORTED;
   C32Args a{};
   a.x = c.x; a.wp = w_frag; a.bias = c.bias; a.y = reinterpret_cast<bf16_t*>(c.y);

@@ -330,14 +330,18 @@ int fx_c3_epilogue_mode(int act, bool has_res, int res_after) {
   return -1;
 }
 
-// 1 iff fx_conv2d_nhwc_bf16 routes this 3x3 shape to the halo kernel (the halo tile must fit the 160 KiB LDS)
-extern "C" int fx_conv3x3_flat_supported(int C, int N, int W) {
-  if (fx_conv3x3_kplane_supported(C, N, W) || fx_conv3x3_c32_supported(C, N, W, 0)) return 1;
-  if (C % 64 != 0 || !(N == 64 || N == 128 || N == 256)) return 0;
+// 1 iff the flat halo kernel covers (C, N, W): its halo tile must fit the 160 KiB LDS
+bool fx_conv3x3_flat_fits(int C, int N, int W) {
+  if (C % 64 != 0 || !(N == 64 || N == 128 || N == 256)) return false;
   const int BM = N == 256 ? 128 : 256;
   const int HLp = (BM + 2 * W + 2 + 7) / 8 * 8;
   const int halo = (C / 64 > 1 ? 2 : 1) * HLp * 128 + 128, tile = BM * N * 2;
-  return (halo > tile ? halo : tile) <= 160 * 1024 ? 1 : 0;
+  return (halo > tile ? halo : tile) <= 160 * 1024;
+}
+
+// 1 iff some kernel of the halo class (conv3x3_c32, conv3x3_kplane or the flat halo kernel) covers this 3x3 / stride-1 shape
+extern "C" int fx_conv3x3_flat_supported(int C, int N, int W) {
+  return (fx_conv3x3_kplane_supported(C, N, W) || fx_conv3x3_c32_supported(C, N, W, 0) || fx_conv3x3_flat_fits(C, N, W)) ? 1 : 0;
 }
 
 static void c3_fill(C3Args& a, const ConvArgs& c, const bf16_t* w_frag) {
@@ -347,21 +351,11 @@ static void c3_fill(C3Args& a, const ConvArgs& c, const bf16_t* w_frag) {
   a.x_bytes = c.x_bytes; a.r_bytes = c.r_bytes;
 }
 
-int fx_launch_conv3x3_flat(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream) {
-  // round 3: the k-plane kernel (conv3x3_kplane.hip) wherever its plane fits the LDS; FX_C3_KPLANE=0 keeps the round-2 kernel
-  // below for A/B runs.  (What was tried on this kernel before the rewrite - consumers issuing the chunk DMA themselves for
-  // 8-wave / 256-register tiles - is in the history of scripts/probes/c3_probe.hip and profiles/r03_c3_probe_*.txt: LDS-DMA and
-  // register loads of one wave do not retire in order, so counted vmcnt waits over a mixed queue read stale fragments under load.)
-  static const int kplane_on = fx_tune("FX_C3_KPLANE", 1);
-  if (c.C == 32) return fx_launch_conv3x3_c32(c, w_frag, stream);
-  // round 5: the 64 -> 64 layers (res2 branch2b) on the LDS-resident-filter kernel (conv3x3_c64.hip)
-  if (fx_conv3x3_c64_supported(c.C, c.N, fx_c3_epilogue_mode(c.act, c.res != nullptr, c.res_after)) && !c.y_bstride) return fx_launch_conv3x3_c64(c, w_frag, stream);
-  if (kplane_on && fx_conv3x3_kplane_supported(c.C, c.N, c.W)) return fx_launch_conv3x3_kplane(c, w_frag, stream);
+int fx_launch_conv3x3_flat(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream) {
   C3Args a;
   c3_fill(a, c, w_frag);
   // 4 consumer waves + the loader, one workgroup per CU; 2 x 4 accumulator blocks per wave where N allows (operand economy:
   // 2 weight + 4 pixel fragments per 8 MFMAs).  N = 64: 256 pixels x 64 channels; 128: 256 x 128; 256: 128 pixels x 256 channels.
-  const int mode = fx_c3_epilogue_mode(c.act, c.res != nullptr, c.res_after);
 #define FX_C3_TILE(ACT_, RM_)                                                      \
   {                                                                                \
     if (c.N == 64) return launch_c3<9, 64, 1, 4, 2, 2, ACT_, RM_>(a, stream);      \
@@ -380,16 +374,10 @@ int fx_launch_conv3x3_flat(const ConvArgs& c, const bf16_t* w_frag, hipStream_t 
 }
 
 // Pointwise (1x1) layers with C % 256 == 0 and N % 256 == 0: 128 pixels x 256 channels per workgroup, K in 256-channel chunks
-int fx_launch_pw_flat(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream) {
-  // round 3: layers whose reduction fits the LDS (K = 256 / 512) on the resident-tile kernel (conv_pw_kplane.hip); FX_PW_KPLANE=0
-  // keeps the round-2 kernel below for A/B runs
-  static const int kplane_on = fx_tune("FX_PW_KPLANE", 1);
-  if (kplane_on && fx_pw_kplane_supported(c.C, c.N, fx_c3_epilogue_mode(c.act, c.res != nullptr, c.res_after)) && c.N * 4 + 128 * c.C * 2 <= 160 * 1024)
-    return fx_launch_pw_kplane(c, w_frag, stream);
+int fx_launch_pw_flat(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream) {
   C3Args a;
   c3_fill(a, c, w_frag);
   static const int no_loader = fx_tune("FX_PW_NO_LOADER", 1);
-  const int mode = fx_c3_epilogue_mode(c.act, c.res != nullptr, c.res_after);
   if (c.C == 256 && no_loader) {   // K = one chunk: 4-wave workgroups, two per CU
     switch (mode) {
       case 0: return launch_c3<1, 256, 2, 4, 4, 1, FX_ACT_RELU, 0, 0>(a, stream);

@@ -425,10 +425,15 @@ static int launch_c3k(C3KArgs& a, hipStream_t stream) {
 // Tiles: N a multiple of 256: 128 pixels x 256 channels (4 waves side by side over N); N = 128: 256 x 128 (2 x 2 waves);
 // N = 64: 512 x 64 (4 waves over M, all four reading the same weight fragments - the whole filter is 72 KiB, L1/L2 resident).
 // Plane heights: the smallest instantiated HLP >= BM + 2W + 2 whose buffers fit the 160 KiB LDS.
+int fx_c3k_small_m_max() {
+  static const int thr = fx_tune("FX_C3K_SMALL_M", 16000);
+  return thr;
+}
+
 // small-M form of the N % 256 tile: 64 pixels x 256 channels (2 x 2 accumulator blocks per wave) - twice the workgroups for the
 // 20x20-level layers (M = 6 400 per 16-image part: 50 -> 100 pixel tiles), each with half the MFMA work
 static bool c3k_small_m(int M, int N, int W, int C) {
-  static const int thr = fx_tune("FX_C3K_SMALL_M", 16000);
+  const int thr = fx_c3k_small_m_max();
   // round 6: for C <= 256 (the hybrid encoder's 20x20 level: four chunks per tile) the limit can be set apart (FX_C3K_SMALL_M_C256; default = the
   // general one) - under three batches in flight the 128-pixel tiles were +1 % for RT-DETR at M = 12 800 while BiSeNetFormer's 512-channel
   // layers of the same M lost 15 % on them
@@ -452,16 +457,15 @@ static int c3k_plan(int C, int N, int W) {   // 0: not covered, else HLP
   return 0;
 }
 
-extern "C" int fx_conv3x3_kplane_supported(int C, int N, int W) { return c3k_plan(C, N, W) ? 1 : 0; }
+bool fx_conv3x3_kplane_supported(int C, int N, int W) { return c3k_plan(C, N, W) != 0; }
 
-int fx_launch_conv3x3_kplane(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream) {
+int fx_launch_conv3x3_kplane(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream) {
   const int hlp = c3k_plan(c.C, c.N, c.W);
   if (!hlp) return FX_ERR_UNSUPPORTED;
   C3KArgs a{};
   a.x = c.x; a.wp = w_frag; a.bias = c.bias; a.res = c.res; a.y = reinterpret_cast<bf16_t*>(c.y);
   a.H = c.H; a.W = c.W; a.C = c.C; a.N = c.N; a.ldx = c.ldx; a.ldy = c.ldy; a.ldr = c.ldr; a.M = c.M;
   a.HW = c.Ho * c.Wo; a.y_bstride = c.y_bstride; a.x_bytes = c.x_bytes; a.r_bytes = c.r_bytes; a.dbg = nullptr;
-  const int mode = fx_c3_epilogue_mode(c.act, c.res != nullptr, c.res_after);
   const bool small = c3k_small_m(c.M, c.N, c.W, c.C);
   // res2's 3x3 layers (64 -> 64, one chunk, no residual): 256-pixel tiles on four waves, no loader, two workgroups per CU
   static const int duo_on = fx_tune("FX_C3K_DUO", 1);
@@ -477,11 +481,8 @@ int fx_launch_conv3x3_kplane(const ConvArgs& c, const bf16_t* w_frag, hipStream_
   static const int duo256_min_m = fx_tune("FX_C3K_DUO256_MIN_M", 40000);
   static const int duo256_res = fx_tune("FX_C3K_DUO256_RES", 1);   // also the layers WITH a residual (the output tile goes through LDS: 64 KiB per workgroup)
   const bool duo256 = duo256_min_m > 0 && c.M >= duo256_min_m && (!c.res || duo256_res) && c.N % 256 == 0;   // hlp 320 (W <= 95) and 576 (MaskFormer's 200-wide level: one 74 KiB buffer, two per CU)
-  static const int duo128_on = fx_tune("FX_C3K_DUO128", 0);   // N = 128 (res3's branch2b): 256 x 128 tiles, one 66 KiB buffer
-  const bool duo128 = duo128_on && duo256_min_m > 0 && c.M >= duo256_min_m && c.N == 128 && (!c.res || duo256_res);
 #define FX_C3K_TILE(ACT_, RM_)                                                             \
   {                                                                                        \
-    if (duo128) return launch_c3k<2, 4, 2, 2, 512, ACT_, RM_, 0, 0>(a, stream);            \
     if (duo256 && hlp == 320) return launch_c3k<2, 4, 4, 1, 320, ACT_, RM_, 0, 0>(a, stream); \
     if (duo256) return launch_c3k<2, 4, 4, 1, 576, ACT_, RM_, 0, 0>(a, stream);            \
     if (small) return launch_c3k<2, 2, 4, 1, 192, ACT_, RM_>(a, stream);                   \

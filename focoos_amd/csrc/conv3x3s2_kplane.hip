@@ -317,9 +317,8 @@ static int launch_c3s2(C3S2Args& a, hipStream_t stream) {
 // 20x20-level layer), N = 128: 256 x 128.  Returns the plane height HLP of the instance that covers (C, N, Wo, M), 0: none.
 static int c3s2_plan(int C, int N, int Wo, int M) {
   if (C % 64 != 0 || Wo < 1) return 0;
-  static const int small_thr = fx_tune("FX_C3K_SMALL_M", 16000);
   if (N > 0 && N % 256 == 0) {
-    if (M <= small_thr && 64 + Wo + 1 <= 128) return 128;
+    if (M <= fx_c3k_small_m_max() && 64 + Wo + 1 <= 128) return 128;
     if (128 + Wo + 1 <= 192) return 192;
     if (128 + Wo + 1 <= 256) return 256;
     return 0;
@@ -330,14 +329,13 @@ static int c3s2_plan(int C, int N, int Wo, int M) {
 
 bool fx_conv3x3s2_kplane_supported(int C, int N, int Wo, int M) { return c3s2_plan(C, N, Wo, M) != 0; }
 
-int fx_launch_conv3x3s2_kplane(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream) {
+int fx_launch_conv3x3s2_kplane(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream) {
   const int hlp = c3s2_plan(c.C, c.N, c.Wo, c.M);
   if (!hlp || c.res || c.H != 2 * c.Ho || c.W != 2 * c.Wo || c.stride != 2 || c.KH != 3 || c.KW != 3 || c.pad != 1) return FX_ERR_UNSUPPORTED;
   C3S2Args a{};
   a.x = c.x; a.wp = w_frag; a.bias = c.bias; a.y = reinterpret_cast<bf16_t*>(c.y);
   a.Ho = c.Ho; a.Wo = c.Wo; a.C = c.C; a.N = c.N; a.ldx = c.ldx; a.ldy = c.ldy; a.M = c.M;
   a.HW = c.Ho * c.Wo; a.y_bstride = c.y_bstride; a.x_bytes = c.x_bytes;
-  const int mode = fx_c3_epilogue_mode(c.act, false, 0);
 #define FX_C3S2_TILE(ACT_)                                                             \
   {                                                                                     \
     if (c.N == 128) return launch_c3s2<2, 4, 2, 2, 384, ACT_, 1>(a, stream);            \

@@ -48,27 +48,32 @@ __device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned b
 #define FX_OOB 0xFFFFFFF0u
 
 
+// Every launcher of a routed kernel family has this signature: the validated arguments, the fragment-order weight copy (NULL for the
+// implicit-GEMM kernels) and the epilogue mode conv_route computed (fx_c3_epilogue_mode).  conv_route (conv_igemm.hip) alone chooses
+// the family; a launcher chooses only among the tile forms of its own family.
+typedef int (*ConvLauncher)(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream);
+int fx_c3_epilogue_mode(int act, bool has_res, int res_after);  // epilogue variant (3x3 kernels: 0-3, 5; pointwise: 0, 1, 3-6), -1: none
+
 // conv_igemm_dma.hip: 8-wave 256-row tiles fed by buffer_load ... lds DMA (deep-K, large-M layers)
-bool fx_conv_dma_eligible(const ConvArgs& a);
-int fx_launch_conv_dma(ConvArgs& a, hipStream_t stream);
+int fx_conv_dma_bn(const ConvArgs& a);   // BN of the DMA tile that covers the layer (256 / 128), 0: not eligible
+int fx_launch_conv_dma256(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream);
+int fx_launch_conv_dma128(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream);
 
 // conv3x3_flat.hip: 3x3 / stride 1 / pad 1 without im2col re-fetching (flat halo tile, loader wave, fragment-ordered weights)
 extern "C" int fx_conv3x3_flat_supported(int C, int N, int W);
-int fx_launch_conv3x3_flat(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream);
+bool fx_conv3x3_flat_fits(int C, int N, int W);
+int fx_launch_conv3x3_flat(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream);
+int fx_launch_pw_flat(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream);  // 1x1, C % 256 == 0, N % 256 == 0
 // conv3x3_kplane.hip: the round-3 form of the same layer class (k-plane LDS layout, immediate-offset fragment reads, direct stores)
-extern "C" int fx_conv3x3_kplane_supported(int C, int N, int W);
-int fx_launch_conv3x3_kplane(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream);
+bool fx_conv3x3_kplane_supported(int C, int N, int W);
+int fx_c3k_small_m_max();   // FX_C3K_SMALL_M: largest M on the 64-pixel tiles of the k-plane kernels (stride 1 and 2)
+int fx_launch_conv3x3_kplane(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream);
 // conv3x3s2_kplane.hip: 3x3 / stride 2 / pad 1 as a stride-1 correlation over the four parity planes of the input (round 4)
 bool fx_conv3x3s2_kplane_supported(int C, int N, int Wo, int M);
-int fx_launch_conv3x3s2_kplane(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream);
+int fx_launch_conv3x3s2_kplane(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream);
 // conv_pw_kplane.hip: pointwise layers with the whole reduction resident in LDS (K = 256 / 512), one workgroup per pixel tile over all N
 bool fx_pw_kplane_supported(int C, int N, int mode);
-int fx_launch_pw_kplane(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream);
+int fx_launch_pw_kplane(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream);
 // conv3x3_c32.hip: 3x3 / s1 with 32 input channels (the ResNet-vd stem layers conv1_2 / conv1_3): one-chunk k-plane kernel, 4 waves, two per CU
 bool fx_conv3x3_c32_supported(int C, int N, int W, int mode);
-int fx_launch_conv3x3_c32(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream);
-// conv3x3_c64.hip: 3x3 / s1 with 64 input and 64 output channels, no residual (res2 branch2b): 2-D tiles, the whole filter LDS-resident (round 5)
-bool fx_conv3x3_c64_supported(int C, int N, int mode);
-int fx_launch_conv3x3_c64(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream);
-int fx_c3_epilogue_mode(int act, bool has_res, int res_after);  // epilogue variant (3x3 kernel: 0-3, 5; pointwise: 0, 1, 3-6), -1: none
-int fx_launch_pw_flat(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream);  // 1x1, C % 256 == 0, N % 256 == 0
+int fx_launch_conv3x3_c32(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream);

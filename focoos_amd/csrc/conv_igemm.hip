@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256, (BK == 32 ? 4 : 2)) void conv_igemm_kernel(con
 }
 
 template <int BM, int BN, int BK, int WM, int WN, bool POOL, int NSTAGE = 2>
-static int launch_conv(ConvArgs& a, hipStream_t stream) {
+static int launch_conv(const ConvArgs& c, const bf16_t*, int, hipStream_t stream) {
   constexpr int STAGE = (BM + BN) * BK * 2;
   constexpr int EPI = 64 * (BN + 4) * 4;  // the epilogue stages 64 rows at a time
   constexpr int SMEM = (NSTAGE * STAGE > EPI) ? NSTAGE * STAGE : EPI;
@@ -262,6 +262,7 @@ static int launch_conv(ConvArgs& a, hipStream_t stream) {
       return FX_ERR_RUNTIME;
     attr_set = true;
   }
+  ConvArgs a = c;
   a.nNt = (a.N + BN - 1) / BN;
   int nMt = (a.M + BM - 1) / BM;
   dim3 grid(nMt * a.nNt), block(256);
@@ -325,41 +326,76 @@ static int conv_prepare(const fx_conv_desc* d, ConvArgs& a) {
   return FX_OK;
 }
 
-// Which kernel runs a layer - ONE routing function for the launch and for the label bench.py reports (fx_conv2d_variant).
-enum ConvRoute { R_C3_FLAT, R_C3_S2, R_PW_FLAT, R_SMALL_M, R_DMA, R_POOL, R_K64_N128, R_K64_N64, R_K64_N32, R_K32_N128, R_K32_N64, R_K32_N32, R_UNSUPPORTED };
+// Which kernel runs a layer: conv_route returns one entry of kRoutes, whose launcher fx_conv2d_nhwc_bf16 calls and whose label
+// fx_conv2d_variant writes (what bench.py groups its per-kernel roofline by) - the label names the kernel family that runs by
+// construction.  A family launcher picks only among its own tile forms, which the labels do not tell apart.
+enum ConvRoute {
+  R_C32, R_C3K, R_C3_FLAT, R_C3_S2, R_PWK, R_PW_FLAT, R_SMALL_M, R_DMA256, R_DMA128, R_POOL,
+  R_K64_N128, R_K64_N64, R_K64_N32, R_K32_N128, R_K32_N64, R_K32_N32, R_UNSUPPORTED
+};
 
-static ConvRoute conv_route(const fx_conv_desc* d, const ConvArgs& a) {
-  // Layers with a fragment-ordered weight copy: 3x3 / stride 1 -> halo kernel (pixels fetched once for all nine taps);
-  // 1x1 with C, N multiples of 256 -> the same machinery with 256-channel LDS rows (conv3x3_flat.hip)
-  // (the two size thresholds are re-read per call - a getenv each, nothing under graph replay - so that kernel tests can route
-  // small shapes here while the end-to-end tests keep the production routing)
-  static const int c3_on = fx_tune("FX_CONV3_FLAT", 1), pw_on = fx_tune("FX_PW_FLAT", 1);
+static const struct {
+  const char* label;   // printf format; %d = N, or C where `by_c`
+  bool by_c;
+  ConvLauncher launch;
+} kRoutes[R_UNSUPPORTED] = {   // indexed by ConvRoute
+    /* R_C32      */ {"conv3x3_c32<%d>", false, fx_launch_conv3x3_c32},
+    /* R_C3K      */ {"conv3x3_kplane<%d>", false, fx_launch_conv3x3_kplane},
+    /* R_C3_FLAT  */ {"conv3x3_flat<%d>", false, fx_launch_conv3x3_flat},
+    /* R_C3_S2    */ {"conv3x3s2_kplane<%d>", false, fx_launch_conv3x3s2_kplane},
+    /* R_PWK      */ {"pw_kplane<K%d>", true, fx_launch_pw_kplane},
+    /* R_PW_FLAT  */ {"pw_flat<K%d>", true, fx_launch_pw_flat},
+    /* R_SMALL_M  */ {"conv_igemm<64,64,256,1stage>", false, launch_conv<64, 64, 256, 2, 2, false, 1>},
+    /* R_DMA256   */ {"conv_igemm_dma<256,256>", false, fx_launch_conv_dma256},
+    /* R_DMA128   */ {"conv_igemm_dma<256,128>", false, fx_launch_conv_dma128},
+    /* R_POOL     */ {"conv_igemm<128,128,64,pool>", false, launch_conv<128, 128, 64, 2, 2, true>},
+    /* R_K64_N128 */ {"conv_igemm<128,128,64>", false, launch_conv<128, 128, 64, 2, 2, false>},
+    /* R_K64_N64  */ {"conv_igemm<128,64,64>", false, launch_conv<128, 64, 64, 2, 2, false>},
+    /* R_K64_N32  */ {"conv_igemm<128,32,64>", false, launch_conv<128, 32, 64, 4, 1, false>},
+    /* R_K32_N128 */ {"conv_igemm<128,128,32>", false, launch_conv<128, 128, 32, 2, 2, false>},
+    /* R_K32_N64  */ {"conv_igemm<128,64,32>", false, launch_conv<128, 64, 32, 2, 2, false>},
+    /* R_K32_N32  */ {"conv_igemm<128,32,32>", false, launch_conv<128, 32, 32, 4, 1, false>},
+};
+
+// `mode`: the epilogue variant of the descriptor (fx_c3_epilogue_mode), computed once by the caller and passed to the launcher.
+static ConvRoute conv_route(const fx_conv_desc* d, const ConvArgs& a, int mode) {
+  // The fragment-order kernels need the weight copy and a plain bf16 output (the mask and the pooled input are implicit-GEMM only)
+  const bool frag = d->w_frag && ((uintptr_t)d->w_frag % 16) == 0 && !d->mask && !d->pool2 && !d->out_f32;
+  // (the two size thresholds are re-read per call - a getenv each, nothing under graph replay - so that kernel tests can route small
+  // shapes to the fragment-order kernels while the end-to-end tests keep the production routing)
   // 5 000 pixels (round 3; was 20 000): with two concurrent half-batch parts a layer's own latency matters less than the CU time it
   // occupies - the 20x20-level layers (M = 6 400 per part) fill only 50-100 workgroups of the flat kernels, but those run at 2-3x the
   // per-CU rate of the implicit-GEMM tiles and the other part's launches take the idle CUs: RT-DETR 3883 -> 3990 img/s
   // (profiles/r03_threshold_sweep.txt); one part alone (FX_STREAMS=1) 3334 -> 3420
   const int c3_min_m = fx_tune("FX_CONV3_MIN_M", 5000), pw_min_m = fx_tune("FX_PW_MIN_M", 5000);
-  if (!d->mask && d->w_frag && ((uintptr_t)d->w_frag % 16) == 0 && d->stride == 1 && !d->pool2 && !d->out_f32) {
-    const int mode = fx_c3_epilogue_mode(d->act, d->residual != nullptr, d->residual_after_act);
-    static const int c32_on = fx_tune("FX_C3_C32", 1);
-    if (c3_on && d->KH == 3 && d->KW == 3 && d->pad == 1 && !d->y_batch_stride && ((mode >= 0 && mode <= 3) || mode == 5) && a.M >= c3_min_m &&
-        fx_conv3x3_flat_supported(d->C, d->N, d->W) && (d->C != 32 || (c32_on && fx_conv3x3_c32_supported(d->C, d->N, d->W, mode))))
+  // 3x3 / stride 1 (halo class: the pixels are fetched once for all nine taps).  Round 3: the k-plane kernel (conv3x3_kplane.hip) wherever
+  // its plane fits the LDS, the 32-channel stem layers on conv3x3_c32.hip; FX_C3_KPLANE=0 keeps the round-2 flat halo kernel for A/B runs.
+  // (What was tried on the flat kernel before the rewrite - consumers issuing the chunk DMA themselves for 8-wave / 256-register tiles - is
+  // in the history of scripts/probes/c3_probe.hip and profiles/r03_c3_probe_*.txt: LDS-DMA and register loads of one wave do not retire
+  // in order, so counted vmcnt waits over a mixed queue read stale fragments under load.)
+  static const int c3_on = fx_tune("FX_CONV3_FLAT", 1), c3k_on = fx_tune("FX_C3_KPLANE", 1), c32_on = fx_tune("FX_C3_C32", 1);
+  if (frag && c3_on && d->stride == 1 && d->KH == 3 && d->KW == 3 && d->pad == 1 && !d->y_batch_stride &&
+      ((mode >= 0 && mode <= 3) || mode == 5) && a.M >= c3_min_m) {
+    if (d->C == 32) {
+      if (c32_on && fx_conv3x3_c32_supported(d->C, d->N, d->W, mode)) return R_C32;
+    } else if (c3k_on && fx_conv3x3_kplane_supported(d->C, d->N, d->W)) {
+      return R_C3K;
+    } else if (fx_conv3x3_flat_fits(d->C, d->N, d->W)) {
       return R_C3_FLAT;
-    // pointwise (FX_PW_SMALL_TILES = t > 0: below 20 000 pixels only layers with >= t (pixel tile x 256-channel tile) pairs - the narrow
-    // 20x20-level layers are faster on the 64x64-tile kernels in isolation (serial kernel sum 10.34 -> 10.25 ms at t = 200), but the
-    // two-part step is not: 4190 vs 4170 img/s, profiles/r03_threshold_sweep.txt - so the rule is off)
-    if (pw_on && d->KH == 1 && d->KW == 1 && d->pad == 0 && d->C % 256 == 0 && d->N % 256 == 0 && a.M >= pw_min_m &&
-        (a.M >= 20000 || (int64_t)((a.M + 127) / 128) * (d->N / 256) >= fx_tune("FX_PW_SMALL_TILES", 0)) && (mode == 0 || mode == 1 || (mode >= 3 && mode <= 6)))
-      return R_PW_FLAT;
+    }
   }
+  // 1x1 with C, N multiples of 256: round 3: layers whose reduction fits the LDS (K = 256 / 512) on the resident-tile kernel
+  // (conv_pw_kplane.hip; FX_PW_KPLANE=0: the round-2 kernel for A/B runs), the deeper ones on the flat kernel's 256-channel LDS rows
+  static const int pw_on = fx_tune("FX_PW_FLAT", 1), pwk_on = fx_tune("FX_PW_KPLANE", 1);
+  if (frag && pw_on && d->stride == 1 && d->KH == 1 && d->KW == 1 && d->pad == 0 && d->C % 256 == 0 && d->N % 256 == 0 && a.M >= pw_min_m &&
+      (mode == 0 || mode == 1 || (mode >= 3 && mode <= 6)))
+    return (pwk_on && fx_pw_kplane_supported(d->C, d->N, mode)) ? R_PWK : R_PW_FLAT;
   // 3x3 / stride 2 (branch2b of the first block of res3 / res4 / res5): k-plane kernel over the parity planes of the input
   // (conv3x3s2_kplane.hip; FX_C3S2_KPLANE=0: the implicit-GEMM tiles of rounds 1-3)
   static const int s2_on = fx_tune("FX_C3S2_KPLANE", 1);
-  if (s2_on && !d->mask && d->w_frag && ((uintptr_t)d->w_frag % 16) == 0 && d->stride == 2 && d->KH == 3 && d->KW == 3 && d->pad == 1 && !d->pool2 &&
-      !d->out_f32 && !d->residual && d->H == 2 * d->Ho && d->W == 2 * d->Wo && a.M >= c3_min_m) {
-    const int mode = fx_c3_epilogue_mode(d->act, false, 0);
-    if ((mode == 0 || mode == 1 || mode == 3) && fx_conv3x3s2_kplane_supported(d->C, d->N, d->Wo, a.M)) return R_C3_S2;
-  }
+  if (frag && s2_on && d->stride == 2 && d->KH == 3 && d->KW == 3 && d->pad == 1 && !d->residual && d->H == 2 * d->Ho && d->W == 2 * d->Wo &&
+      a.M >= c3_min_m && (mode == 0 || mode == 1 || mode == 3) && fx_conv3x3s2_kplane_supported(d->C, d->N, d->Wo, a.M))
+    return R_C3_S2;
   // BK=64 (2 workgroups/CU, 64 KiB LDS) for deep-K compute-bound layers; BK=32 (4 workgroups/CU, 34 KiB LDS: more
   // tiles and bytes in flight per CU) for the short-K layers, which are HBM/latency-bound.
   static const int k64_min = fx_tune("FX_K64_MIN_KTOT", FX_K64_MIN_KTOT);
@@ -369,33 +405,23 @@ static ConvRoute conv_route(const fx_conv_desc* d, const ConvArgs& a) {
   // (Ktot <= 2048 since round 4: MaskFormer-L's FFN linear2 - 800 rows, K = 2048 - took 45 us on 14 workgroups of the 128 x 128 tiles)
   static const int small_k = fx_tune("FX_SMALL_M_KTOT", 2048);
   if (!d->pool2 && a.M <= small_m && d->C % 256 == 0 && a.Ktot <= small_k) return R_SMALL_M;
-  const bool k64 = (d->C % 64 == 0) && (a.Ktot >= k64_min);
-  if (!d->pool2 && !d->mask && fx_conv_dma_eligible(a)) return R_DMA;
+  if (!d->pool2 && !d->mask) {
+    const int bn = fx_conv_dma_bn(a);
+    if (bn) return bn == 256 ? R_DMA256 : R_DMA128;
+  }
   if (d->pool2) return d->C % 64 != 0 ? R_UNSUPPORTED : R_POOL;
-  if (k64) return d->N > 64 ? R_K64_N128 : (d->N > 32 ? R_K64_N64 : R_K64_N32);
+  if ((d->C % 64 == 0) && (a.Ktot >= k64_min)) return d->N > 64 ? R_K64_N128 : (d->N > 32 ? R_K64_N64 : R_K64_N32);
   return d->N > 64 ? R_K32_N128 : (d->N > 32 ? R_K32_N64 : R_K32_N32);
 }
 
-extern "C" int fx_conv2d_nhwc_bf16(const fx_conv_desc* d, fx_stream_t stream_) {
+extern "C" int fx_conv2d_nhwc_bf16(const fx_conv_desc* d, fx_stream_t stream) {
   ConvArgs a;
   const int rc = conv_prepare(d, a);
   if (rc != FX_OK) return rc;
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  switch (conv_route(d, a)) {
-    case R_C3_FLAT: return fx_launch_conv3x3_flat(a, reinterpret_cast<const bf16_t*>(d->w_frag), stream);
-    case R_C3_S2: return fx_launch_conv3x3s2_kplane(a, reinterpret_cast<const bf16_t*>(d->w_frag), stream);
-    case R_PW_FLAT: return fx_launch_pw_flat(a, reinterpret_cast<const bf16_t*>(d->w_frag), stream);
-    case R_SMALL_M: return launch_conv<64, 64, 256, 2, 2, false, 1>(a, stream);
-    case R_DMA: return fx_launch_conv_dma(a, stream);
-    case R_POOL: return launch_conv<128, 128, 64, 2, 2, true>(a, stream);
-    case R_K64_N128: return launch_conv<128, 128, 64, 2, 2, false>(a, stream);
-    case R_K64_N64: return launch_conv<128, 64, 64, 2, 2, false>(a, stream);
-    case R_K64_N32: return launch_conv<128, 32, 64, 4, 1, false>(a, stream);
-    case R_K32_N128: return launch_conv<128, 128, 32, 2, 2, false>(a, stream);
-    case R_K32_N64: return launch_conv<128, 64, 32, 2, 2, false>(a, stream);
-    case R_K32_N32: return launch_conv<128, 32, 32, 4, 1, false>(a, stream);
-    default: return FX_ERR_UNSUPPORTED;
-  }
+  const int mode = fx_c3_epilogue_mode(a.act, a.res != nullptr, a.res_after);
+  const ConvRoute r = conv_route(d, a, mode);
+  if (r == R_UNSUPPORTED) return FX_ERR_UNSUPPORTED;
+  return kRoutes[r].launch(a, reinterpret_cast<const bf16_t*>(d->w_frag), mode, reinterpret_cast<hipStream_t>(stream));
 }
 
 // The label of the kernel fx_conv2d_nhwc_bf16 would run for this descriptor (pointers only checked for presence / alignment): what
@@ -405,33 +431,8 @@ extern "C" int fx_conv2d_variant(const fx_conv_desc* d, char* out, int cap) {
   ConvArgs a;
   const int rc = conv_prepare(d, a);
   if (rc != FX_OK) return rc;
-  switch (conv_route(d, a)) {
-    case R_C3_FLAT: {   // the same decision fx_launch_conv3x3_flat takes
-      static const int kplane_on = fx_tune("FX_C3_KPLANE", 1);
-      const bool c64 = fx_conv3x3_c64_supported(d->C, d->N, fx_c3_epilogue_mode(d->act, d->residual != nullptr, d->residual_after_act)) && !d->y_batch_stride;
-      const char* fmt = d->C == 32 ? "conv3x3_c32<%d>" : (c64 ? "conv3x3_c64<%d>" : ((kplane_on && fx_conv3x3_kplane_supported(d->C, d->N, d->W)) ? "conv3x3_kplane<%d>" : "conv3x3_flat<%d>"));
-      snprintf(out, cap, fmt, d->N);
-      break;
-    }
-    case R_PW_FLAT: {
-      static const int pwk_on = fx_tune("FX_PW_KPLANE", 1);
-      const int mode = fx_c3_epilogue_mode(d->act, d->residual != nullptr, d->residual_after_act);
-      const bool res_tile = d->residual != nullptr;
-      const bool kp = pwk_on && fx_pw_kplane_supported(d->C, d->N, mode) && d->N * 4 + 128 * d->C * 2 <= 160 * 1024;
-      snprintf(out, cap, kp ? "pw_kplane<K%d>" : "pw_flat<K%d>", d->C);
-      break;
-    }
-    case R_C3_S2: snprintf(out, cap, "conv3x3s2_kplane<%d>", d->N); break;
-    case R_SMALL_M: snprintf(out, cap, "conv_igemm<64,64,256,1stage>"); break;
-    case R_DMA: snprintf(out, cap, "conv_igemm_dma<256,%d>", d->N % 256 == 0 ? 256 : 128); break;
-    case R_POOL: snprintf(out, cap, "conv_igemm<128,128,64,pool>"); break;
-    case R_K64_N128: snprintf(out, cap, "conv_igemm<128,128,64>"); break;
-    case R_K64_N64: snprintf(out, cap, "conv_igemm<128,64,64>"); break;
-    case R_K64_N32: snprintf(out, cap, "conv_igemm<128,32,64>"); break;
-    case R_K32_N128: snprintf(out, cap, "conv_igemm<128,128,32>"); break;
-    case R_K32_N64: snprintf(out, cap, "conv_igemm<128,64,32>"); break;
-    case R_K32_N32: snprintf(out, cap, "conv_igemm<128,32,32>"); break;
-    default: return FX_ERR_UNSUPPORTED;
-  }
+  const ConvRoute r = conv_route(d, a, fx_c3_epilogue_mode(a.act, a.res != nullptr, a.res_after));
+  if (r == R_UNSUPPORTED) return FX_ERR_UNSUPPORTED;
+  snprintf(out, cap, kRoutes[r].label, kRoutes[r].by_c ? d->C : d->N);
   return FX_OK;
 }

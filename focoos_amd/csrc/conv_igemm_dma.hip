@@ -239,7 +239,7 @@ __global__ __launch_bounds__(WM* WN * 64, 1) void conv_igemm_dma_kernel(const Co
 }
 
 template <int BM, int BN, int WM, int WN>
-static int launch_dma(ConvArgs& a, hipStream_t stream) {
+static int launch_dma(const ConvArgs& c, hipStream_t stream) {
   constexpr int STAGE = (BM + BN) * 128;
   constexpr int EPI = 64 * (BN + 4) * 4;
   constexpr int SMEM = (2 * STAGE > EPI) ? 2 * STAGE : EPI;
@@ -250,6 +250,7 @@ static int launch_dma(ConvArgs& a, hipStream_t stream) {
       return FX_ERR_RUNTIME;
     attr_set = true;
   }
+  ConvArgs a = c;
   a.nNt = (a.N + BN - 1) / BN;
   const int nMt = (a.M + BM - 1) / BM;
   hipLaunchKernelGGL(kern, dim3(nMt * a.nNt), dim3(WM * WN * 64), SMEM, stream, a);
@@ -264,15 +265,13 @@ static int launch_dma(ConvArgs& a, hipStream_t stream) {
 #endif
 
 // Deep-K layers with enough rows to fill the chip with 256-row tiles.  Weights are padded to a multiple of 128
-// rows, so BN = 256 needs N % 256 == 0 (or N <= 128 -> BN = 128).
-bool fx_conv_dma_eligible(const ConvArgs& a) {
+// rows, so BN = 256 needs N % 256 == 0 (else N % 128 == 0 -> BN = 128; FX_DMA_FORCE_BN=128: BN = 128 for every layer).
+int fx_conv_dma_bn(const ConvArgs& a) {
   static const int min_k = fx_tune("FX_DMA_MIN_KTOT", FX_DMA_MIN_KTOT), min_m = fx_tune("FX_DMA_MIN_M", FX_DMA_MIN_M);
-  if (a.C % 64 != 0 || a.Ktot < min_k || a.M < min_m) return false;
-  return (a.N % 256 == 0) || (a.N % 128 == 0);
+  static const int force_bn = fx_tune("FX_DMA_FORCE_BN", 0);
+  if (a.C % 64 != 0 || a.Ktot < min_k || a.M < min_m || a.N % 128 != 0) return 0;
+  return (a.N % 256 == 0 && force_bn != 128) ? 256 : 128;
 }
 
-int fx_launch_conv_dma(ConvArgs& a, hipStream_t stream) {
-  static const int force_bn = fx_tune("FX_DMA_FORCE_BN", 0);
-  if (a.N % 256 == 0 && force_bn != 128) return launch_dma<256, 256, 2, 4>(a, stream);
-  return launch_dma<256, 128, 4, 2>(a, stream);
-}
+int fx_launch_conv_dma256(const ConvArgs& c, const bf16_t*, int, hipStream_t stream) { return launch_dma<256, 256, 2, 4>(c, stream); }
+int fx_launch_conv_dma128(const ConvArgs& c, const bf16_t*, int, hipStream_t stream) { return launch_dma<256, 128, 4, 2>(c, stream); }

@@ -60,7 +60,8 @@ __device__ __forceinline__ float pwk_act(float v, std::integral_constant<int, FX
 // TM: 32-pixel blocks per wave = pixel tile / 32.  4 (128 pixels, two workgroups per CU) or - round 6 - 2 (64 pixels: 32 KiB of LDS at
 // K = 256 and <= 168 registers, THREE workgroups per CU: these layers are HBM-bound, and what a CU can keep in flight towards memory is set by
 // the number of waves that are in a load / store phase, not by its MFMA rate - at 64 pixels a wave issues one memory instruction per MFMA,
-// which would cap an MFMA-bound kernel at half rate and costs nothing here).
+// which would cap an MFMA-bound kernel at half rate and costs nothing here).  Measured ±3 % (profiles/r06_pw_knobs.txt): the library
+// instantiates TM = 4 only; TM = 2 stays for scripts/probes/pw_probe.hip.
 // ABL: ablation switches of scripts/probes/pw_probe.hip (1: weight ring never refilled, 2: no output stores, 4: residual not read,
 //      8: no MFMAs, 16: pixel tile not fetched); 0 in the product.
 template <int K, int ACT, int RESMODE, int TM = 4, int ABL = 0>
@@ -260,11 +261,9 @@ __global__ __launch_bounds__(256, TM == 4 ? 2 : 3) void conv_pw_kplane_kernel(co
 
 template <int K, int ACT, int RESMODE, int TM = 4, int ABL = 0>
 static int launch_pwk(PWKArgs& a, hipStream_t stream) {
-  static const int one_per_cu = fx_tune("FX_PWK_ONE_PER_CU", 0);   // A/B knob: pad the LDS request so that one workgroup owns a CU
   constexpr int BM = TM * 32, BN = 256;
-  int smem = BM * K * 2 + a.N * 4;
+  const int smem = BM * K * 2 + a.N * 4;
   if (smem > 160 * 1024) return FX_ERR_UNSUPPORTED;
-  if (one_per_cu && smem < 96 * 1024) smem = 96 * 1024;
   // n-tiles per workgroup: all of them when the pixel tiles alone fill the chip, else spread over more workgroups (two 64 KiB pixel
   // tiles share a CU)
   const int mt = (a.M + BM - 1) / BM, NT = a.N / BN;
@@ -295,34 +294,12 @@ bool fx_pw_kplane_supported(int C, int N, int mode) {
   return false;
 }
 
-int fx_launch_pw_kplane(const ConvArgs& c, const bf16_t* w_frag, hipStream_t stream) {
-  const int mode = fx_c3_epilogue_mode(c.act, c.res != nullptr, c.res_after);
+int fx_launch_pw_kplane(const ConvArgs& c, const bf16_t* w_frag, int mode, hipStream_t stream) {
   if (!fx_pw_kplane_supported(c.C, c.N, mode)) return FX_ERR_UNSUPPORTED;
   PWKArgs a{};
   a.x = c.x; a.wp = w_frag; a.bias = c.bias; a.res = c.res; a.y = reinterpret_cast<bf16_t*>(c.y);
   a.N = c.N; a.ldx = c.ldx; a.ldy = c.ldy; a.ldr = c.ldr; a.M = c.M;
   a.HW = c.Ho * c.Wo; a.y_bstride = c.y_bstride; a.x_bytes = c.x_bytes; a.r_bytes = c.r_bytes;
-  // 64-pixel tiles (three workgroups per CU) for the layers selected by FX_PWK_BM64: bit 0 = K 256 with a residual (res4's branch2c), bit 1 =
-  // K 256 without, bit 2 = K 512 with a residual (res5's branch2c), bit 3 = K 512 without
-  static const int bm64 = fx_tune("FX_PWK_BM64", 0);
-  const bool has_res = mode >= 4;
-  if (bm64 & (c.C == 256 ? (has_res ? 1 : 2) : (has_res ? 4 : 8))) {
-    if (c.C == 256) {
-      switch (mode) {
-        case 0: return launch_pwk<256, FX_ACT_RELU, 0, 2>(a, stream);
-        case 1: return launch_pwk<256, FX_ACT_SILU, 0, 2>(a, stream);
-        case 3: return launch_pwk<256, FX_ACT_NONE, 0, 2>(a, stream);
-        case 4: return launch_pwk<256, FX_ACT_RELU, 1, 2>(a, stream);
-      }
-    } else {
-      switch (mode) {
-        case 0: return launch_pwk<512, FX_ACT_RELU, 0, 2>(a, stream);
-        case 1: return launch_pwk<512, FX_ACT_SILU, 0, 2>(a, stream);
-        case 3: return launch_pwk<512, FX_ACT_NONE, 0, 2>(a, stream);
-        case 4: return launch_pwk<512, FX_ACT_RELU, 1, 2>(a, stream);
-      }
-    }
-  }
   if (c.C == 256) {
     switch (mode) {
       case 0: return launch_pwk<256, FX_ACT_RELU, 0>(a, stream);

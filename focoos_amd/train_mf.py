@@ -21,7 +21,7 @@ from ._lib import check
 from .engine_maskdec import pos_embed_sine_normalized
 from .train_bf import STDC, Conv1x1, TransformerDecoder, _CriterionHolder
 from .train_nn import (ARENA, DIRECT_GRAD, WEIGHTS_EPOCH, ConvNormLayer, LayerNorm, Linear, MultiheadAttention, ResNetVd, _AddFn, _conv_call,
-                       _conv_input_grad, _conv_param_grads, _frag_eligible, _ptr, _stream, set_norm_mode)
+                       _conv_input_grad, _conv_param_grads, _ptr, _stream, set_norm_mode)
 
 
 class ConvNormFlat(ConvNormLayer):
@@ -92,8 +92,9 @@ class ConvBias(nn.Module):
                 self.w_fwd = torch.zeros(Np, k, k, Cc, dtype=_lib.act_dtype(), device=dev)
                 self.w_dgrad = torch.zeros(Cp, k, k, N, dtype=_lib.act_dtype(), device=dev)
                 self.shift = torch.zeros(Np, dtype=torch.float32, device=dev)
-                self.w_fwd_frag = torch.empty(N * k * k * Cc, dtype=_lib.act_dtype(), device=dev) if _frag_eligible(N, Cc, k) else None
-                self.w_dgrad_frag = torch.empty(N * k * k * Cc, dtype=_lib.act_dtype(), device=dev) if _frag_eligible(Cc, N, k) else None
+                # c32=False: as train_nn.ConvNormLayer (training keeps C = 32 layers on the implicit-GEMM kernels its tests were measured on)
+                self.w_fwd_frag = torch.empty(N * k * k * Cc, dtype=_lib.act_dtype(), device=dev) if _lib.conv_frag_eligible(N, Cc, k, c32=False) else None
+                self.w_dgrad_frag = torch.empty(N * k * k * Cc, dtype=_lib.act_dtype(), device=dev) if _lib.conv_frag_eligible(Cc, N, k, c32=False) else None
             self.shift[:N] = b
             check(self.lib.fx_pack_conv_weights_f32(w.data_ptr(), None, self.w_fwd.data_ptr(), self.w_dgrad.data_ptr(), _ptr(self.w_fwd_frag),
                                                     _ptr(self.w_dgrad_frag), N, Cc, k, k, _stream(dev)), "fx_pack_conv_weights_f32")

@@ -239,14 +239,6 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
-def _frag_eligible(rows: int, cin: int, k: int) -> bool:
-    """Shapes fx_conv2d_nhwc_bf16 can run on the kernels of conv3x3_flat.hip, given the weight copy in fragment order (``rows`` output
-    channels, ``cin`` input channels of the convolution that USES the image - swapped for the input-gradient convolution)."""
-    if k == 3:
-        return (rows in (64, 128) or rows % 256 == 0) and cin % 64 == 0
-    return k == 1 and rows % 256 == 0 and cin % 256 == 0
-
-
 class _ConvBnActFn(torch.autograd.Function):
     """y = act(conv(x, W * s) + (beta - mu * s) [+ residual]) with s = gamma / sqrt(var + eps) frozen."""
 
@@ -645,9 +637,11 @@ class ConvNormLayer(nn.Module):
             if self.w_fwd is None or self.w_fwd.device != dev:
                 self.w_fwd = torch.zeros(Np, k, k, Cc, dtype=_lib.act_dtype(), device=dev)
                 self.w_dgrad = torch.zeros(Cp, k, k, N, dtype=_lib.act_dtype(), device=dev)
+                # c32=False: training keeps the C = 32 stem layers (conv1_2 / conv1_3) on the implicit-GEMM kernels its tests were measured on
                 self.w_fwd_frag = (torch.empty(N * k * k * Cc, dtype=_lib.act_dtype(), device=dev)
-                                   if self.stride == 1 and _frag_eligible(N, Cc, k) else None)
-                self.w_dgrad_frag = torch.empty(N * k * k * Cc, dtype=_lib.act_dtype(), device=dev) if _frag_eligible(Cc, N, k) else None
+                                   if self.stride == 1 and _lib.conv_frag_eligible(N, Cc, k, c32=False) else None)
+                self.w_dgrad_frag = (torch.empty(N * k * k * Cc, dtype=_lib.act_dtype(), device=dev)
+                                     if _lib.conv_frag_eligible(Cc, N, k, c32=False) else None)
         return (w.data_ptr(), None if live else self.scale.data_ptr(), None, self.w_fwd.data_ptr(), self.w_dgrad.data_ptr(),
                 _ptr(self.w_fwd_frag), _ptr(self.w_dgrad_frag), None, N, Cc, k, k, k * k * Cc, k * k * N)
 
@@ -1069,7 +1063,7 @@ class _PackedLinear:
             if self.w_fwd is None or self.w_fwd.device != dev:
                 self.w_fwd = torch.zeros(_rup(Np, 128), 1, 1, Kp, dtype=_lib.act_dtype(), device=dev)
                 self.w_t = torch.zeros(_rup(Kp, 128), 1, 1, Np, dtype=_lib.act_dtype(), device=dev)
-                ok = _frag_eligible(Np, Kp, 1) and Np == N and Kp == K   # 256-multiples both ways: the flat pointwise kernel, forward and input gradient
+                ok = _lib.conv_frag_eligible(Np, Kp, 1) and Np == N and Kp == K   # 256-multiples both ways: the flat pointwise kernel, forward and input gradient
                 self.w_fwd_frag = torch.empty(Np * Kp, dtype=_lib.act_dtype(), device=dev) if ok else None
                 self.w_t_frag = torch.empty(Np * Kp, dtype=_lib.act_dtype(), device=dev) if ok else None
             if self.bias is None or self.bias.device != dev or self.bias.numel() != _rup(Np, 128):
@@ -1127,7 +1121,7 @@ class _PackedLinearGroup:
             self.w_fwd = torch.zeros(_rup(Nt, 128), 1, 1, K, dtype=_lib.act_dtype(), device=dev)
             self.w_t = torch.zeros(_rup(K, 128), 1, 1, Nt, dtype=_lib.act_dtype(), device=dev)
             self.bias = torch.zeros(_rup(Nt, 128), dtype=torch.float32, device=dev)
-            ok = _frag_eligible(Nt, K, 1)
+            ok = _lib.conv_frag_eligible(Nt, K, 1)
             self.w_fwd_frag = torch.empty(Nt * K, dtype=_lib.act_dtype(), device=dev) if ok else None
             self.w_t_frag = torch.empty(Nt * K, dtype=_lib.act_dtype(), device=dev) if ok else None
         return tuple((w.data_ptr(), None, b.data_ptr(), self.w_fwd.data_ptr(), self.w_t.data_ptr(), _ptr(self.w_fwd_frag), _ptr(self.w_t_frag),

@@ -14,12 +14,7 @@
 #include "../../focoos_amd/csrc/conv3x3_flat.hip"
 #include "../../focoos_amd/csrc/conv3x3_kplane.hip"
 
-// entry points of other translation units that conv3x3_flat.hip's dispatcher references (never reached by the probe)
-int fx_launch_pw_kplane(const ConvArgs&, const bf16_t*, hipStream_t) { return FX_ERR_UNSUPPORTED; }
-bool fx_pw_kplane_supported(int, int, int) { return false; }
-int fx_launch_conv3x3_c64(const ConvArgs&, const bf16_t*, hipStream_t) { return FX_ERR_UNSUPPORTED; }
-bool fx_conv3x3_c64_supported(int, int, int) { return false; }
-int fx_launch_conv3x3_c32(const ConvArgs&, const bf16_t*, hipStream_t) { return FX_ERR_UNSUPPORTED; }
+// entry point of another translation unit that conv3x3_flat.hip references (never reached by the probe)
 bool fx_conv3x3_c32_supported(int, int, int, int) { return false; }
 
 int fx_tune(const char* name, int dflt) {

@@ -16,7 +16,6 @@ int fx_tune(const char* name, int dflt) {
   const char* v = getenv(name);
   return v ? atoi(v) : dflt;
 }
-int fx_c3_epilogue_mode(int, bool, int) { return -1; }
 
 #define HIPCHECK(x)                                                                      \
   do {                                                                                   \

@@ -697,7 +697,8 @@ def test_enc_score_head_fused(lib, M, S, K):
     assert (got_sc - full).abs().max().item() <= 3e-2
 
 
-# 3x3 / stride 1 layers on the halo kernel (conv3x3_flat.hip): B,H,W,C,N,act,residual-after-act,ldx pad
+# 3x3 / stride 1 layers on the halo-class kernels (conv3x3_kplane.hip, conv3x3_flat.hip, conv3x3_c32.hip: whichever conv_route picks):
+# B,H,W,C,N,act,residual-after-act,ldx pad
 FLAT_CASES = [
     (2, 24, 20, 64, 64, "relu", False, 0),      # res2 branch2b class: one channel chunk, M = 960 (partial last tile)
     (1, 17, 13, 64, 64, "relu", False, 8),      # odd sizes, M = 221 < one tile, strided input rows
@@ -709,15 +710,16 @@ FLAT_CASES = [
     (5, 6, 7, 64, 256, "relu", False, 0),       # several tiny images per tile: every tap crosses image borders
     (2, 20, 20, 512, 512, "relu", False, 0),    # res5 branch2b: eight channel chunks, two 256-channel output tiles per pixel tile
     (1, 5, 200, 256, 256, "silu", True, 0),     # W = 200 (MaskFormer FPN): the 576-row plane instantiation, residual epilogue through LDS
-    (1, 7, 160, 64, 64, "relu", False, 0),      # W = 160 (res2): 512-pixel tile, one chunk
+    (1, 7, 160, 64, 64, "relu", False, 0),      # W = 160 (res2): the widest plane of the duo form below, one chunk
     (1, 9, 100, 128, 128, None, False, 16),     # W = 100 (MaskFormer res3), strided input rows, no activation
     (2, 20, 24, 32, 32, "relu", False, 0),      # 32 input channels (conv3x3_c32.hip): conv1_2 class, several images per 512-pixel tile
     (1, 5, 320, 32, 64, "relu", False, 0),      # conv1_3 at the benchmark's width, M = 1600 (3 full tiles + a tail)
     (1, 3, 400, 32, 64, None, False, 32),       # MaskFormer's 400-wide stem: the 1344-row plane, strided input rows, no activation
-    # round 5: 64 -> 64 layers on the LDS-resident-filter kernel (conv3x3_c64.hip): 16 x 32 tiles - partial bands / strips, several images
-    (2, 33, 47, 64, 64, "relu", False, 8),
-    (1, 40, 200, 64, 64, None, False, 0),       # MaskFormer res2 width, no activation (the input-gradient form of the training graph)
-    (3, 16, 32, 64, 64, "relu", False, 0),      # exactly one tile per image
+    # 64 -> 64 layers without a residual (res2 branch2b) on conv3x3_kplane's loader-less duo form (256-pixel tiles, two workgroups per CU,
+    # W <= 175); written for the round-5 LDS-resident-filter kernel, which was removed (profiles/r05_c64_ab.txt)
+    (2, 33, 47, 64, 64, "relu", False, 8),      # partial last tile, tiles across image borders, strided input rows
+    (1, 40, 200, 64, 64, None, False, 0),       # MaskFormer res2 width (past the duo form: the 512-pixel tile), no activation (the input-gradient form of the training graph)
+    (3, 16, 32, 64, 64, "relu", False, 0),      # two whole tiles per image
     # round 6: M >= 40 000 without a residual = the loader-less multi-chunk form (two workgroups per CU, FX_C3K_DUO256_MIN_M): four channel
     # chunks through ONE halo buffer, partial last tile (M = 40 960 + 37 rows of a ninth image would not divide - 8 x 64 x 81 = 41 472 does not either)
     (8, 64, 81, 256, 256, "silu", False, 0),

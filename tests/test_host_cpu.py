@@ -348,6 +348,78 @@ def test_conv_routing_labels(lib_path, monkeypatch):
     assert label(2, 16, 16, 64, 64, 3) == "conv3x3_kplane<64>"                   # the kernel tests' lowered threshold
 
 
+def _routing_census():
+    """scripts/make_golden_routing.py as a module: the grid, the census and the fixture's encoding."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("make_golden_routing", os.path.join(ROOT, "scripts", "make_golden_routing.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_conv_routing_matches_golden_census(lib_path, monkeypatch):
+    """fx_conv2d_variant over the descriptor grid of scripts/make_golden_routing.py (43 316 descriptors: KH, stride, C, N, M on both sides
+    of every routing threshold, epilogue, fragment copy, out_f32, pool2, mask, y_batch_stride) returns exactly the return codes and labels
+    of tests/golden/conv_routing.json, under the default thresholds and under FX_CONV3_MIN_M = FX_PW_MIN_M = 0."""
+    from focoos_amd import _lib
+
+    g = _routing_census()
+    with open(os.path.join(ROOT, "tests", "golden", "conv_routing.json")) as f:
+        doc = json.load(f)
+    assert json.loads(json.dumps(g.grid())) == doc["grid"], "the script's grid is not the one the fixture was recorded on"
+    for k in g.THRESHOLDS:
+        monkeypatch.delenv(k, raising=False)
+    want, got, pts = g.decode(doc), g.census(_lib.load()), g.points()
+    assert sorted(want) == sorted(got) == sorted(g.ENVS)
+    for env in g.ENVS:
+        assert len(want[env]) == len(got[env]) == len(pts)
+        moved = [(pts[i], w, o) for i, (w, o) in enumerate(zip(want[env], got[env])) if w != o]
+        assert not moved, f"{env}: {len(moved)} descriptors changed route, e.g. (KH, stride, C, N, (B, H, W), variant), want, got: {moved[:5]}"
+
+
+def test_conv_frag_predicate_matches_the_former_conditions():
+    """_lib.conv_frag_eligible (which weights get an MFMA fragment-order copy) selects the same shapes as the two conditions it replaced:
+    the one inlined in engine._EngineBase._pack, and train_nn._frag_eligible, which never offered the C = 32 stem layers (c32=False)."""
+    from focoos_amd._lib import conv_frag_eligible
+
+    def engine_former(N, Cc, KH, KW):
+        return bool((KH == 3 and KW == 3 and (N in (64, 128) or N % 256 == 0) and Cc % 64 == 0) or (KH == 1 and KW == 1 and N % 256 == 0 and Cc % 256 == 0)
+                    or (KH == 3 and KW == 3 and Cc == 32 and N in (32, 64)))
+
+    def train_former(rows, cin, k):
+        if k == 3:
+            return (rows in (64, 128) or rows % 256 == 0) and cin % 64 == 0
+        return k == 1 and rows % 256 == 0 and cin % 256 == 0
+
+    g = _routing_census()
+    chans = sorted(set(g.CS + g.NS + [8, 16, 48, 96, 192, 320, 768, 1536, 4096]))
+    n_eng = n_train = 0
+    for k in (1, 3, 5, 7):
+        for n in chans:
+            for c in chans:
+                for kh, kw in ((k, k), (k, 1), (1, k)):
+                    assert (kh == kw and conv_frag_eligible(n, c, kh)) == engine_former(n, c, kh, kw), (n, c, kh, kw)
+                assert conv_frag_eligible(n, c, k, c32=False) == train_former(n, c, k), (n, c, k)
+                n_eng += engine_former(n, c, k, k)
+                n_train += train_former(n, c, k)
+    assert n_eng - n_train == 2   # 3x3, C = 32, N = 32 / 64: the stem's conv1_2 / conv1_3, inference only
+
+
+def test_dynamic_symbols_are_exactly_the_declared_functions(lib_path):
+    """The fx_* names in each library's dynamic symbol table (nm -D) are exactly the functions include/focoos_amd.h declares: no C entry
+    point outside the ABI."""
+    import shutil
+
+    from focoos_amd import build
+
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"
+    for path in (lib_path, build.build(force=False, verbose=False, fp16=True)):
+        out = subprocess.run([nm, "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+        names = sorted({ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("fx_")})
+        assert names == header_functions(), (path, sorted(set(names) ^ set(header_functions())))
+
+
 def test_pack_entry_blocks(lib_path):
     """fx_pack_entry_blocks = workgroups of one fx_pack_weights_many_f32 table entry: tiles of 8 output channels x at most 2304
     (input channel, tap) elements, the channel chunk a multiple of 8 (host logic; the Python packer sums these into first_block)."""
