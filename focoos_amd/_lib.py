@@ -43,6 +43,15 @@ def conv_frag_eligible(n: int, c: int, k: int, c32: bool = True) -> bool:
     return (n in (64, 128) or n % 256 == 0) and c % 64 == 0
 
 
+class FxAugRecord(C.Structure):
+    """include/focoos_amd.h fx_aug_record (64 bytes)"""
+    _fields_ = [
+        ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("pad_x", C.c_int32), ("pad_y", C.c_int32), ("res_w", C.c_int32), ("res_h", C.c_int32),
+        ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("flags", C.c_int32), ("reserved0", C.c_int32),
+        ("brightness", C.c_float), ("contrast", C.c_float), ("saturation", C.c_float), ("reserved1", C.c_int32 * 3),
+    ]
+
+
 class FxPackEntry(C.Structure):
     """include/focoos_amd.h fx_pack_entry"""
     _fields_ = [
@@ -90,6 +99,8 @@ SIGNATURES = {
     "fx_stem16_conv3x3s2": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "fx_conv3x3_c16_nhwc_bf16": [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "fx_semseg_eval_accumulate": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "fx_augment_images_u8": [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp],
+    "fx_augment_labels": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp],
     "fx_resize_bilinear_u8": [_vp, _i, _i, _vp, _i, _i, _vp],
     "fx_maxpool3x3s2_nhwc_bf16": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "fx_stem_conv12_u8_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -257,7 +268,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 10  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 11  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:

@@ -73,6 +73,21 @@ def _spawned_rank(args, data_train, data_val, snapshot, family, config, im_size,
     return run_train(args, data_train, data_val, snapshot, processor, model_info, hub)
 
 
+def batch_assembler(data_train, family: str, processor, dev, seed: int, rank: int):
+    """``entries -> (images, targets)`` of one rank.  An ``augment.AugmentedDataset`` is assembled by a ``DeviceAugmenter`` drawing from a
+    CPU generator seeded with the rank's seed (unsupported augmentation fields raise here, before the training graph is built); any other
+    ``data_train`` goes through ``processor.preprocess`` exactly as before."""
+    from .augment import AugmentedDataset, DeviceAugmenter, task_of_family
+    from .train_data import rank_seed
+
+    if not isinstance(data_train, AugmentedDataset):
+        return lambda entries: processor.preprocess(entries, device=dev)
+    augmenter = DeviceAugmenter(data_train.augmentations, task_of_family(family), dev)
+    gen = torch.Generator()
+    gen.manual_seed(rank_seed(seed, rank))
+    return lambda entries: augmenter(entries, gen)
+
+
 def run_train(args: TrainerArgs, data_train, data_val, model, processor, model_info, hub=None) -> Dict[str, float]:
     """Per-rank training body.  ``model`` is the engine-backed FAIDetr / BisenetFormer mirror or its ``ModelSnapshot`` (its state_dict
     seeds the trainable graph); ``data_train[i]`` is a DatasetEntry.  Returns the last step's losses (floats) on every rank.
@@ -94,6 +109,7 @@ def run_train(args: TrainerArgs, data_train, data_val, model, processor, model_i
     rank, world = _dist()
     local = int(os.environ.get("LOCAL_RANK", rank))
     dev = torch.device("cuda", local if world > 1 else (model.device.index or 0))
+    assemble = batch_assembler(data_train, family, processor, dev, args.seed, rank)
     torch.cuda.set_device(dev)
     torch.manual_seed(rank_seed(args.seed, rank))
     norm = "FrozenBN" if args.freeze_bn else ("SyncBN" if world > 1 else "BN")
@@ -121,7 +137,7 @@ def run_train(args: TrainerArgs, data_train, data_val, model, processor, model_i
         t0 = time.perf_counter()
         for it in range(args.max_iters):
             entries = [data_train[next(sampler)] for _ in range(bs)]
-            images, targets = processor.preprocess(entries, device=dev)
+            images, targets = assemble(entries)
             losses = stepper.step(images, targets)
             if args.log_period and (it + 1) % args.log_period == 0:
                 stepper.check()    # every rank (MAX-all-reduced status): a diverged step (NaN / inf matching costs) ends the run as SciPy's error does in the reference

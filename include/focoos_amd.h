@@ -29,7 +29,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 10
+#define FX_ABI_VERSION 11
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -172,6 +172,37 @@ int fx_conv3x3_c16_nhwc_bf16(const void* x, int ldx, const void* w_frag, const f
 int fx_semseg_eval_accumulate(const float* mask_probs, const float* probs, int B, int Q, int K, int h, int w, int Hin, int Win, const int32_t* sizes,
                               int64_t max_pixels, const void* gt, const int64_t* gt_off, int gt_int32, int ignore_label, int64_t* conf,
                               int32_t* status, int32_t* pred, float* score, fx_stream_t stream);
+
+/* ---- Training augmentation (ABI 11; csrc/augment.hip): flip, scale, crop, pad and colour jitter of a batch in one
+ * resample.  One record per source image; all extents in pixels.  The placed window shows columns [crop_x, crop_x + crop_w) / rows
+ * [crop_y, crop_y + crop_h) of the source resized to (res_h, res_w) (mirrored first where the flip bit is set) at output offset
+ * (pad_x, pad_y); everything else of the output is the pad value.  flags: bit 0 horizontal flip, bit 1 vertical flip, bits 4-5 colour order
+ * (0 none, 1 brightness-contrast-saturation, 2 brightness-saturation-contrast).  Factors of 1.0 leave the pixel as it is. */
+typedef struct fx_aug_record {
+  int32_t crop_w, crop_h, pad_x, pad_y, res_w, res_h, crop_x, crop_y, flags, reserved0;
+  float brightness, contrast, saturation;
+  int32_t reserved1[3];
+} fx_aug_record;
+
+/* src: B uint8 HWC images in one buffer of src_bytes bytes, image i at byte offset src_off[i] with sizes[i] = (H_i, W_i); dst: uint8
+ * [B][Ho][Wo][3], every byte written.  Resample = PIL's BILINEAR (normalised triangle filter of half-width max(1, source step), exact integer
+ * tap geometry), then the colour blends in fp32 (contrast against the mean of the source image over all channels), round half up, clamp.
+ * src_off / sizes / recs are DEVICE arrays; the *_host arrays are the same values in host memory: they are validated (window inside the
+ * resized image and the output, image inside the buffer, extents in 1..16384) before anything is launched.  mean_ws: B * 32 uint64 of device
+ * scratch, required when a record has a colour order and contrast != 1.  16-byte stores when Wo % 16 == 0 and dst is 16-byte aligned.
+ * Anything outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched.  The same in both libraries. */
+int fx_augment_images_u8(const uint8_t* src, const int64_t* src_off, const int32_t* sizes, const fx_aug_record* recs, const int64_t* src_off_host,
+                         int64_t src_bytes, const int32_t* sizes_host, const fx_aug_record* recs_host, int B, uint8_t* dst, int Ho, int Wo,
+                         int pad_value, uint64_t* mean_ws, fx_stream_t stream);
+
+/* The same map with nearest sampling (PIL's NEAREST index floor((x + 0.5) * in / out)) for P planes of uint8 (elem_int32 = 0) or int32
+ * elements: plane p starts at ELEMENT offset src_off[p] of a buffer of src_count elements and uses record / size plane_rec[p] of B.  A
+ * semantic label map is one plane padded with the ignore label, a stack of T instance masks is T planes padded with 0.  dst: [P][Ho][Wo].
+ * flags (optional, int32 [P], zeroed by the caller): set to 1 where the output plane holds a non-zero element inside its window. */
+int fx_augment_labels(const void* src, const int64_t* src_off, const int32_t* plane_rec, const int32_t* sizes, const fx_aug_record* recs,
+                      const int64_t* src_off_host, int64_t src_count, const int32_t* plane_rec_host, const int32_t* sizes_host,
+                      const fx_aug_record* recs_host, int P, int B, void* dst, int Ho, int Wo, int elem_int32, int pad_value, int32_t* flags,
+                      fx_stream_t stream);
 
 /* Processor.get_torch_batch resize (focoos/processor/base_processor.py:285-288):
  * F.interpolate(bilinear, align_corners=False) of one HWC uint8 image to [Ho,Wo,3] float32. */
