@@ -99,6 +99,10 @@ SIGNATURES = {
     "fx_stem16_conv3x3s2": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "fx_conv3x3_c16_nhwc_bf16": [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "fx_semseg_eval_accumulate": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_int64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "fx_detr_eval_boxes_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "fx_coco_match_workspace_bytes": [_i],
+    "fx_coco_match_bbox": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                           _vp],
     "fx_augment_images_u8": [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp],
     "fx_augment_labels": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp],
     "fx_resize_bilinear_u8": [_vp, _i, _i, _vp, _i, _i, _vp],
@@ -268,7 +272,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 11  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 12  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:
@@ -295,6 +299,7 @@ def load(name: str = None) -> C.CDLL:
     lib.fx_mf_postprocess_workspace_bytes_fused.restype = C.c_size_t
     lib.fx_mask_set_loss_workspace_bytes.restype = C.c_size_t
     lib.fx_topk_rows_workspace_bytes.restype = C.c_size_t
+    lib.fx_coco_match_workspace_bytes.restype = C.c_size_t
     lib.fx_error_string.argtypes = [C.c_int]
     lib.fx_error_string.restype = C.c_char_p
     if lib.fx_abi_version() != FX_ABI_VERSION:

@@ -8,7 +8,8 @@
 
 Same names, argument meaning and error behaviour; the compute is the HIP engine (engine.py).
 ``FocoosModel.train`` drives the HIP training step (trainer.py; RT-DETR and BiSeNetFormer families); ``FocoosModel.eval`` evaluates the
-semantic-segmentation and classification entries (evaluation.py); ``.export()`` is out of scope and raises
+semantic-segmentation and classification entries (evaluation.py), ``FocoosModel.eval_detection`` scores RT-DETR with COCO bbox AP
+(detection_eval.py); ``.export()`` is out of scope and raises
 NotImplementedError (loudly — never a silent fallback)."""
 from __future__ import annotations
 
@@ -374,6 +375,17 @@ class FocoosModel:
         from .evaluation import run_eval
 
         return run_eval(self, args, data_test, save_json)
+
+    def eval_detection(self, args, data_test, save_json: bool = True) -> dict:
+        """COCO bbox AP of an RT-DETR model on ``data_test`` (indexable; ports.DetectionDatasetEntry items with ``annotations`` or
+        ``instances`` ground truth): same arguments and artifacts as ``eval``, returns ``{"bbox": {"AP", "AP50", "AP75", "APs", "APm",
+        "APl", "AP-<class>"...}}`` like the reference's DetectionEvaluator.  The detections are matched on the device
+        (fx_detr_eval_boxes_f32 + fx_coco_match_bbox), accumulated in numpy float64 (detection_eval.py).  Every family but fai_detr raises
+        NotImplementedError before anything is created."""
+        from .detection_eval import check_supported, run_eval_detection
+
+        check_supported(self)
+        return run_eval_detection(self, args, data_test, save_json)
 
     def export(self, *a, **k):
         raise NotImplementedError("FocoosModel.export: the ONNX/TensorRT export path is out of scope (BASELINE north_star)")

@@ -308,6 +308,13 @@ class DatasetEntry(DictClass):
 
 
 @dataclass
+class DetectionDatasetEntry(DatasetEntry):
+    """A detection sample with COCO-style ground truth for evaluation: ``annotations`` = dicts with ``bbox`` (XYWH absolute) and
+    ``category_id``, optional ``iscrowd`` / ``area`` / ``ignore`` (detection_eval.ground_truth; ``instances`` is read when it is None)."""
+    annotations: Optional[list] = None
+
+
+@dataclass
 class SemanticSegmentationDatasetEntry(DatasetEntry):
     """focoos/ports.py SemanticSegmentationDatasetEntry: ``sem_seg_file_name`` is the ground-truth label image (read with PIL, as
     load_image_into_numpy_array does); ``sem_seg`` an in-memory [H, W] label array (engine extension: synthetic or pre-loaded data)."""

@@ -20,6 +20,7 @@
 #ifndef FOCOOS_AMD_H
 #define FOCOOS_AMD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -29,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 11
+#define FX_ABI_VERSION 12
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -172,6 +173,31 @@ int fx_conv3x3_c16_nhwc_bf16(const void* x, int ldx, const void* w_frag, const f
 int fx_semseg_eval_accumulate(const float* mask_probs, const float* probs, int B, int Q, int K, int h, int w, int Hin, int Win, const int32_t* sizes,
                               int64_t max_pixels, const void* gt, const int64_t* gt_off, int gt_int32, int ignore_label, int64_t* conf,
                               int32_t* status, int32_t* pred, float* score, fx_stream_t stream);
+
+/* ---- COCO bbox AP evaluation (ABI 12; csrc/coco_eval.hip): FocoosModel.eval_detection's device side.
+ * fx_detr_eval_boxes_f32 = DETRProcessor.eval_postprocess for a whole batch: per top-k slot (idx [B][T] from fx_topk_rows_ws_f32, whose
+ * values are the scores), label = idx % K, box = boxes[b][idx / K] scaled by the image's (w, h) (sizes [B][2] = (height, width)), clamped to the image, all in
+ * fp32; keep = 1 where (x1 - x0) > 0 and (y1 - y0) > 0; xywh = (x0, y0, x1 - x0, y1 - y0) with the differences rounded to fp32. */
+int fx_detr_eval_boxes_f32(const int32_t* idx, const float* boxes, const int32_t* sizes, int B, int Q, int K, int T,
+                           int32_t* label, float* xyxy, int32_t* keep, float* xywh, fx_stream_t stream);
+
+/* COCOeval.computeIoU + evaluateImg for iouType "bbox", useCats = 1, maxDets = 100, iouThrs = linspace(.5, .95, 10) and the four COCO area
+ * ranges, for a batch of B images with T detection slots each (label / score / keep [B][T], xywh [B][T][4] fp32; slots with keep == 0 or a
+ * label outside [0, K) take no part).  Ground truth: image b owns elements [gt_off[b], gt_off[b + 1]) of gt_box (XYWH fp64 [n_gt][4]),
+ * gt_cat, gt_flag (bit 0 crowd, bit 1 ignore) and gt_area (fp64); gt_off has B + 1 entries and is given on the device and on the host (the
+ * host copy is validated: gt_off[0] >= 0, non-decreasing, fewer than 2^26 boxes per image, gt_off[B] <= n_gt).  An image without a kept detection is skipped whole (the
+ * reference evaluates only images that have predictions).  Per (image, category): detections stably sorted by descending score, cut to
+ * 100; IoU in fp64 (maskApi bbIou, every operation a single IEEE operation); bit (10 a + t) of matched / ignored [B][T] (uint64) is the
+ * decision for area range a and threshold t; rank [B][T] is the position in the sorted list or -1 (not scored); npig (int64 [K][4]) gains
+ * the number of non-ignored ground-truth boxes (accumulated, never cleared).  max_gt bounds the ground-truth boxes of one (image,
+ * category): when a 100 x max_gt tile does not fit the kernel's LDS slice, ws must hold fx_coco_match_workspace_bytes(max_gt) bytes.  An item
+ * with more boxes than max_gt that does not fit is not matched and adds 1 to *status.  Anything outside the contract:
+ * FX_ERR_INVALID_ARGUMENT, nothing launched.  The same in both libraries. */
+size_t fx_coco_match_workspace_bytes(int max_gt);
+int fx_coco_match_bbox(const int32_t* label, const float* score, const int32_t* keep, const float* xywh, int B, int T, int K,
+                       const double* gt_box, const int32_t* gt_cat, const int32_t* gt_flag, const double* gt_area, const int64_t* gt_off,
+                       const int64_t* gt_off_host, int64_t n_gt, int max_gt, int32_t* rank, uint64_t* matched, uint64_t* ignored,
+                       int64_t* npig, int32_t* status, void* ws, size_t ws_bytes, fx_stream_t stream);
 
 /* ---- Training augmentation (ABI 11; csrc/augment.hip): flip, scale, crop, pad and colour jitter of a batch in one
  * resample.  One record per source image; all extents in pixels.  The placed window shows columns [crop_x, crop_x + crop_w) / rows
