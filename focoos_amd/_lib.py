@@ -103,6 +103,13 @@ SIGNATURES = {
     "fx_coco_match_workspace_bytes": [_i],
     "fx_coco_match_bbox": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
                            _vp],
+    "fx_mf_eval_masks_workspace_bytes": [_i, _i, _i],
+    "fx_mf_eval_masks": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_int64, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                         _vp, _vp, C.c_size_t, _vp],
+    "fx_coco_mask_inter": [_vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp,
+                           _vp, _vp],
+    "fx_coco_match_segm": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                           C.c_size_t, _vp],
     "fx_augment_images_u8": [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp],
     "fx_augment_labels": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp],
     "fx_resize_bilinear_u8": [_vp, _i, _i, _vp, _i, _i, _vp],
@@ -272,7 +279,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 12  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 13  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:
@@ -300,6 +307,7 @@ def load(name: str = None) -> C.CDLL:
     lib.fx_mask_set_loss_workspace_bytes.restype = C.c_size_t
     lib.fx_topk_rows_workspace_bytes.restype = C.c_size_t
     lib.fx_coco_match_workspace_bytes.restype = C.c_size_t
+    lib.fx_mf_eval_masks_workspace_bytes.restype = C.c_size_t
     lib.fx_error_string.argtypes = [C.c_int]
     lib.fx_error_string.restype = C.c_char_p
     if lib.fx_abi_version() != FX_ABI_VERSION:

@@ -1,7 +1,9 @@
 // COCO bbox AP evaluation on the device (FocoosModel.eval_detection):
 //   fx_detr_eval_boxes_f32 = DETRProcessor.eval_postprocess for a whole batch (label = idx % K, box of query idx / K scaled to the
 //     original size, clipped, nonempty(), XYWH in fp32) - one thread per detection slot;
-//   fx_coco_match_bbox     = COCOeval.computeIoU + evaluateImg (iouType "bbox", useCats, maxDets 100, 10 thresholds x 4 area ranges).
+//   fx_coco_match_bbox     = COCOeval.computeIoU + evaluateImg (iouType "bbox", useCats, maxDets 100, 10 thresholds x 4 area ranges);
+//   fx_coco_match_segm     = the same kernel for iouType "segm" (DESIGN.md section 13): the template parameter is the IoU source - boxes
+//     (maskApi bbIou) or the integer mask intersections and pixel counts of csrc/coco_segm_eval.hip (maskApi rleIou).
 // Matching layout: one wavefront per (image, category); the work list is the dense [B][K] grid walked by a fixed number of workgroups, an
 // item without a detection or a ground-truth box of its category ends after two label scans.  All 64 lanes rank the detections (stable,
 // descending score), compact the ground truth of the category and fill the [nD][G] fp64 IoU tile once; lanes 0-39 then each own one
@@ -75,6 +77,57 @@ struct CmArgs {
   size_t ws_slice;
   int B, T, K, max_gt, lds_bytes;
   double thr[10];
+  // the segm source (fx_coco_match_segm; keep / xywh / gt_box are not read there)
+  const int32_t* query;    // [B][T] query of a slot
+  const int32_t* dcount;   // [B][Q] mask pixels of a query
+  const int32_t* inter;    // image b, query q, gt g of the image: inter[Q * gt_off[b] + q * G_b + g]
+  const int32_t* gcount;   // [n_gt] mask pixels of a ground-truth mask
+  int Q;
+};
+
+// IoU sources.  load() fills the detection's LDS record, area() is the area compared with the area ranges, iou() one tile entry.
+struct CmBbox {
+  static __device__ __forceinline__ bool kept(const CmArgs& a, int64_t slot) { return a.keep[slot] != 0; }
+  static __device__ __forceinline__ void load(const CmArgs& a, int b, int64_t slot, double* db) {
+    const float* p = a.xywh + slot * 4;
+    db[0] = (double)p[0], db[1] = (double)p[1], db[2] = (double)p[2], db[3] = (double)p[3];
+  }
+  static __device__ __forceinline__ double area(const double* db) { return db[2] * db[3]; }
+  // maskApi bbIou: o = i / u, u = crowd ? area(d) : area(d) + area(g) - i
+  static __device__ __forceinline__ double iou(const CmArgs& a, int b, const double* db, int64_t g0, int64_t Gi, uint32_t gl, bool crowd) {
+    const double* Gb = a.gt_box + (g0 + gl) * 4;
+    const double dx = db[0], dy = db[1], dw = db[2], dh = db[3];
+    const double gx = Gb[0], gy = Gb[1], gw = Gb[2], gh = Gb[3];
+    double o = 0.0;
+    const double w = fmin(dw + dx, gw + gx) - fmax(dx, gx);
+    if (w > 0.0) {
+      const double h = fmin(dh + dy, gh + gy) - fmax(dy, gy);
+      if (h > 0.0) {
+        const double da = dw * dh, ga = gw * gh, in = w * h;
+        const double u = crowd ? da : (da + ga) - in;
+        o = in / u;
+      }
+    }
+    return o;
+  }
+};
+
+struct CmSegm {
+  static __device__ __forceinline__ bool kept(const CmArgs&, int64_t) { return true; }   // instance_inference drops nothing
+  static __device__ __forceinline__ void load(const CmArgs& a, int b, int64_t slot, double* db) {
+    int q = a.query[slot];
+    q = q < 0 ? 0 : (q >= a.Q ? a.Q - 1 : q);
+    db[0] = (double)a.dcount[(int64_t)b * a.Q + q], db[1] = (double)q, db[2] = 0.0, db[3] = 0.0;
+  }
+  static __device__ __forceinline__ double area(const double* db) { return db[0]; }
+  // maskApi rleIou on integers: 0 without a common pixel, else one fp64 division of exactly represented integers
+  static __device__ __forceinline__ double iou(const CmArgs& a, int b, const double* db, int64_t g0, int64_t Gi, uint32_t gl, bool crowd) {
+    const int q = (int)db[1];
+    const int64_t in = a.inter[(int64_t)a.Q * g0 + (int64_t)q * Gi + gl];
+    if (in == 0) return 0.0;
+    const int64_t da = (int64_t)db[0], ga = a.gcount[g0 + gl];
+    return (double)in / (double)(crowd ? da : da + ga - in);
+  }
 };
 
 // bytes of one item's scratch: IoU tile [nD][G] f64, gt list [G] u32, orders [4][G] u32, taken bitsets [40][ceil(G / 32)] u32
@@ -88,6 +141,7 @@ __device__ __forceinline__ int cm_wave_sum(int v) {
   return v;
 }
 
+template <class Src>
 __global__ __launch_bounds__(64) void coco_match_kernel(CmArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_buf[];   // lds_bytes: sized by the host from max_gt
   __shared__ int s_sel[CM_MAXDET];
@@ -100,12 +154,11 @@ __global__ __launch_bounds__(64) void coco_match_kernel(CmArgs a) {
     const int b = (int)(item / K), c = (int)(item - (int64_t)b * K);
     const int64_t sb = (int64_t)b * T;
     const int32_t* lab = a.label + sb;
-    const int32_t* kp = a.keep + sb;
     const float* sc = a.score + sb;
     __syncthreads();   // the previous item's LDS reads are over
     int nk = 0, nc = 0, nl = 0;
     for (int j = lane; j < T; j += 64) {
-      const int k = kp[j] != 0, l = lab[j] == c;
+      const int k = Src::kept(a, sb + j), l = lab[j] == c;
       nk += k, nl += l, nc += (k && l);
     }
     nk = cm_wave_sum(nk), nc = cm_wave_sum(nc), nl = cm_wave_sum(nl);
@@ -127,10 +180,10 @@ __global__ __launch_bounds__(64) void coco_match_kernel(CmArgs a) {
     for (int j = lane; j < T; j += 64) {
       if (lab[j] != c) continue;
       int r = -1;
-      if (live && fits && kp[j] != 0) {
+      if (live && fits && Src::kept(a, sb + j)) {
         const float sj = sc[j];
         r = 0;
-        for (int i = 0; i < T; ++i) r += (kp[i] != 0 && lab[i] == c && (sc[i] > sj || (sc[i] == sj && i < j)));
+        for (int i = 0; i < T; ++i) r += (Src::kept(a, sb + i) && lab[i] == c && (sc[i] > sj || (sc[i] == sj && i < j)));
         if (r >= CM_MAXDET) r = -1;
       }
       a.rank[sb + j] = r;
@@ -147,10 +200,7 @@ __global__ __launch_bounds__(64) void coco_match_kernel(CmArgs a) {
     uint32_t* order = glist + G;
     uint32_t* taken = order + 4 * (int64_t)G;
     __syncthreads();
-    for (int r = lane; r < nD; r += 64) {
-      const float* p = a.xywh + (sb + s_sel[r]) * 4;
-      s_db[r][0] = (double)p[0], s_db[r][1] = (double)p[1], s_db[r][2] = (double)p[2], s_db[r][3] = (double)p[3];
-    }
+    for (int r = lane; r < nD; r += 64) Src::load(a, b, sb + s_sel[r], s_db[r]);
     // ground truth of this category, in dataset order: entry = index in the image | crowd << 26 | ignored in area range a << (27 + a)
     int cnt = 0;
     for (int64_t gb = 0; gb < Gi; gb += 64) {
@@ -180,24 +230,11 @@ __global__ __launch_bounds__(64) void coco_match_kernel(CmArgs a) {
       for (int ar = 0; ar < 4; ++ar) nn[ar] += __popcll(__ballot(g < G && !(bits & (2u << ar))));
     }
     __syncthreads();
-    // IoU tile (maskApi bbIou): o = i / u, u = crowd ? area(d) : area(d) + area(g) - i
+    // IoU tile, [nD][G] in the category's dataset order
     for (int64_t e = lane; e < (int64_t)nD * G; e += 64) {
       const int d = (int)(e / G), g = (int)(e - (int64_t)d * G);
       const uint32_t ge = glist[g];
-      const double* Gb = a.gt_box + (g0 + (ge & 0x3ffffffu)) * 4;
-      const double dx = s_db[d][0], dy = s_db[d][1], dw = s_db[d][2], dh = s_db[d][3];
-      const double gx = Gb[0], gy = Gb[1], gw = Gb[2], gh = Gb[3];
-      double o = 0.0;
-      const double w = fmin(dw + dx, gw + gx) - fmax(dx, gx);
-      if (w > 0.0) {
-        const double h = fmin(dh + dy, gh + gy) - fmax(dy, gy);
-        if (h > 0.0) {
-          const double da = dw * dh, ga = gw * gh, in = w * h;
-          const double u = ((ge >> 26) & 1u) ? da : (da + ga) - in;
-          o = in / u;
-        }
-      }
-      tile[e] = o;
+      tile[e] = Src::iou(a, b, s_db[d], g0, Gi, ge & 0x3ffffffu, (ge >> 26) & 1u);
     }
     // per area range: ground truth reordered non-ignored first (stable); entry = position in glist | crowd << 30 | ignored << 31
     for (int ar = 0; ar < 4; ++ar) {
@@ -246,7 +283,7 @@ __global__ __launch_bounds__(64) void coco_match_kernel(CmArgs a) {
           mt = true, ig = mig;
           tk[m >> 5] |= 1u << (m & 31);
         } else {
-          const double da = s_db[d][2] * s_db[d][3];
+          const double da = Src::area(s_db[d]);
           ig = da < lo || da > hi;
         }
       }
@@ -275,41 +312,77 @@ extern "C" size_t fx_coco_match_workspace_bytes(int max_gt) {
   return cm_ws_slice(max_gt) * CM_WS_GRID;
 }
 
-extern "C" int fx_coco_match_bbox(const int32_t* label, const float* score, const int32_t* keep, const float* xywh, int B, int T, int K,
-                                  const double* gt_box, const int32_t* gt_cat, const int32_t* gt_flag, const double* gt_area,
-                                  const int64_t* gt_off, const int64_t* gt_off_host, int64_t n_gt, int max_gt, int32_t* rank, uint64_t* matched,
-                                  uint64_t* ignored, int64_t* npig, int32_t* status, void* ws, size_t ws_bytes, fx_stream_t stream_) {
-  FX_CHECK_ARG(label && score && keep && xywh && gt_off && gt_off_host && rank && matched && ignored && npig && status);
+// the checks both entry points share
+static int cm_check_common(const int32_t* label, const float* score, int B, int T, int K, const int32_t* gt_cat, const int32_t* gt_flag,
+                           const double* gt_area, const int64_t* gt_off, const int64_t* gt_off_host, int64_t n_gt, int max_gt, int32_t* rank,
+                           uint64_t* matched, uint64_t* ignored, int64_t* npig, int32_t* status, void* ws, size_t ws_bytes) {
+  FX_CHECK_ARG(label && score && gt_off && gt_off_host && rank && matched && ignored && npig && status);
   FX_CHECK_ARG(B > 0 && B <= 65535 && T > 0 && T <= 65536 && K > 0 && (int64_t)B * K < (1ll << 31));
   FX_CHECK_ARG(n_gt >= 0 && n_gt < (1ll << 30) && max_gt >= 0);
-  FX_CHECK_ARG(n_gt == 0 || (gt_box && gt_cat && gt_flag && gt_area));
-  FX_CHECK_ARG((((uintptr_t)label | (uintptr_t)score | (uintptr_t)keep | (uintptr_t)xywh | (uintptr_t)gt_cat | (uintptr_t)gt_flag |
-                 (uintptr_t)rank | (uintptr_t)status) & 3) == 0);
-  FX_CHECK_ARG((((uintptr_t)gt_box | (uintptr_t)gt_area | (uintptr_t)gt_off | (uintptr_t)gt_off_host | (uintptr_t)matched | (uintptr_t)ignored |
-                 (uintptr_t)npig) & 7) == 0);
+  FX_CHECK_ARG(n_gt == 0 || (gt_cat && gt_flag && gt_area));
+  FX_CHECK_ARG((((uintptr_t)label | (uintptr_t)score | (uintptr_t)gt_cat | (uintptr_t)gt_flag | (uintptr_t)rank | (uintptr_t)status) & 3) == 0);
+  FX_CHECK_ARG((((uintptr_t)gt_area | (uintptr_t)gt_off | (uintptr_t)gt_off_host | (uintptr_t)matched | (uintptr_t)ignored | (uintptr_t)npig) & 7) ==
+               0);
   FX_CHECK_ARG(gt_off_host[0] >= 0);
   for (int b = 0; b < B; ++b) FX_CHECK_ARG(gt_off_host[b + 1] >= gt_off_host[b] && gt_off_host[b + 1] - gt_off_host[b] < (1ll << 26));
   FX_CHECK_ARG(gt_off_host[B] <= n_gt);
   const size_t need = fx_coco_match_workspace_bytes(max_gt);
   FX_CHECK_ARG(need == 0 || (ws && ((uintptr_t)ws & 15) == 0 && ws_bytes >= need));
-  CmArgs a;
-  a.label = label, a.score = score, a.keep = keep, a.xywh = xywh;
-  a.gt_box = gt_box, a.gt_cat = gt_cat, a.gt_flag = gt_flag, a.gt_area = gt_area, a.gt_off = gt_off;
-  a.rank = rank;
+  return FX_OK;
+}
+
+template <class Src>
+static int cm_launch(CmArgs& a, int max_gt, void* ws, uint64_t* matched, uint64_t* ignored, int64_t* npig, fx_stream_t stream_) {
+  const size_t need = fx_coco_match_workspace_bytes(max_gt);
   a.matched = reinterpret_cast<unsigned long long*>(matched);
   a.ignored = reinterpret_cast<unsigned long long*>(ignored);
   a.npig = reinterpret_cast<unsigned long long*>(npig);
-  a.status = status;
   a.ws = need ? static_cast<unsigned char*>(ws) : nullptr;
   a.ws_slice = need ? cm_ws_slice(max_gt) : 0;
-  a.B = B, a.T = T, a.K = K, a.max_gt = max_gt;
+  a.max_gt = max_gt;
   a.lds_bytes = cm_lds_bytes(max_gt);
   // np.linspace(.5, .95, 10) as COCOeval's Params builds it
   const double thr[10] = {0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85, 0.8999999999999999, 0.95};
   for (int i = 0; i < 10; ++i) a.thr[i] = thr[i];
-  const int64_t nitems = (int64_t)B * K;
+  const int64_t nitems = (int64_t)a.B * a.K;
   const int cap = need ? CM_WS_GRID : CM_GRID;
   const int grid = (int)(nitems < cap ? nitems : cap);
-  hipLaunchKernelGGL(coco_match_kernel, dim3(grid), dim3(64), (size_t)a.lds_bytes, reinterpret_cast<hipStream_t>(stream_), a);
+  hipLaunchKernelGGL(coco_match_kernel<Src>, dim3(grid), dim3(64), (size_t)a.lds_bytes, reinterpret_cast<hipStream_t>(stream_), a);
   return fx_launch_status();
+}
+
+extern "C" int fx_coco_match_bbox(const int32_t* label, const float* score, const int32_t* keep, const float* xywh, int B, int T, int K,
+                                  const double* gt_box, const int32_t* gt_cat, const int32_t* gt_flag, const double* gt_area,
+                                  const int64_t* gt_off, const int64_t* gt_off_host, int64_t n_gt, int max_gt, int32_t* rank, uint64_t* matched,
+                                  uint64_t* ignored, int64_t* npig, int32_t* status, void* ws, size_t ws_bytes, fx_stream_t stream_) {
+  FX_CHECK_ARG(keep && xywh && (n_gt <= 0 || gt_box));
+  FX_CHECK_ARG((((uintptr_t)keep | (uintptr_t)xywh) & 3) == 0 && ((uintptr_t)gt_box & 7) == 0);
+  const int rc = cm_check_common(label, score, B, T, K, gt_cat, gt_flag, gt_area, gt_off, gt_off_host, n_gt, max_gt, rank, matched, ignored, npig,
+                                 status, ws, ws_bytes);
+  if (rc != FX_OK) return rc;
+  CmArgs a{};
+  a.label = label, a.score = score, a.keep = keep, a.xywh = xywh;
+  a.gt_box = gt_box, a.gt_cat = gt_cat, a.gt_flag = gt_flag, a.gt_area = gt_area, a.gt_off = gt_off;
+  a.rank = rank, a.status = status;
+  a.B = B, a.T = T, a.K = K;
+  return cm_launch<CmBbox>(a, max_gt, ws, matched, ignored, npig, stream_);
+}
+
+// iouType "segm": query [B][T] (the mask of a slot), dcount [B][Q] / inter / gcount as fx_mf_eval_masks and fx_coco_mask_inter leave them.
+extern "C" int fx_coco_match_segm(const int32_t* label, const float* score, const int32_t* query, const int32_t* dcount, int B, int T, int K,
+                                  int Q, const int32_t* inter, const int32_t* gcount, const int32_t* gt_cat, const int32_t* gt_flag,
+                                  const double* gt_area, const int64_t* gt_off, const int64_t* gt_off_host, int64_t n_gt, int max_gt,
+                                  int32_t* rank, uint64_t* matched, uint64_t* ignored, int64_t* npig, int32_t* status, void* ws, size_t ws_bytes,
+                                  fx_stream_t stream_) {
+  FX_CHECK_ARG(query && dcount && Q > 0 && Q <= 128 && (n_gt <= 0 || (inter && gcount)) && n_gt < (1ll << 31) / 128);
+  FX_CHECK_ARG((((uintptr_t)query | (uintptr_t)dcount | (uintptr_t)inter | (uintptr_t)gcount) & 3) == 0);
+  const int rc = cm_check_common(label, score, B, T, K, gt_cat, gt_flag, gt_area, gt_off, gt_off_host, n_gt, max_gt, rank, matched, ignored, npig,
+                                 status, ws, ws_bytes);
+  if (rc != FX_OK) return rc;
+  CmArgs a{};
+  a.label = label, a.score = score, a.query = query, a.dcount = dcount, a.inter = inter, a.gcount = gcount, a.Q = Q;
+  a.gt_cat = gt_cat, a.gt_flag = gt_flag, a.gt_area = gt_area, a.gt_off = gt_off;
+  a.rank = rank, a.status = status;
+  a.B = B, a.T = T, a.K = K;
+  return cm_launch<CmSegm>(a, max_gt, ws, matched, ignored, npig, stream_);
 }

@@ -20,8 +20,13 @@ Reference behaviour that is kept on purpose:
   pycocotools' ``_prepare`` overwrites ``ignore`` with ``iscrowd``, so an annotation with ``ignore`` = 1 and ``iscrowd`` = 0 counts there);
 * values are x 100, a value that cannot be computed is None, per-category rows exist only with more than one class.
 
-Instance segmentation (segm AP), keypoints, maxDets 1 / 10 and the AR rows are not built.  ``FocoosModel.eval`` keeps refusing detection;
-this module is reached through ``FocoosModel.eval_detection``."""
+Segm AP (iouType "segm") shares everything after the IoU: ``InstanceSegmentationEvaluator`` is the host form, focoos_amd/segm_eval.py the
+device path behind ``FocoosModel.eval_instance_segmentation``.  Mask IoU is maskApi's rleIou on integers: 0 when the masks share no pixel,
+else inter / (crowd ? |d| : |d| + |g| - inter) as one fp64 division; a detection's area is its mask's pixel count.  Ground-truth masks are
+dense arrays, uncompressed RLE or ``instances.masks``; polygons and compressed RLE strings are refused (ground_truth_masks).
+
+Keypoints, maxDets 1 / 10 and the AR rows are not built.  ``FocoosModel.eval`` keeps refusing detection and instance segmentation;
+this module is reached through ``FocoosModel.eval_detection`` / ``eval_instance_segmentation``."""
 from __future__ import annotations
 
 import ctypes
@@ -118,6 +123,66 @@ def ground_truth(entry):
     return box, cat, np.zeros(len(cat), np.int32), box[:, 2] * box[:, 3]
 
 
+def _rle_to_mask(seg: dict) -> np.ndarray:
+    """uncompressed COCO RLE {"size": [H, W], "counts": [run of 0s, run of 1s, ...]} (column-major) -> bool [H, W]"""
+    counts = seg["counts"]
+    if isinstance(counts, (str, bytes)):
+        raise NotImplementedError("ground-truth segmentation as a compressed RLE string is not decoded (maskApi's string codec cannot be "
+                                  "checked against pycocotools here); give a dense mask or an uncompressed RLE")
+    H, W = (int(v) for v in seg["size"])
+    runs = np.asarray(counts, np.int64)
+    if (runs < 0).any() or int(runs.sum()) != H * W:
+        raise ValueError(f"uncompressed RLE counts sum to {int(runs.sum())}, the size is {H} x {W}")
+    flat = np.repeat(np.arange(len(runs)) % 2 == 1, runs)
+    return flat.reshape(W, H).T
+
+
+def ground_truth_masks(entry):
+    """(mask bool [G, H, W], category int32 [G], flag int32 [G] (bit 0 crowd, bit 1 ignore), area float64 [G]) of a dataset entry, H x W its
+    ``height`` x ``width``.  ``annotations[i]["segmentation"]`` as a 2-D array or an uncompressed RLE dict when annotations are present
+    (``area`` defaults to the mask's pixel count, create_coco :412), else ``instances.masks`` (BitMasks or a [G, H, W] tensor) with
+    ``instances.classes``.  Polygon lists and compressed RLE raise NotImplementedError; a mask of another shape raises ValueError."""
+    get = (lambda k: entry.get(k)) if isinstance(entry, dict) else (lambda k: getattr(entry, k, None))
+    H, W = int(get("height") or 0), int(get("width") or 0)
+    anns = get("annotations")
+    masks = []
+    if anns is not None:
+        G = len(anns)
+        cat, flag, area = np.zeros(G, np.int32), np.zeros(G, np.int32), np.zeros(G, np.float64)
+        for i, a in enumerate(anns):
+            seg = a.get("segmentation")
+            if seg is None:
+                raise ValueError("segm evaluation needs a segmentation on every annotation")
+            if isinstance(seg, dict):
+                m = _rle_to_mask(seg)
+            elif isinstance(seg, (list, tuple)):                      # COCO polygons: a list of [x0, y0, x1, y1, ...] lists
+                raise NotImplementedError("ground-truth segmentation as polygon lists is not rasterised (maskApi's polygon rasteriser cannot be "
+                                          "checked against pycocotools here); give a dense mask or an uncompressed RLE")
+            else:
+                m = np.asarray(seg.cpu() if isinstance(seg, torch.Tensor) else seg)
+                if m.ndim != 2:
+                    raise ValueError(f"a dense ground-truth mask must be 2-D, got shape {m.shape}")
+                m = m != 0
+            if m.shape != (H, W):
+                raise ValueError(f"ground-truth mask {m.shape} does not match the entry's (height, width) {(H, W)}")
+            masks.append(m)
+            cat[i] = int(a["category_id"])
+            area[i] = float(a["area"]) if "area" in a else float(m.sum())
+            flag[i] = (1 if a.get("iscrowd", 0) else 0) | (2 if a.get("ignore", 0) else 0)
+        return (np.stack(masks) if masks else np.zeros((0, H, W), bool)), cat, flag, area
+    inst = get("instances")
+    if inst is None or not inst.has("masks"):
+        z = np.zeros(0)
+        return np.zeros((0, H, W), bool), z.astype(np.int32), z.astype(np.int32), z
+    m = inst.masks.tensor if hasattr(inst.masks, "tensor") else inst.masks
+    m = np.asarray(torch.as_tensor(m).detach().cpu().numpy()) != 0
+    m = m.reshape((-1,) + m.shape[-2:])
+    if len(m) and m.shape[1:] != (H, W):
+        raise ValueError(f"ground-truth mask {m.shape[1:]} does not match the entry's (height, width) {(H, W)}")
+    cat = np.asarray(torch.as_tensor(inst.classes).cpu().numpy(), dtype=np.int32).reshape(-1)
+    return m.reshape(len(cat), H, W), cat, np.zeros(len(cat), np.int32), m.reshape(len(cat), -1).sum(1).astype(np.float64)
+
+
 # ---------------------------------------------------------------------------------------------------------------- host matching
 def bbox_iou(d: np.ndarray, g: np.ndarray, crowd: np.ndarray) -> np.ndarray:
     """maskApi bbIou on XYWH float64 boxes: [D, G]; the union of a crowd box is the detection's own area."""
@@ -131,6 +196,36 @@ def bbox_iou(d: np.ndarray, g: np.ndarray, crowd: np.ndarray) -> np.ndarray:
     return np.where((w <= 0) | (h <= 0), 0.0, o)
 
 
+_POP8 = np.array([bin(i).count("1") for i in range(256)], np.int64)
+
+
+def pack_rows(masks: np.ndarray) -> np.ndarray:
+    """bool [N, H, W] -> uint8 [N, H, 8 ceil(W / 64)]: the kernels' layout (64 consecutive x of a row are one little-endian 64-bit word,
+    tail bits zero); ``.view(np.int32)`` is what MaskFormerProcessor.unpack_masks reads."""
+    m = np.asarray(masks, dtype=bool)
+    N, H, W = m.shape
+    out = np.zeros((N, H, 8 * ((W + 63) // 64)), np.uint8)
+    if N and H and W:
+        out[:, :, : (W + 7) // 8] = np.packbits(m, axis=-1, bitorder="little")
+    return out
+
+
+def popcount(packed: np.ndarray) -> np.ndarray:
+    """set bits of every plane of pack_rows' output: int64 [N]"""
+    return _POP8[packed].reshape(packed.shape[0], -1).sum(1) if packed.shape[0] else np.zeros(0, np.int64)
+
+
+def mask_iou(dp: np.ndarray, dn: np.ndarray, gp: np.ndarray, gn: np.ndarray, crowd: np.ndarray) -> np.ndarray:
+    """maskApi rleIou on packed masks and their pixel counts: [D, G] float64; integers until the one division."""
+    D, G = len(dp), len(gp)
+    inter = np.zeros((D, G), np.int64)
+    if G:
+        for d in range(D):
+            inter[d] = _POP8[dp[d][None] & gp].reshape(G, -1).sum(1)
+    u = np.where(crowd[None, :], dn[:, None], dn[:, None] + gn[None, :] - inter)
+    return np.where(inter == 0, 0.0, inter / np.where(inter == 0, 1, u))
+
+
 def _pack(bits: np.ndarray) -> np.ndarray:
     """bool [n, 40] -> uint64 [n]"""
     return np.bitwise_or.reduce(bits.astype(np.uint64) << _BITS[None, :], axis=1) if bits.shape[0] else np.zeros(0, np.uint64)
@@ -141,16 +236,22 @@ def _unpack(words: np.ndarray) -> np.ndarray:
 
 
 def match_image_category(dbox: np.ndarray, gbox: np.ndarray, gflag: np.ndarray, garea: np.ndarray):
-    """evaluateImg for one (image, category): ``dbox`` the detections already in descending score order and cut to MAX_DETS.  The 40
-    (area range, threshold) pairs advance together, one detection per step.  Returns (matched bool [D, 40], ignored bool [D, 40], npig [4])."""
-    D, G = len(dbox), len(gbox)
-    darea = dbox[:, 2] * dbox[:, 3]
+    """evaluateImg for one (image, category) of boxes: ``dbox`` the detections already in descending score order and cut to MAX_DETS.
+    Returns (matched bool [D, 40], ignored bool [D, 40], npig [4])."""
+    iou = bbox_iou(dbox, gbox, (gflag & 1).astype(bool)) if len(dbox) and len(gbox) else np.zeros((len(dbox), len(gbox)))
+    return match_from_iou(iou, dbox[:, 2] * dbox[:, 3], gflag, garea)
+
+
+def match_from_iou(iou: np.ndarray, darea: np.ndarray, gflag: np.ndarray, garea: np.ndarray):
+    """evaluateImg from the [D, G] IoU matrix (bbox_iou or mask_iou; detections in descending score order, cut to MAX_DETS) and the
+    detections' areas.  The 40 (area range, threshold) pairs advance together, one detection per step.  Returns (matched bool [D, 40],
+    ignored bool [D, 40], npig [4])."""
+    D, G = iou.shape
     d_out = (darea[:, None] < AREA_RNG[None, :, 0]) | (darea[:, None] > AREA_RNG[None, :, 1])        # [D, 4]
     if G == 0 or D == 0:
         gig = (gflag[None, :] != 0) | (garea[None, :] < AREA_RNG[:, :1]) | (garea[None, :] > AREA_RNG[:, 1:])
         return np.zeros((D, _LANES), bool), d_out[:, _LANE_AREA], (~gig).sum(1).astype(np.int64)
     crowd = (gflag & 1).astype(bool)
-    iou = bbox_iou(dbox, gbox, crowd)
     gig = (gflag[None, :] != 0) | (garea[None, :] < AREA_RNG[:, :1]) | (garea[None, :] > AREA_RNG[:, 1:])    # [4, G]
     order = np.argsort(gig, axis=1, kind="mergesort")                                                      # non-ignored first, stable
     nn = (~gig).sum(1)
@@ -179,6 +280,24 @@ def match_image_category(dbox: np.ndarray, gbox: np.ndarray, gflag: np.ndarray, 
 def match_image(image_id: int, dbox: np.ndarray, dscore: np.ndarray, dcls: np.ndarray, gt, K: int) -> MatchRecords:
     """computeIoU + evaluateImg of one image on the host.  ``dbox`` XYWH float64 [N, 4] (every row a prediction), ``gt`` of ground_truth()."""
     gbox, gcat, gflag, garea = gt
+    return _match_image(image_id, dscore, dcls, gcat, K, lambda di, gi: match_image_category(dbox[di], gbox[gi], gflag[gi], garea[gi]))
+
+
+def match_image_masks(image_id: int, dmask: np.ndarray, dscore: np.ndarray, dcls: np.ndarray, gt, K: int) -> MatchRecords:
+    """The segm form: ``dmask`` bool [N, H, W] (every plane a prediction, empty ones included), ``gt`` of ground_truth_masks()."""
+    gmask, gcat, gflag, garea = gt
+    dp, gp = pack_rows(dmask), pack_rows(gmask)
+    dn, gn = popcount(dp), popcount(gp)
+
+    def one(di, gi):
+        iou = mask_iou(dp[di], dn[di], gp[gi], gn[gi], (gflag[gi] & 1).astype(bool))
+        return match_from_iou(iou, dn[di].astype(np.float64), gflag[gi], garea[gi])
+
+    return _match_image(image_id, dscore, dcls, gcat, K, one)
+
+
+def _match_image(image_id: int, dscore: np.ndarray, dcls: np.ndarray, gcat: np.ndarray, K: int, match) -> MatchRecords:
+    """Per category present in the image: detections in stable descending score order cut to MAX_DETS, ``match(det indices, gt indices)``."""
     parts = {name: [] for name, _ in MatchRecords.FIELDS}
     npig = np.zeros((K, _NA), np.int64)
     cats = np.union1d(dcls, gcat)
@@ -186,7 +305,7 @@ def match_image(image_id: int, dbox: np.ndarray, dscore: np.ndarray, dcls: np.nd
         di = np.flatnonzero(dcls == c)
         di = di[np.argsort(-dscore[di], kind="mergesort")][:MAX_DETS]
         gi = np.flatnonzero(gcat == c)
-        m, ig, nn = match_image_category(dbox[di], gbox[gi], gflag[gi], garea[gi])
+        m, ig, nn = match(di, gi)
         npig[c] += nn
         parts["image_id"].append(np.full(len(di), image_id, np.int64))
         parts["category"].append(np.full(len(di), c, np.int32))
@@ -250,8 +369,8 @@ def summarize(precision: np.ndarray, class_names: Sequence[str]) -> "OrderedDict
     return OrderedDict((k, (v if np.isfinite(v) else None)) for k, v in res.items())
 
 
-def results_from(rec: MatchRecords, class_names: Sequence[str]) -> "OrderedDict":
-    return OrderedDict({"bbox": summarize(accumulate(rec), class_names)})
+def results_from(rec: MatchRecords, class_names: Sequence[str], key: str = "bbox") -> "OrderedDict":
+    return OrderedDict({key: summarize(accumulate(rec), class_names)})
 
 
 # ---------------------------------------------------------------------------------------------------------------- evaluator
@@ -306,6 +425,59 @@ class DetectionEvaluator:
         if rec is None:
             return {}
         return results_from(rec, self.class_names)
+
+
+class InstanceSegmentationEvaluator:
+    """The reference's InstanceSegmentationEvaluator (DetectionEvaluator with task "segm") on the host.  ``process(inputs, outputs)``:
+    ``inputs`` dataset entries with ``image_id``, ``height``, ``width`` and their ground truth (ground_truth_masks()), ``outputs`` either
+    MaskFormerProcessor.eval_postprocess's ``[{"instances": Instances}]`` (masks, scores, classes) or raw arrays ``[{"masks": bool [N, H, W],
+    "scores": [N], "classes": [N]}]``.  Every prediction is scored, an empty mask included (instance_inference filters nothing).
+    ``evaluate()`` -> ``{"segm": {...}}`` ({} without a prediction)."""
+
+    def __init__(self, class_names: Sequence[str]):
+        self.class_names = list(class_names)
+        self.reset()
+
+    def reset(self):
+        self._images = {}
+
+    @staticmethod
+    def _arrays(output):
+        if "instances" in output:
+            inst = output["instances"]
+            masks, scores, classes = (inst.masks.tensor if hasattr(inst.masks, "tensor") else inst.masks), inst.scores, inst.classes
+        elif "masks" in output:
+            masks, scores, classes = output["masks"], output["scores"], output["classes"]
+        else:
+            raise Exception("No instances in output?!")
+        to_np = lambda t, dt: np.array(torch.as_tensor(t).detach().cpu().numpy(), dtype=dt)   # noqa: E731
+        m = to_np(masks, bool)
+        return m.reshape((-1,) + m.shape[-2:]), to_np(scores, np.float32).reshape(-1), to_np(classes, np.int64).reshape(-1)
+
+    def process(self, inputs, outputs):
+        for inp, out in zip(inputs, outputs):
+            image_id = inp.get("image_id") if isinstance(inp, dict) else getattr(inp, "image_id", None)
+            assert image_id is not None, "Image ID must be present in the input!"
+            if int(image_id) in self._images:
+                raise ValueError(f"image id {image_id} was processed twice")
+            masks, scores, classes = self._arrays(out)
+            if len(scores) == 0:
+                continue                                     # an image without predictions contributes nothing, its ground truth included
+            gt = ground_truth_masks(inp)
+            if masks.shape[1:] != gt[0].shape[1:]:
+                raise ValueError(f"predicted masks {masks.shape[1:]} do not match the entry's (height, width) {gt[0].shape[1:]}")
+            self._images[int(image_id)] = (masks, scores.astype(np.float64), classes, gt)
+
+    def records(self) -> Optional[MatchRecords]:
+        K = len(self.class_names)
+        parts = [match_image_masks(i, *self._images[i], K) for i in sorted(self._images)]
+        return MatchRecords.merge(parts) if parts else None
+
+    def evaluate(self):
+        rec = self.records()
+        if rec is None:
+            return {}
+        return results_from(rec, self.class_names, "segm")
 
 
 # ---------------------------------------------------------------------------------------------------------------- device side
@@ -391,7 +563,7 @@ def check_supported(focoos_model) -> None:
     fam = focoos_model.model.family
     if fam != "fai_detr":
         raise NotImplementedError(f"FocoosModel.eval_detection: COCO bbox AP is evaluated for the fai_detr family only, not {fam!r} "
-                                  "(segm AP needs RLE mask IoU, which is not built)")
+                                  "(instance segmentation is scored by FocoosModel.eval_instance_segmentation)")
 
 
 def resolve(focoos_model, data_test):

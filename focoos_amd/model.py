@@ -371,7 +371,8 @@ class FocoosModel:
         ClassificationDatasetDict items, metadata from ``data_test.dataset.metadata`` or ``data_test.metadata``), write
         ``args.output_dir/<run_name>_eval/{model_info,metrics}.json`` and return the results dict.  Semantic segmentation runs the fused
         fx_semseg_eval_accumulate kernel, classification counts TP / FP / FN on the device (evaluation.py).  Detection and instance
-        segmentation raise NotImplementedError (COCO AP needs pycocotools' COCOeval)."""
+        segmentation raise NotImplementedError here: ``eval_detection`` scores RT-DETR (COCO bbox AP) and ``eval_instance_segmentation`` the
+        instance-segmentation MaskFormer models (COCO segm AP)."""
         from .evaluation import run_eval
 
         return run_eval(self, args, data_test, save_json)
@@ -386,6 +387,18 @@ class FocoosModel:
 
         check_supported(self)
         return run_eval_detection(self, args, data_test, save_json)
+
+    def eval_instance_segmentation(self, args, data_test, save_json: bool = True) -> dict:
+        """COCO segm AP of an instance-segmentation MaskFormer model (fai-mf-*-coco-ins) on ``data_test`` (indexable; entries with ``image``,
+        ``height``, ``width`` and ground-truth masks as ``annotations[i]["segmentation"]`` - a 2-D array or an uncompressed RLE dict - or
+        ``instances.masks``): same arguments and artifacts as ``eval``, returns ``{"segm": {"AP", "AP50", "AP75", "APs", "APm", "APl",
+        "AP-<class>"...}}`` like the reference's InstanceSegmentationEvaluator.  Masks are thresholded into bit-packed words, intersected and
+        matched on the device (fx_mf_eval_masks + fx_coco_mask_inter + fx_coco_match_segm; segm_eval.py), accumulated in numpy float64.
+        Every other family, and a semantic fai_mf, raises NotImplementedError before anything is created."""
+        from .segm_eval import check_supported, run_eval_instance_segmentation
+
+        check_supported(self)
+        return run_eval_instance_segmentation(self, args, data_test, save_json)
 
     def export(self, *a, **k):
         raise NotImplementedError("FocoosModel.export: the ONNX/TensorRT export path is out of scope (BASELINE north_star)")

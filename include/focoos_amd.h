@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 12
+#define FX_ABI_VERSION 13
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -198,6 +198,39 @@ int fx_coco_match_bbox(const int32_t* label, const float* score, const int32_t* 
                        const double* gt_box, const int32_t* gt_cat, const int32_t* gt_flag, const double* gt_area, const int64_t* gt_off,
                        const int64_t* gt_off_host, int64_t n_gt, int max_gt, int32_t* rank, uint64_t* matched, uint64_t* ignored,
                        int64_t* npig, int32_t* status, void* ws, size_t ws_bytes, fx_stream_t stream);
+
+/* ---- COCO segm AP evaluation (ABI 13; csrc/coco_segm_eval.hip + csrc/coco_eval.hip): the device side of
+ * FocoosModel.eval_instance_segmentation.  Masks are bit-packed: 64 consecutive x of a row are one 64-bit word (bit i = pixel 64 c + i), a
+ * plane is [H][ceil(W / 64)] words = int32 [H][2 ceil(W / 64)], tail bits zero.  Offsets are in 64-bit words, have B + 1 entries and are
+ * given on the device and on the host; the host copies (and sizes_host) are validated - image b's span must hold its planes and end inside
+ * the buffer of n_words.
+ * fx_mf_eval_masks = MaskFormerProcessor.eval_postprocess + instance_inference for a batch run at one input size (Hin, Win): for every
+ * query a top-k slot of its image refers to (idx [B][T] into [Q K], val [B][T] the slot's class probability, from fx_topk_rows_ws_f32),
+ * m = mask_probs [B][Q][h][w] sampled at every pixel of the original size sizes[b] = (H_b, W_b) with fx_semseg_eval_accumulate's two-stage
+ * arithmetic, bit = m > mask_threshold, written to words at word_off[b] + q H_b ceil(W_b / 64) (planes of other queries are not touched);
+ * count [B][Q] = pixels, box [B][Q][4] = BitMasks.get_bounding_boxes (x0, y0, x1 + 1, y1 + 1; zeros when empty), psum [B][Q] = the fp32 sum of m
+ * inside the mask in a fixed order that depends on (H_b, W_b) alone; qlist [B][Q] / nref [B] = the referenced queries, ascending.  Per slot:
+ * label = idx % K, query = idx / K, score = val * (psum / ((float)count + 1e-3f)).  ws: fx_mf_eval_masks_workspace_bytes(B, Q, max_b H_b).
+ * fx_coco_mask_inter: inter[Q gt_off[b] + q G_b + g] = |mask of referenced query q AND ground-truth mask g of image b| (G_b = gt_off[b + 1]
+ * - gt_off[b]; gt_words at gt_word_off[b] + g H_b ceil(W_b / 64); gt_box [n_gt][4] = x0, y0, x1, y1 with exclusive ends bounds the words
+ * that are read), gcount [n_gt] = pixels of a ground-truth mask.  T as in fx_mf_eval_masks.
+ * fx_coco_match_segm = fx_coco_match_bbox for iouType "segm": every slot is scored, a detection's area is count[b][query], IoU = 0 when
+ * inter == 0, else (double)inter / (double)(crowd ? da : da + ga - inter) with the integer sum exact; everything else as fx_coco_match_bbox.
+ * Q <= 128; anything outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched.  The same in both libraries. */
+size_t fx_mf_eval_masks_workspace_bytes(int B, int Q, int max_h);
+int fx_mf_eval_masks(const float* mask_probs, const float* val, const int32_t* idx, int B, int Q, int K, int T, int h, int w, int Hin, int Win,
+                     const int32_t* sizes, const int32_t* sizes_host, const int64_t* word_off, const int64_t* word_off_host, int64_t n_words,
+                     float mask_threshold, void* words, int32_t* qlist, int32_t* nref, int32_t* count, int32_t* box, float* psum, int32_t* label,
+                     int32_t* query, float* score, void* ws, size_t ws_bytes, fx_stream_t stream);
+int fx_coco_mask_inter(const void* words, const int64_t* word_off, const int64_t* word_off_host, int64_t n_words, const int32_t* qlist,
+                       const int32_t* nref, const int32_t* box, int B, int Q, int T, const int32_t* sizes, const int32_t* sizes_host,
+                       const void* gt_words, const int64_t* gt_word_off, const int64_t* gt_word_off_host, int64_t n_gt_words,
+                       const int32_t* gt_box, const int64_t* gt_off, const int64_t* gt_off_host, int64_t n_gt, int32_t* inter, int32_t* gcount,
+                       fx_stream_t stream);
+int fx_coco_match_segm(const int32_t* label, const float* score, const int32_t* query, const int32_t* dcount, int B, int T, int K, int Q,
+                       const int32_t* inter, const int32_t* gcount, const int32_t* gt_cat, const int32_t* gt_flag, const double* gt_area,
+                       const int64_t* gt_off, const int64_t* gt_off_host, int64_t n_gt, int max_gt, int32_t* rank, uint64_t* matched,
+                       uint64_t* ignored, int64_t* npig, int32_t* status, void* ws, size_t ws_bytes, fx_stream_t stream);
 
 /* ---- Training augmentation (ABI 11; csrc/augment.hip): flip, scale, crop, pad and colour jitter of a batch in one
  * resample.  One record per source image; all extents in pixels.  The placed window shows columns [crop_x, crop_x + crop_w) / rows
