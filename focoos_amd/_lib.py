@@ -62,6 +62,15 @@ class FxPackEntry(C.Structure):
     ]
 
 
+class FxPublishEntry(C.Structure):
+    """include/focoos_amd.h fx_publish_entry"""
+    _fields_ = [
+        ("w", C.c_void_p), ("bn_weight", C.c_void_p), ("bn_bias", C.c_void_p), ("bn_mean", C.c_void_p), ("bn_var", C.c_void_p),
+        ("bias", C.c_void_p), ("w_rows", C.c_void_p), ("w_frag", C.c_void_p), ("bias_out", C.c_void_p), ("eps", C.c_double),
+        ("N", C.c_int32), ("C", C.c_int32), ("KH", C.c_int32), ("KW", C.c_int32), ("Np", C.c_int32), ("first_block", C.c_int32),
+    ]
+
+
 class FxPwChainDesc(C.Structure):
     _fields_ = [
         ("x1", C.c_void_p), ("x2", C.c_void_p), ("residual", C.c_void_p), ("w1", C.c_void_p), ("bias1", C.c_void_p), ("y1", C.c_void_p),
@@ -217,6 +226,8 @@ SIGNATURES = {
     "fx_pack_entry_blocks": [_i, _i, _i, _i],
     "fx_pack_weights_many_f32": [_vp, _i, _i, _vp],
     "fx_pack_frag_bf16": [_vp, _vp, _i, _i, _vp],
+    "fx_publish_entry_blocks": [_i, _i, _i, _i],
+    "fx_publish_weights_f32": [_vp, _i, _i, _vp],
     "fx_pack_linear_weights_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "fx_box_refine_f32": [_vp, _vp, _vp, C.c_int64, _f, _vp],
     "fx_box_refine_bwd_f32": [_vp, _vp, _vp, _vp, _vp, C.c_int64, _f, _vp],
@@ -279,7 +290,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 13  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 14  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:

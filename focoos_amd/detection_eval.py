@@ -620,7 +620,7 @@ def collect(focoos_model, data_test, indices: Sequence[int], batch_size: int) ->
         return records_from_device(indices[:pos], *cat, npig, K)
     finally:
         torch.cuda.synchronize(dev)
-        for k in [k for k in eng.plans.keys() if k not in before]:
+        for k in [k for k in eng.plans.keys() if k not in before and not getattr(eng, "retain_plans", False)]:
             del eng.plans[k]
 
 

@@ -23,6 +23,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -144,6 +145,91 @@ def _concurrent_streams(dev: torch.device, n: int) -> List["torch.cuda.Stream"]:
     return chosen
 
 
+def publish_table(entries: Sequence[Tuple], dev: torch.device) -> None:
+    """One fx_publish_weights_f32 launch (csrc/publish.hip) on the current stream of ``dev``.  An entry is ``(W, bn, bias, w_rows, w_frag,
+    bias_out, Np)``: W fp32 [N, C, KH, KW] on the device; ``bn`` = None or the (weight, bias, running_mean, running_var) vectors; ``bias``
+    = None or the conv bias [N]; the destinations (or None) hold Np x KH*KW*C bf16, N x KH*KW*C bf16 in fragment order and Np fp32."""
+    lib = _lib.load()
+    arr = (_lib.FxPublishEntry * len(entries))()
+    keep, blocks = [], 0
+    for e, (W, bn, bias, w_rows, w_frag, bias_out, Np) in zip(arr, entries):
+        N, Cc, KH, KW = (int(v) for v in W.shape)
+        src = [W] + list(bn or ()) + ([bias] if bias is not None else [])
+        src = [t.detach().to(torch.float32).contiguous() for t in src]
+        if any(t.device != dev for t in src):
+            raise _lib.FocoosAmdError("publish: source tensors must be on the engine's device")
+        if bn is not None and any(t.numel() != N for t in src[1:5]) or bias is not None and src[-1].numel() != N:
+            raise _lib.FocoosAmdError(f"publish: per-channel vectors of a layer with {N} output channels have other lengths")
+        K = KH * KW * Cc
+        if Np % 8 or Np < N or (w_rows is not None and (w_rows.numel() != Np * K or w_rows.element_size() != 2)) \
+                or (w_frag is not None and (N % 32 or K % 16 or w_frag.numel() != N * K or w_frag.element_size() != 2)) \
+                or (bias_out is not None and (bias_out.numel() != Np or bias_out.dtype != torch.float32)):
+            raise _lib.FocoosAmdError(f"publish: destinations do not fit a [{N}, {Cc}, {KH}, {KW}] layer padded to {Np} rows")
+        keep.append(src)
+        e.w = src[0].data_ptr()
+        if bn is not None:
+            e.bn_weight, e.bn_bias, e.bn_mean, e.bn_var = (t.data_ptr() for t in src[1:5])
+        elif bias is not None:
+            e.bias = src[-1].data_ptr()
+        e.w_rows = w_rows.data_ptr() if w_rows is not None else None
+        e.w_frag = w_frag.data_ptr() if w_frag is not None else None
+        e.bias_out = bias_out.data_ptr() if bias_out is not None else None
+        e.eps, e.N, e.C, e.KH, e.KW, e.Np, e.first_block = BN_EPS, N, Cc, KH, KW, Np, blocks
+        nb = int(lib.fx_publish_entry_blocks(Np, Cc, KH, KW))
+        if nb <= 0:
+            raise _lib.FocoosAmdError(f"fx_publish_entry_blocks({Np}, {Cc}, {KH}, {KW}) = {nb}")
+        blocks += nb
+    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    check(lib.fx_publish_weights_f32(table.data_ptr(), len(entries), blocks, torch.cuda.current_stream(dev).cuda_stream), "fx_publish_weights_f32")
+    # (table and sources may be released now: the caching allocator keeps their memory until the stream has passed the launch)
+
+
+class _Publisher:
+    """Publish-mode back end of the packing helpers (``_EngineBase.publish_state_dict``): walks the buffers ``load_state_dict`` recorded, in
+    the same order, checks that each helper call still describes the buffer it meets and queues its refill.  Nothing is written before
+    ``launch``: the weight images and biases in one table launch, the small fp32 vectors (LayerNorm pairs, side tables) as device copies."""
+
+    def __init__(self, eng: "_EngineBase"):
+        self.eng, self.slots, self.i = eng, eng._slots, 0
+        self.entries: List[Tuple] = []
+        self.copies: List[Tuple[torch.Tensor, torch.Tensor]] = []
+
+    def _next(self, kind, what: str):
+        if self.i >= len(self.slots) or not isinstance(self.slots[self.i], kind):
+            raise _lib.FocoosAmdError(f"publish_state_dict: the packing sequence differs from the one that filled the engine (call {self.i}: {what})")
+        self.i += 1
+        return self.slots[self.i - 1]
+
+    def copy(self, t: torch.Tensor, dtype) -> torch.Tensor:
+        dst = self._next(torch.Tensor, "vector")
+        if tuple(dst.shape) != tuple(t.shape) or dst.dtype != dtype:
+            raise _lib.FocoosAmdError(f"publish_state_dict: a {tuple(t.shape)} {dtype} table meets a {tuple(dst.shape)} {dst.dtype} buffer")
+        self.copies.append((dst, t))
+        return dst
+
+    def conv(self, W4: torch.Tensor, bias: Optional[torch.Tensor], bn: Optional[Tuple] = None) -> PackedConv:
+        pc = self._next(PackedConv, "conv")
+        if (pc.N, pc.C, pc.KH, pc.KW) != tuple(W4.shape):
+            raise _lib.FocoosAmdError(f"publish_state_dict: a {tuple(W4.shape)} weight meets a packed [{pc.N}, {pc.C}, {pc.KH}, {pc.KW}] layer")
+        self.entries.append((W4, bn, bias, pc.w, pc.wf, pc.b, pc.w.shape[0]))
+        return pc
+
+    def frag(self, W2: torch.Tensor) -> torch.Tensor:
+        dst = self._next(torch.Tensor, "fragment image")
+        N, K = W2.shape
+        if N % 32 or K % 16 or tuple(dst.shape) != (N // 32, K // 16, 64, 8):
+            raise _lib.FocoosAmdError(f"publish_state_dict: a [{N}, {K}] matrix meets a fragment image of shape {tuple(dst.shape)}")
+        self.entries.append((W2.reshape(N, K, 1, 1), None, None, None, dst, None, N))
+        return dst
+
+    def launch(self) -> None:
+        if self.i != len(self.slots):
+            raise _lib.FocoosAmdError(f"publish_state_dict: {len(self.slots) - self.i} buffers of the engine were not reached")
+        publish_table(self.entries, self.eng.dev)
+        for dst, t in self.copies:
+            dst.copy_(t, non_blocking=True)
+
+
 class _EngineBase:
     """Device handle, weight-packing helpers and the ResNet-vd backbone weights shared by the model families."""
 
@@ -163,11 +249,77 @@ class _EngineBase:
         self.stream = _device_stream(self.dev, 0)
         self.plans: Dict[Tuple, "_PlanBase"] = {}
         self.ln: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self.retain_plans = False   # True (validation.Validator): the evaluators leave the plans they create in place
+        self._pub: Optional["_Publisher"] = None   # set while publish_state_dict replays the packing code
+        self._slots: Optional[List] = None         # buffers of the last load_state_dict, in packing order
+        self._replicas: List[Tuple] = []           # (weak reference to a plan's replicated weight table, attribute name, batch): _replicated
 
-    def _dev(self, t: torch.Tensor, dtype=None) -> torch.Tensor:
+    # ---- packing helpers.  ``load_state_dict`` (host tensors) allocates: between ``_begin_load`` and ``_end_load`` every buffer a helper
+    # returns is recorded, in call order, in ``self._slots``.  ``publish_state_dict`` (device tensors) replays the SAME packing code with
+    # ``self._pub`` set: each helper call takes the next recorded buffer and queues its refill, in place, for the one fx_publish_weights_f32
+    # launch (``_Publisher``) - the packing code of an engine exists once and serves both.
+    def _begin_load(self, sd) -> Dict[str, torch.Tensor]:
+        self._slots: Optional[List] = []
+        self._sd_shapes = {k: tuple(v.shape) for k, v in sd.items()}
+        return {k: v.detach().cpu() for k, v in sd.items()}
+
+    def _end_load(self) -> None:
+        self.plans.clear()
+
+    def publish_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        """Refill every packed buffer from ``sd`` - the keys and shapes of the last ``load_state_dict``, tensors ON the engine's device
+        (a training run's parameters or EMA copy) - with what ``load_state_dict`` of the same values would have produced, bit for bit, at
+        the same addresses: no host copy of the weights, ``self.plans`` (captured graphs, timed whole-batch plans) stays alive.  A key set
+        or a shape that differs raises ``FocoosAmdError`` before anything is written."""
+        shapes = getattr(self, "_sd_shapes", None)
+        if not shapes or getattr(self, "_slots", None) is None:
+            raise _lib.FocoosAmdError("publish_state_dict needs an engine whose weights were loaded with load_state_dict")
+        if set(sd) != set(shapes):
+            diff = sorted(set(sd) ^ set(shapes))
+            raise _lib.FocoosAmdError(f"publish_state_dict: key set differs from the engine's ({len(diff)} keys, e.g. {diff[:3]})")
+        for k, v in sd.items():
+            if tuple(v.shape) != shapes[k]:
+                raise _lib.FocoosAmdError(f"publish_state_dict: {k} has shape {tuple(v.shape)}, the engine holds {shapes[k]}")
+            if v.device != self.dev:
+                raise _lib.FocoosAmdError(f"publish_state_dict: {k} is on {v.device}, the engine on {self.dev} (host weights: load_state_dict)")
+        self._pub = _Publisher(self)
+        try:
+            with torch.no_grad():
+                self._pack_all({k: v.detach() for k, v in sd.items()})
+            self._pub.launch()
+            alive = []
+            for ref, name, B in self._replicas:      # the plans' own per-batch copies of weight tables
+                t = ref()
+                if t is not None:
+                    t.copy_(getattr(self, name).repeat(B, 1))
+                    alive.append((ref, name, B))
+            self._replicas = alive
+        finally:
+            self._pub = None
+
+    def _replicated(self, name: str, B: int) -> torch.Tensor:
+        """[B * rows, C] copy of the weight table ``self.<name>`` for a plan (a row-chain LOAD stage reads row m of a global matrix).  The
+        engine remembers it weakly: ``publish_state_dict`` refreshes the copies of the plans that are alive."""
+        t = getattr(self, name).repeat(B, 1).contiguous()
+        self._replicas.append((weakref.ref(t), name, B))
+        return t
+
+    def _rec(self, x):
+        if getattr(self, "_slots", None) is not None:
+            self._slots.append(x)
+        return x
+
+    def _to_dev(self, t: torch.Tensor, dtype=None) -> torch.Tensor:
         return t.to(device=self.dev, dtype=dtype or t.dtype).contiguous()
 
+    def _dev(self, t: torch.Tensor, dtype=None) -> torch.Tensor:
+        if self._pub is not None:
+            return self._pub.copy(t, dtype or t.dtype)
+        return self._rec(self._to_dev(t, dtype))
+
     def _pack(self, W4: torch.Tensor, bias: Optional[torch.Tensor]) -> PackedConv:
+        if self._pub is not None:
+            return self._pub.conv(W4, bias)
         N, Cc, KH, KW = W4.shape
         Np = (N + 127) // 128 * 128
         w = torch.zeros(Np, KH, KW, Cc, dtype=torch.float32)
@@ -179,16 +331,27 @@ class _EngineBase:
         if KH == KW and _lib.conv_frag_eligible(N, Cc, KH):
             # second copy in MFMA fragment order (fx_conv_desc.w_frag) for the fragment-order 3x3 / pointwise kernels:
             # k = (kh*KW + kw)*C + c
-            wf = self._pack_frag(W4.permute(0, 2, 3, 1).reshape(N, KH * KW * Cc))
-        return PackedConv(self._dev(w, torch.bfloat16), self._dev(b), N, Cc, KH, KW, wf)
+            wf = self._frag_image(W4.permute(0, 2, 3, 1).reshape(N, KH * KW * Cc))
+        return self._rec(PackedConv(self._to_dev(w, torch.bfloat16), self._to_dev(b), N, Cc, KH, KW, wf))
+
+    def _pack_bn(self, sd, conv_w_key: str, bn_prefix: str) -> PackedConv:
+        """conv + eval BatchNorm as one packed layer: ``_pack(*_fold_bn(...))``; a publish hands the five tensors to the kernel, which folds."""
+        if self._pub is not None:
+            return self._pub.conv(sd[conv_w_key], None, tuple(sd[f"{bn_prefix}.{k}"] for k in ("weight", "bias", "running_mean", "running_var")))
+        return self._pack(*_fold_bn(sd, conv_w_key, bn_prefix))
+
+    def _frag_image(self, W2: torch.Tensor) -> torch.Tensor:
+        N, K = W2.shape
+        assert N % 32 == 0 and K % 16 == 0, (N, K)
+        w = W2.float().reshape(N // 32, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()  # [nb][ks][half][row][8]
+        return self._to_dev(w.reshape(N // 32, K // 16, 64, 8), torch.bfloat16)
 
     def _pack_frag(self, W2: torch.Tensor) -> torch.Tensor:
         """[N, K] weights in MFMA fragment order [N/32][K/16][lane][8] (include/focoos_amd.h, fx_pw_chain_desc): lane l of
         fragment (nb, ks) holds W[nb*32 + l%32][ks*16 + (l//32)*8 : +8] - one contiguous 1 KiB read per wave and fragment."""
-        N, K = W2.shape
-        assert N % 32 == 0 and K % 16 == 0, (N, K)
-        w = W2.float().reshape(N // 32, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()  # [nb][ks][half][row][8]
-        return self._dev(w.reshape(N // 32, K // 16, 64, 8), torch.bfloat16)
+        if self._pub is not None:
+            return self._pub.frag(W2)
+        return self._rec(self._frag_image(W2))
 
     def _pack_linear(self, W: torch.Tensor, b: Optional[torch.Tensor]) -> PackedConv:
         return self._pack(W.float().view(W.shape[0], W.shape[1], 1, 1), None if b is None else b.float())
@@ -201,7 +364,7 @@ class _EngineBase:
         bb = "pixel_decoder.backbone"
 
         def cbn(name):
-            P[name] = self._pack(*_fold_bn(sd, f"{name}.conv.weight", f"{name}.norm"))
+            P[name] = self._pack_bn(sd, f"{name}.conv.weight", f"{name}.norm")
 
         # stem conv1_1 stays fp32 [kh][kw][c][n] (direct-conv kernel, weights via LDS)
         w, b = _fold_bn(sd, f"{bb}.conv1.conv1_1.conv.weight", f"{bb}.conv1.conv1_1.norm")
@@ -261,11 +424,16 @@ class DetrEngine(StdcEngineMixin, _EngineBase):
 
     # ------------------------------------------------------------------ weight packing
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        sd = {k: v.detach().cpu() for k, v in sd.items()}
+        self._pack_all(self._begin_load(sd))
+        self._end_load()
+
+    def _pack_all(self, sd: Dict[str, torch.Tensor]) -> None:
+        """The packing sequence, for host tensors (load_state_dict) and device tensors (publish_state_dict) alike: whatever it composes
+        with torch stays on the device of ``sd``."""
         P: Dict[str, PackedConv] = {}
 
         def cbn(name, conv="conv", norm="norm"):
-            P[name] = self._pack(*_fold_bn(sd, f"{name}.{conv}.weight", f"{name}.{norm}"))
+            P[name] = self._pack_bn(sd, f"{name}.{conv}.weight", f"{name}.{norm}")
 
         if self.stdc:
             self._pack_stdc(sd, P)
@@ -273,7 +441,7 @@ class DetrEngine(StdcEngineMixin, _EngineBase):
             self._pack_backbone(sd, P)
         pd = "pixel_decoder"
         for i in range(3):
-            P[f"{pd}.input_proj.{i}"] = self._pack(*_fold_bn(sd, f"{pd}.input_proj.{i}.0.weight", f"{pd}.input_proj.{i}.1"))
+            P[f"{pd}.input_proj.{i}"] = self._pack_bn(sd, f"{pd}.input_proj.{i}.0.weight", f"{pd}.input_proj.{i}.1")
         for li in range(self.n_enc):
             p = f"{pd}.encoder.0.layers.{li}"
             Wi, bi_ = sd[f"{p}.self_attn.in_proj_weight"], sd[f"{p}.self_attn.in_proj_bias"]
@@ -320,16 +488,18 @@ class DetrEngine(StdcEngineMixin, _EngineBase):
         self.score_head = None
         ncp = (self.nc + 127) // 128 * 128
         if ncp <= 384:
-            w2 = torch.zeros(ncp, self.hd)
-            w2[: self.nc] = sd[f"{hp}.enc_score_classifier.weight"].float()
-            b2 = torch.full((ncp,), -3e38)
-            b2[: self.nc] = sd[f"{hp}.enc_score_classifier.bias"].float()
+            sw, sb = sd[f"{hp}.enc_score_classifier.weight"].float(), sd[f"{hp}.enc_score_classifier.bias"].float()
+            w2 = sw.new_zeros(ncp, self.hd)
+            w2[: self.nc] = sw
+            b2 = sb.new_full((ncp,), -3e38)
+            b2[: self.nc] = sb
             self.score_head = (self._pack_frag(sd[f"{hp}.enc_output.0.weight"].float()), self._dev(sd[f"{hp}.enc_output.0.bias"].float()),
                                self._pack_frag(w2), self._dev(b2), ncp)
-        # constant output_memory row of masked (invalid-anchor) tokens: LN(Linear(0)) = LN(bias)
-        b0 = sd[f"{hp}.enc_output.0.bias"].float()
-        row = torch.nn.functional.layer_norm(b0.to(torch.bfloat16).float(), (self.hd,), sd[f"{hp}.enc_output.1.weight"].float(),
-                                             sd[f"{hp}.enc_output.1.bias"].float(), 1e-5)
+        # constant output_memory row of masked (invalid-anchor) tokens: LN(Linear(0)) = LN(bias).  Always evaluated on the host (a publish
+        # fetches these three 256-vectors): a device LayerNorm sums in another order, and the row has to come out bit-identical
+        b0 = sd[f"{hp}.enc_output.0.bias"].float().cpu()
+        row = torch.nn.functional.layer_norm(b0.to(torch.bfloat16).float(), (self.hd,), sd[f"{hp}.enc_output.1.weight"].float().cpu(),
+                                             sd[f"{hp}.enc_output.1.bias"].float().cpu(), 1e-5)
         self.invalid_row = self._dev(row, torch.bfloat16)
 
         def mlp3(prefix, key):
@@ -370,8 +540,8 @@ class DetrEngine(StdcEngineMixin, _EngineBase):
         def rc(key, W, b, pad_to=None):
             W, b = W.float(), b.float()
             if pad_to is not None and W.shape[0] < pad_to:
-                W = torch.cat([W, torch.zeros(pad_to - W.shape[0], W.shape[1])], 0)
-                b = torch.cat([b, torch.zeros(pad_to - b.shape[0])], 0)
+                W = torch.cat([W, W.new_zeros(pad_to - W.shape[0], W.shape[1])], 0)
+                b = torch.cat([b, b.new_zeros(pad_to - b.shape[0])], 0)
             RC[key] = (self._pack_frag(W), self._dev(b))
 
         rc("qpos1", sd[f"{hp}.query_pos_head.layers.1.weight"], sd[f"{hp}.query_pos_head.layers.1.bias"])
@@ -397,7 +567,6 @@ class DetrEngine(StdcEngineMixin, _EngineBase):
         rc("score", sd[f"{hp}.dec_score_classifier.{last}.weight"], sd[f"{hp}.dec_score_classifier.{last}.bias"], pad_to=self.nc_pad32)
         self.RC = RC
         self.P = P
-        self.plans.clear()
 
     # ------------------------------------------------------------------ constants that depend on the input size
     @staticmethod

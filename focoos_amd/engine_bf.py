@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import _lib
-from .engine import DEFAULT_STREAMS, MIN_PART_BATCH, NT, PackedConv, _EngineBase, _MultiPlan, _PlanBase, _fold_bn
+from .engine import DEFAULT_STREAMS, MIN_PART_BATCH, NT, PackedConv, _EngineBase, _MultiPlan, _PlanBase
 from .engine_maskdec import MaskDecoderPlanMixin, pack_masked_decoder, pos_embed_sine_normalized
 from .engine_stdc import StdcEngineMixin, StdcPlanMixin, _bn_scale_shift
 
@@ -63,14 +63,18 @@ class BfEngine(StdcEngineMixin, _EngineBase):
 
     # ------------------------------------------------------------------ weight packing
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        sd = {k: v.detach().cpu() for k, v in sd.items()}
+        self._pack_all(self._begin_load(sd))
+        self._end_load()
+
+    def _pack_all(self, sd: Dict[str, torch.Tensor]) -> None:
+        """The packing sequence, for host tensors (load_state_dict) and device tensors (publish_state_dict) alike."""
         P: Dict[str, PackedConv] = {}
         self.ln = {}
         self.vec: Dict[str, torch.Tensor] = {}   # fp32 side tables: depthwise filters, pooled 1x1 convs
         bb = "pixel_decoder.backbone"
 
         def cbn(name):   # ConvX / ConvBNReLU: conv + BatchNorm folded
-            P[name] = self._pack(*_fold_bn(sd, f"{name}.conv.weight", f"{name}.bn"))
+            P[name] = self._pack_bn(sd, f"{name}.conv.weight", f"{name}.bn")
 
         self._pack_stdc(sd, P)
         pd = "pixel_decoder"
@@ -94,7 +98,6 @@ class BfEngine(StdcEngineMixin, _EngineBase):
         cbn(f"{pd}.conv_out")
         pack_masked_decoder(self, sd, P, self.nlev)
         self.P = P
-        self.plans.clear()
 
     # ------------------------------------------------------------------ run
     def plan(self, B: int, H: int, W: int, f32_input: bool = False, full_masks: Optional[bool] = None, nsplit: Optional[int] = None):

@@ -88,10 +88,11 @@ def pack_masked_decoder(eng, sd: Dict[str, torch.Tensor], P: Dict[str, PackedCon
     RC: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
 
     def rc(key, W, b, pad_n=None):
-        W, b = W.float(), (b.float() if b is not None else torch.zeros(W.shape[0]))
+        W = W.float()
+        b = b.float() if b is not None else W.new_zeros(W.shape[0])
         if pad_n is not None and W.shape[0] < pad_n:
-            W = torch.cat([W, torch.zeros(pad_n - W.shape[0], W.shape[1])], 0)
-            b = torch.cat([b, torch.zeros(pad_n - b.shape[0])], 0)
+            W = torch.cat([W, W.new_zeros(pad_n - W.shape[0], W.shape[1])], 0)
+            b = torch.cat([b, b.new_zeros(pad_n - b.shape[0])], 0)
         RC[key] = (eng._pack_frag(W), eng._dev(b))
 
     for li in range(eng.nl):
@@ -153,7 +154,7 @@ class MaskDecoderPlanMixin:
             mfp.append(m)
         R = B * Q
         qe = NT(e.query_embed, Q, 1, 1, 256, 256)
-        out0 = e.query_feat.repeat(B, 1).contiguous()
+        out0 = e._replicated("query_feat", B)
         self.keep.append(out0)
         out = NT(out0, R, 1, 1, 256, 256)
         self.attn_bits: List[torch.Tensor] = []
@@ -254,7 +255,7 @@ class MaskDecoderPlanMixin:
         def add(a, b_, dst, out: Optional[NT] = None):
             return st(3, K=256, src=a, aux=b_, dst=dst, g0=out.ptr if out is not None else None, ld=out.ld if out is not None else 0)
 
-        qe_rep = e.query_embed.repeat(B, 1).contiguous()     # [R, 256]: a LOAD stage reads row m of a global matrix
+        qe_rep = e._replicated("query_embed", B)              # [R, 256]: a LOAD stage reads row m of a global matrix
         self.keep.append(qe_rep)
         qe_r = NT(qe_rep, R, 1, 1, 256, 256)
         mdn = RC["mc2"][0].shape[0] * 32                      # mask-embedding width as packed (zero-padded to 128 below that)

@@ -32,7 +32,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .engine import DEFAULT_STREAMS, MIN_PART_BATCH, NT, PackedConv, _EngineBase, _MultiPlan, _PlanBase, _fold_bn
+from .engine import DEFAULT_STREAMS, MIN_PART_BATCH, NT, PackedConv, _EngineBase, _MultiPlan, _PlanBase
 from .engine_stdc import StdcEngineMixin, StdcPlanMixin
 from .engine_maskdec import MaskDecoderPlanMixin, pack_mask_bits, pack_masked_decoder, pos_embed_sine_normalized  # noqa: F401  (pack_mask_bits re-exported)
 
@@ -73,7 +73,11 @@ class MfEngine(StdcEngineMixin, _EngineBase):
 
     # ------------------------------------------------------------------ weight packing
     def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        sd = {k: v.detach().cpu() for k, v in sd.items()}
+        self._pack_all(self._begin_load(sd))
+        self._end_load()
+
+    def _pack_all(self, sd: Dict[str, torch.Tensor]) -> None:
+        """The packing sequence, for host tensors (load_state_dict) and device tensors (publish_state_dict) alike."""
         P: Dict[str, PackedConv] = {}
         self.ln = {}
         if self.stdc:
@@ -96,7 +100,7 @@ class MfEngine(StdcEngineMixin, _EngineBase):
             c = Wi.shape[1]
 
             def pad_rows(W, b, scale=1.0):
-                Wp, bp = torch.zeros(256, c), torch.zeros(256)
+                Wp, bp = W.new_zeros(256, c), b.new_zeros(256)
                 for h in range(8):
                     Wp[32 * h:32 * h + 16] = W[16 * h:16 * h + 16] * scale
                     bp[32 * h:32 * h + 16] = b[16 * h:16 * h + 16] * scale
@@ -108,7 +112,7 @@ class MfEngine(StdcEngineMixin, _EngineBase):
             P[f"{prefix}.qk"] = self._pack_linear(torch.cat([wq, wk], 0), torch.cat([bq, bk], 0))
             P[f"{prefix}.v"] = self._pack_linear(wv, bv)
             Wo, bo = sd[f"{prefix}.{name}.out_proj.weight"].float(), sd[f"{prefix}.{name}.out_proj.bias"].float()
-            Wop = torch.zeros(c, 256)
+            Wop = Wo.new_zeros(c, 256)
             for h in range(8):
                 Wop[:, 32 * h:32 * h + 16] = Wo[:, 16 * h:16 * h + 16]
             P[f"{prefix}.out_proj"] = self._pack_linear(Wop, bo)
@@ -138,12 +142,11 @@ class MfEngine(StdcEngineMixin, _EngineBase):
             self._pack_ln(sd, f"{pd}.transformer.encoder.norm")
         for idx in (1, 2, 3, 4):
             if idx < 4:
-                P[f"{pd}.adapter_{idx}"] = self._pack(*_fold_bn(sd, f"{pd}.adapter_{idx}.weight", f"{pd}.adapter_{idx}.norm"))
-            P[f"{pd}.layer_{idx}"] = self._pack(*_fold_bn(sd, f"{pd}.layer_{idx}.weight", f"{pd}.layer_{idx}.norm"))
+                P[f"{pd}.adapter_{idx}"] = self._pack_bn(sd, f"{pd}.adapter_{idx}.weight", f"{pd}.adapter_{idx}.norm")
+            P[f"{pd}.layer_{idx}"] = self._pack_bn(sd, f"{pd}.layer_{idx}.weight", f"{pd}.layer_{idx}.norm")
         P[f"{pd}.mask_features"] = self._pack(sd[f"{pd}.mask_features.weight"].float(), sd[f"{pd}.mask_features.bias"].float())
         pack_masked_decoder(self, sd, P, self.nlev)
         self.P = P
-        self.plans.clear()
 
     _pos_embed_sine_normalized = staticmethod(pos_embed_sine_normalized)
 

@@ -70,14 +70,15 @@ class StdcEngineMixin:
         self.c16: Dict[str, tuple] = {}   # 3x3 layers with a 16-channel side (STDC-nano): fragment-order weights + bias for fx_conv3x3_c16_nhwc_bf16
 
         def cbn(name):   # ConvX: conv + BatchNorm folded
-            w, b = _fold_bn(sd, f"{name}.conv.weight", f"{name}.bn")
-            if w.shape[2] == 3 and 16 in (w.shape[0], w.shape[1]):
+            shape = sd[f"{name}.conv.weight"].shape
+            if shape[2] == 3 and 16 in (shape[0], shape[1]):
+                w, b = _fold_bn(sd, f"{name}.conv.weight", f"{name}.bn")
                 N, Cc = w.shape[0], w.shape[1]
-                w32 = torch.zeros(32, 3, 3, Cc, dtype=torch.float32)
+                w32 = w.new_zeros(32, 3, 3, Cc)
                 w32[:N] = w.permute(0, 2, 3, 1)
                 self.c16[name] = (self._pack_frag(w32.reshape(32, 9 * Cc)), self._dev(b), N, Cc)
                 return
-            P[name] = self._pack(w, b)
+            P[name] = self._pack_bn(sd, f"{name}.conv.weight", f"{name}.bn")
 
         w, b = _fold_bn(sd, f"{bb}.features.0.conv.weight", f"{bb}.features.0.bn")
         self.stem_w = self._dev(w.permute(2, 3, 1, 0).contiguous())  # [kh][kw][c][n] fp32 (direct-conv stem kernel)

@@ -283,7 +283,7 @@ def accumulate(focoos_model, data_test, indices: Sequence[int], task: str, ignor
         return counts
     finally:
         torch.cuda.synchronize(dev)
-        for k in [k for k in eng.plans.keys() if k not in before]:
+        for k in [k for k in eng.plans.keys() if k not in before and not getattr(eng, "retain_plans", False)]:
             del eng.plans[k]
 
 

@@ -115,6 +115,34 @@ class _EngineModel:
         self.engine.load_state_dict(new)
         return IncompatibleKeys(missing, unexpected, bad)
 
+    def publish_state_dict(self, state_dict: Dict[str, torch.Tensor]) -> None:
+        """Hand weights that live on the engine's device (a training run's parameters or EMA copy) to the inference engine in place
+        (``engine.publish_state_dict``: no host copy, the plans stay alive).  ``state_dict`` must hold every key of the model at its
+        shape; other keys are ignored.  ``state_dict()`` returns these values afterwards (fetched from the device on first use)."""
+        from ._lib import FocoosAmdError
+
+        cur = self._state_dev if self._state_dev is not None else self._state_host
+        new = OrderedDict()
+        for k, (shape, _) in self._spec.items():
+            if k not in state_dict:
+                raise FocoosAmdError(f"publish_state_dict: {k} is missing")
+            v = state_dict[k].detach()
+            if tuple(v.shape) != tuple(shape):
+                raise FocoosAmdError(f"publish_state_dict: {k} has shape {tuple(v.shape)}, the model holds {tuple(shape)}")
+            new[k] = v.to(cur[k].dtype)
+        self.engine.publish_state_dict(new)
+        self._state_dev = OrderedDict((k, v.clone()) for k, v in new.items())
+
+    @property
+    def _state(self) -> "OrderedDict[str, torch.Tensor]":
+        if self._state_dev is not None:     # the values of the last publish_state_dict: one device-to-host copy, when somebody asks
+            self._state_host, self._state_dev = OrderedDict((k, v.cpu()) for k, v in self._state_dev.items()), None
+        return self._state_host
+
+    @_state.setter
+    def _state(self, value) -> None:
+        self._state_host, self._state_dev = value, None
+
     # ---- forward
     def _to_nhwc(self, images: torch.Tensor) -> torch.Tensor:
         if images.dim() != 4:

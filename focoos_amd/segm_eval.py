@@ -252,7 +252,7 @@ def collect(focoos_model, data_test, indices: Sequence[int], batch_size: int) ->
         return records_from_device(indices[:pos], *[torch.cat([o[i] for o in outs]) for i in range(5)], npig, K)
     finally:
         torch.cuda.synchronize(dev)
-        for k in [k for k in eng.plans.keys() if k not in before]:
+        for k in [k for k in eng.plans.keys() if k not in before and not getattr(eng, "retain_plans", False)]:
             del eng.plans[k]
 
 

@@ -5,8 +5,9 @@ averaged with one bucketed RCCL all-reduce) over its shard of the total batch, r
 
 What is mirrored: the data-parallel partitioning (``TrainerArgs.batch_size`` is the TOTAL batch; ``TrainingSampler`` strides one
 identically seeded permutation by rank; rank RNG seed = seed + rank), the optimizer / schedule / EMA hyper-parameters, freeze_bn vs
-batch statistics (SyncBN when num_gpus > 1, as ``trainer.py:333-334`` converts), the artifact names.  What is not: hub syncing,
-visualisation hooks, periodic COCO evaluation, early stopping (trainer-side features outside SURVEY §8)."""
+batch statistics (SyncBN when num_gpus > 1, as ``trainer.py:333-334`` converts), the artifact names, and - with ``data_val`` and
+``0 < eval_period <= max_iters`` - the periodic validation, best checkpoint and early stopping (validation.py).  What is not: hub
+syncing, visualisation hooks (trainer-side features outside SURVEY §8)."""
 from __future__ import annotations
 
 import json
@@ -20,6 +21,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .ports import TrainerArgs
+from .validation import Validator, validation_iterations
 
 WEIGHTS_NAME = "model_final.pth"    # focoos.ports.ArtifactName.WEIGHTS
 INFO_NAME = "model_info.json"       # focoos.ports.ArtifactName.INFO
@@ -50,8 +52,7 @@ class ModelSnapshot:
 
 def check_supported(args: TrainerArgs) -> None:
     """TrainerArgs fields that change the training arithmetic of the reference and that this trainer does not implement are refused,
-    never ignored (fields that only steer hub syncing / visualisation / periodic evaluation / early stopping are accepted: see the
-    module docstring).  Reference: ``build_optimizer`` solver/build.py:39-138, ``TrainerLoop`` trainer/trainer.py:600-773."""
+    never ignored (fields that only steer hub syncing / visualisation are accepted: see the module docstring).  Reference: ``build_optimizer`` solver/build.py:39-138, ``TrainerLoop`` trainer/trainer.py:600-773."""
     if str(args.optimizer).upper() != "ADAMW":
         raise NotImplementedError(f"TrainerArgs.optimizer={args.optimizer!r}: the engine's optimizer is the fused AdamW (fx_adamw_step_f32)")
     if args.optimizer_extra:
@@ -88,11 +89,53 @@ def batch_assembler(data_train, family: str, processor, dev, seed: int, rank: in
     return lambda entries: augmenter(entries, gen)
 
 
+def _weights(net, stepper, ema_enabled: bool) -> Dict[str, torch.Tensor]:
+    """The weights a run would save now, where they live: the trainable graph's parameters and buffers on the device, the EMA copy's
+    views over them when EMA is on (no clone, no host copy)."""
+    state = {k: v.detach() for k, v in net.state_dict().items()}
+    if ema_enabled and stepper.ema is not None:
+        ema = dict(stepper.ema.views)
+        ema.update(stepper.ema.buf_state)
+        state.update({k: v.detach() for k, v in ema.items() if k in state})
+    return state
+
+
+def _ordered_state(order, net, stepper, ema_enabled: bool) -> "OrderedDict[str, torch.Tensor]":
+    """``_weights`` on the host in the reference's key order (``order``: state_spec), as torch.save of the reference module writes it."""
+    net_state = {k: v.cpu() for k, v in _weights(net, stepper, ema_enabled).items()}
+    full = OrderedDict((k, net_state[k]) for k in order if k in net_state)
+    full.update({k: v for k, v in net_state.items() if k not in full})
+    return full
+
+
+def _validation_model(model, model_info, dev):
+    """The engine-backed model validation runs on: the caller's, or - for a ``ModelSnapshot`` under ``launch`` - one built on this rank's
+    device from the model info (its weights are published before every use)."""
+    if hasattr(model, "engine"):
+        return model
+    import copy
+
+    from .model import ModelManager
+
+    info = copy.deepcopy(model_info)
+    info.weights_uri = None
+    return ModelManager.get(info.name, model_info=info, device=str(dev)).model
+
+
 def run_train(args: TrainerArgs, data_train, data_val, model, processor, model_info, hub=None) -> Dict[str, float]:
     """Per-rank training body.  ``model`` is the engine-backed FAIDetr / BisenetFormer mirror or its ``ModelSnapshot`` (its state_dict
     seeds the trainable graph); ``data_train[i]`` is a DatasetEntry.  Returns the last step's losses (floats) on every rank.
-    Ignored TrainerArgs fields (trainer-side features outside SURVEY §8): ckpt_dir, checkpointer_period / _max_to_keep, eval_period,
-    samples, early_stop, patience, workers, ddp_*, gather_metric_period, zero_grad_before_forward, sync_to_hub, size_divisibility."""
+
+    Validation (validation.py) runs only when ``data_val is not None`` and ``0 < args.eval_period <= args.max_iters``: after every
+    iteration ``it`` with ``(it + 1) % eval_period == 0`` and once more after the last one.  Rank 0 publishes the weights - the EMA copy
+    when ``ema_enabled`` - to the inference engine on the device (``publish_state_dict``: the caller's model, or under ``launch`` one model
+    built from the snapshot), scores ``data_val`` with the task's evaluator at the per-rank batch size and appends the record to
+    ``<run>/metrics.json``; the other ranks wait.  A strictly greater ``evaluation.TASK_METRICS[task]`` writes ``model_best.pth``; with
+    ``early_stop``, ``patience`` validations in a row without one end the loop.  At the end the best weights are ``model_final.pth`` (its
+    "iteration" the best record's), ``model_best.pth`` is gone and ``model_info.json`` carries ``val_metrics`` and ``val_history``.  Any
+    other call trains exactly as before and writes no further file.
+    Ignored TrainerArgs fields (trainer-side features outside SURVEY §8): ckpt_dir, checkpointer_period / _max_to_keep, samples, workers,
+    ddp_*, gather_metric_period, zero_grad_before_forward, sync_to_hub, size_divisibility."""
     check_supported(args)
     from .train_data import TrainingSampler, per_rank_batch_size, rank_seed
     from .train_detr import FAIDetrTrainable, TrainStep
@@ -119,6 +162,8 @@ def run_train(args: TrainerArgs, data_train, data_val, model, processor, model_i
 
     dtype = os.environ.get("FX_TRAIN_DTYPE", "bf16") if args.amp_enabled else "bf16"
     prev_dtype = _lib.set_compute_dtype(dtype)
+    validator = None
+    order = list(model.state_dict())   # the reference's key order
     try:     # the run's element type is restored whatever ends the run (a raising stepper.check() used to leave the process in fp16)
         net = trainable(model.config, norm=norm).to(dev)
         net.load_state_dict(model.state_dict(), strict=True)
@@ -134,6 +179,14 @@ def run_train(args: TrainerArgs, data_train, data_val, model, processor, model_i
         sampler = iter(TrainingSampler(len(data_train), shuffle=True, seed=args.seed, rank=rank, world_size=world))
         processor.train(True)
         losses: Dict[str, torch.Tensor] = {}
+        folder = os.path.join(args.output_dir, args.run_name.strip())
+        val_at = set(validation_iterations(args.max_iters, int(args.eval_period or 0))) if data_val is not None else set()
+        if val_at and rank == 0:
+            with _lib.using_compute_dtype("bf16"):
+                validator = Validator(_validation_model(model, model_info, dev), processor, model_info, data_val, folder, bs, args.early_stop,
+                                      args.patience, lambda: _weights(net, stepper, args.ema_enabled),
+                                      lambda iteration: {"model": _ordered_state(order, net, stepper, args.ema_enabled), "iteration": iteration})
+        done_iters = args.max_iters
         t0 = time.perf_counter()
         for it in range(args.max_iters):
             entries = [data_train[next(sampler)] for _ in range(bs)]
@@ -144,24 +197,34 @@ def run_train(args: TrainerArgs, data_train, data_val, model, processor, model_i
             if rank == 0 and args.log_period and (it + 1) % args.log_period == 0:
                 tot = float(sum(v.detach().float() for v in losses.values()))
                 print(f"[focoos_amd.train] iter {it + 1}/{args.max_iters} total_loss {tot:.4f} {(time.perf_counter() - t0) / (it + 1) * 1e3:.1f} ms/iter", flush=True)
+            if (it + 1) in val_at:
+                stepper.check()
+                stop = validator.run(it + 1) if validator is not None else False
+                if world > 1:        # the other ranks wait here for rank 0's validation and its verdict
+                    import torch.distributed as dist
+
+                    flag = torch.tensor([int(stop)], dtype=torch.int32, device=dev)
+                    dist.broadcast(flag, src=0)
+                    stop = bool(flag.item())
+                if stop:
+                    done_iters = it + 1
+                    break
         torch.cuda.synchronize(dev)
         stepper.check()
     finally:
         _lib.set_compute_dtype(prev_dtype)
+        if validator is not None:
+            validator.close()
     out = {k: float(v.detach().float()) for k, v in losses.items()}
     if rank == 0:
-        folder = os.path.join(args.output_dir, args.run_name.strip())
         os.makedirs(folder, exist_ok=True)
-        state = stepper.ema.state_dict() if (args.ema_enabled and stepper.ema is not None) else {k: v.detach().cpu() for k, v in net.state_dict().items()}
-        net_state = {k: v.detach().cpu() for k, v in net.state_dict().items()}
-        net_state.update({k: v.detach().cpu() for k, v in state.items() if k in net_state})
-        order = list(model.state_dict())            # the reference's key order (state_spec), as torch.save of the reference module writes it
-        full = {k: net_state[k] for k in order if k in net_state}
-        full.update({k: v for k, v in net_state.items() if k not in full})
-        torch.save({"model": full, "iteration": args.max_iters}, os.path.join(folder, WEIGHTS_NAME))
+        torch.save({"model": _ordered_state(order, net, stepper, args.ema_enabled), "iteration": done_iters}, os.path.join(folder, WEIGHTS_NAME))
         info = {k: getattr(model_info, k) for k in ("name", "model_family", "classes", "im_size", "task", "config", "description")}
         info.update(name=args.run_name.strip(), weights_uri=os.path.join(folder, WEIGHTS_NAME), status="TRAINING_COMPLETED",
                     train_args={k: v for k, v in asdict(args).items()}, final_losses=out)
+        if validator is not None:
+            best = validator.finish(os.path.join(folder, WEIGHTS_NAME))
+            info.update(val_metrics=best, val_history=validator.tracker.history)
         with open(os.path.join(folder, INFO_NAME), "w") as f:
             json.dump(info, f, indent=1, default=str)
     if world > 1:

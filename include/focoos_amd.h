@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 13
+#define FX_ABI_VERSION 14
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -697,6 +697,34 @@ typedef struct {
 } fx_pack_entry;
 int fx_pack_entry_blocks(int N, int C, int KH, int KW);   /* workgroups of one entry (tiles of 8 output channels x <= 2304 (channel, tap) elements); -1: unsupported filter size */
 int fx_pack_weights_many_f32(const fx_pack_entry* entries_dev, int n_entries, int total_blocks, fx_stream_t stream);
+
+/* Device-side weight publish (csrc/publish.hip): fp32 weights on the device -> the packed buffers of an inference engine, in
+ * place and in one launch over a device table.  Entry e reads the weight w [N][C][KH][KW] (a Linear: KH = KW = 1, C = K), optionally the
+ * four eval-BatchNorm vectors [N] (all or none) or a conv bias [N] (ignored when the BatchNorm vectors are given: no layer has both), and
+ * writes whichever destinations are not NULL:
+ *   w_rows   bf16 [Np][KH][KW][C] (fx_conv_desc.w), rows N .. Np-1 zero;
+ *   w_frag   the MFMA fragment-order copy [N/32][K/16][64][8], k = (kh*KW + kw)*C + c (fx_conv_desc.w_frag; N % 32 == 0, K % 16 == 0);
+ *   bias_out fp32 [Np], entries N .. Np-1 zero.
+ * The fold is s = g / sqrt(var + eps), w * s and beta - mu * s in fp64, each operation rounded on its own, the result rounded to fp32 and
+ * then to bf16 (nearest-even): bit-identical to the host packer of the engines.  Np is a multiple of 8, >= N.  Workgroups first_block ..
+ * first_block + fx_publish_entry_blocks(Np, C, KH, KW) - 1 belong to entry e (ascending, gap-free); total_blocks = their sum.  16-byte
+ * stores are taken when C % 8 == 0 and both image pointers are 16-byte aligned (element stores otherwise). */
+typedef struct {
+  const float* w;
+  const float* bn_weight;
+  const float* bn_bias;
+  const float* bn_mean;
+  const float* bn_var;
+  const float* bias;
+  void* w_rows;
+  void* w_frag;
+  float* bias_out;
+  double eps;
+  int32_t N, C, KH, KW;
+  int32_t Np, first_block;
+} fx_publish_entry;
+int fx_publish_entry_blocks(int Np, int C, int KH, int KW);   /* workgroups of one entry (tiles of 8 rows x <= 2304 (channel, tap) elements); -1: unsupported */
+int fx_publish_weights_f32(const fx_publish_entry* entries_dev, int n_entries, int total_blocks, fx_stream_t stream);
 
 /* dw_master[n][c][kh][kw] (+)= scale[n] * dw_eff[n][kh][kw][c]; dw_eff rows have C_eff >= C channels (stem: 3 of 8). */
 int fx_unpack_conv_wgrad_f32(const float* dw_eff, const float* scale, float* dw_master, int N, int C, int KH, int KW, int C_eff, int accumulate,
