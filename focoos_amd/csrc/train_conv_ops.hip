@@ -549,7 +549,11 @@ __global__ __launch_bounds__(256) void normalize_pad8_kernel(const void* __restr
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float raw = is_f32 ? reinterpret_cast<const float*>(img)[i * 3 + c] : (float)reinterpret_cast<const unsigned char*>(img)[i * 3 + c];
-      v[c] = (raw - mean[c]) * inv_std[c];
+      float p = (raw - mean[c]) * inv_std[c];
+      // every channel, in both libraries, is the fp32 product rounded once to the element type: left to the compiler, the fp16 build fuses
+      // the multiply of the channel packed beside a constant zero with the conversion (v_fma_mixlo_f16) and that channel alone rounds differently
+      asm volatile("" : "+v"(p));
+      v[c] = p;
     }
     *reinterpret_cast<uint4*>(out + i * 8) = pack_bf16x8(v);
   }

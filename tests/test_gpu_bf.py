@@ -47,8 +47,38 @@ def dev(t, dtype=None):
     return t.to(device=DEV, dtype=dtype or t.dtype).contiguous()
 
 
-@pytest.mark.parametrize("shape", [(2, 12, 16, 128), (1, 13, 15, 64), (3, 7, 9, 520)])
-def test_dwconv3x3s2_and_avgpool(lib, shape):
+_DW_SHAPES = [(2, 12, 16, 128), (1, 13, 15, 64), (3, 7, 9, 520)]
+_DW_MORE = [(1, 1, 1, 8), (2, 7, 9, 24)]     # a single pixel (every tap but the centre is padding); C below one 256-thread row of groups
+
+
+def _dwconv_f32out(lib, x, w, bias, xd, wd, bd):
+    """fx_dwconv3x3s2_nhwc_f32out (the fp32 conv output train-mode BatchNorm reads) vs fp64 F.conv2d(groups=C) on the same bf16 x and fp32
+    w / bias: nine fused multiply-adds onto the bias, so |got - ref| <= 10 * 2^-24 * (sum|x w| + |bias|) per output; ldy = C + 8 and a
+    guard row on either side keep their sentinel bits."""
+    B, H, W, Cc = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    full = torch.empty(B * Ho * Wo + 2, Cc + 8, dtype=torch.float32, device=DEV)
+    full.view(torch.int32).fill_(0x5A5A5A5A)
+    y = full[1:-1]
+    for b in (bd, None):
+        check(lib.fx_dwconv3x3s2_nhwc_f32out(xd.data_ptr(), Cc, wd.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), Cc + 8, B, H, W, Cc,
+                                             stream()))
+        torch.cuda.synchronize()
+        bias64 = bias.double() if b is not None else None
+        x64 = x.double().permute(0, 3, 1, 2)
+        ref = F.conv2d(x64, w.double(), bias64, stride=2, padding=1, groups=Cc).permute(0, 2, 3, 1)
+        mag = F.conv2d(x64.abs(), w.double().abs(), bias64.abs() if b is not None else None, stride=2, padding=1, groups=Cc).permute(0, 2, 3, 1)
+        got = y[:, :Cc].cpu().double().reshape(B, Ho, Wo, Cc)
+        assert bool(((got - ref).abs() <= 10 * 2.0 ** -24 * mag).all()), float(((got - ref).abs() / mag.clamp_min(1e-300)).max())
+        guard = full.view(torch.int32).cpu().clone()
+        guard[1:-1, :Cc] = 0x5A5A5A5A
+        assert bool((guard == 0x5A5A5A5A).all())
+
+
+@pytest.mark.parametrize("shape,entry", [pytest.param(s, "bf16", id=f"shape{i}") for i, s in enumerate(_DW_SHAPES)]
+                         + [pytest.param(s, "bf16", id=f"bf16-{'x'.join(map(str, s))}") for s in _DW_MORE]
+                         + [pytest.param(s, "f32out", id=f"f32out-{'x'.join(map(str, s))}") for s in _DW_SHAPES + _DW_MORE])
+def test_dwconv3x3s2_and_avgpool(lib, shape, entry):
     B, H, W, Cc = shape
     g = torch.Generator().manual_seed(Cc)
     x = torch.randn(B, H, W, Cc, generator=g).bfloat16()
@@ -56,6 +86,8 @@ def test_dwconv3x3s2_and_avgpool(lib, shape):
     bias = torch.randn(Cc, generator=g) * 0.2
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     xd, wd, bd = dev(x), dev(w[:, 0].permute(1, 2, 0).reshape(9, Cc).contiguous()), dev(bias)
+    if entry == "f32out":
+        return _dwconv_f32out(lib, x, w, bias, xd, wd, bd)
     y = torch.empty(B, Ho, Wo, Cc + 8, dtype=torch.bfloat16, device=DEV).fill_(7.0)   # strided output (channel slice of a wider buffer)
     check(lib.fx_dwconv3x3s2_nhwc_bf16(xd.data_ptr(), Cc, wd.data_ptr(), bd.data_ptr(), y.data_ptr(), Cc + 8, B, H, W, Cc, stream()))
     torch.cuda.synchronize()
