@@ -10,9 +10,11 @@ D2H of the packed (<=300x6 per image) results.  Workload at N=1: BASELINE config
 N>1: one process per GPU, independent replicas (inference shards by image, no data-path collective:
 SURVEY §8e) -> weak scaling; timing = barrier + synchronize, max over ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel:
-the implicit-GEMM conv template, live HIP-event timing on the engine's stream) and `cpu_baseline`
-(the CPU fp32 oracle = "port" of the reference path, timed on this host's cores on a bounded sample).
+Prints ONE JSON line on rank 0.  A plain run does what the headline figure needs and no more: set-up, warm-up, the timed steps,
+`--dump-outputs`, the line.  `--full` adds every measurement that takes work of its own: `cpu_baseline` (the CPU fp32 oracle = "port"
+of the reference path, timed on this host's cores on a bounded sample), `single_batch_in_flight`, `roofline` / `composite_roofline`
+(dominant kernel: the implicit-GEMM conv template, live HIP-event timing on the engine's stream; `--per-op` writes the table),
+`other_configs` (the other BASELINE configs, briefly) and, with `--train`, the weight-gradient `roofline` and `dp_check`.
 """
 from __future__ import annotations
 
@@ -57,20 +59,26 @@ def parse():
     ap.add_argument("--mf-masks-dtype", default="fp32", choices=["fp32", "bf16"], help="fai-mf-* with --mf-full-masks: element type of the [B,Q,H,W] masks tensor")
     ap.add_argument("--mf-masks-d2h", action="store_true", help="fai-mf-*: include the D2H copy of the bit-packed mask buffer in the step")
     ap.add_argument("--model", default="fai-detr-l-obj365")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything that takes work of its own: CPU baseline, one batch in flight, per-kernel "
+                         "and composite roofline (--per-op), the other BASELINE configs; --train: weight-gradient roofline, dp_check.  Off by "
+                         "default: a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--cpu-iters", type=int, default=5)
     ap.add_argument("--cpu-threads", type=int, default=64, help="upper bound of the CPU baseline's thread sweep (8 / 16 / 32 / 64)")
     ap.add_argument("--dry-run", action="store_true", help="CPU-only plumbing check (gloo): no GPU work, fake step")
-    ap.add_argument("--per-op", default="", help="write per-op timing table to this path")
+    ap.add_argument("--per-op", default="", help="--full: write per-op timing table to this path")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all; "
                          "bench_out/ is git-ignored)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run only: skip the short extra legs (RT-DETR / BiSeNetFormer training step, MaskFormer / BiSeNetFormer inference) "
+                    help="--full default run only: skip the short extra legs (RT-DETR / BiSeNetFormer training step, MaskFormer / BiSeNetFormer inference) "
                          "reported under `other_configs` of the one JSON line")
     ap.add_argument("--other-configs-budget", type=float, default=240.0, help="seconds after which the extra legs are abandoned (watchdog)")
     a = ap.parse_args()
+    if a.per_op and not a.full:
+        ap.error("--per-op writes the table of the per-kernel timing pass, which runs under --full")
     a.default_run = len([x for x in sys.argv[1:] if x.startswith("--model") or x in ("--train", "--dry-run")]) == 0
     mf = a.model.startswith("fai-mf")
     a.family = "fai_mf" if mf else ("bisenetformer" if a.model.startswith("bisenetformer") else "fai_detr")
@@ -476,9 +484,9 @@ def train_measure(args, world, rank, local, with_roofline=True):
            (ALG_GFLOP_PER_IMAGE_MF_800 * (S / 800.0) ** 2 if args.family == "fai_mf" else ALG_GFLOP_PER_IMAGE * (S / 640.0) ** 2))
     alg = 3 * fwd  # training ~ 3 x forward (fwd + dgrad + wgrad)
     # data-parallel consistency: after the timed steps every rank must hold bit-identical fp32 master weights (same all-reduced
-    # gradients, same optimizer arithmetic).  Checked with one MIN and one MAX all-reduce of a float64 checksum.
+    # gradients, same optimizer arithmetic).  Checked under --full with one MIN and one MAX all-reduce of a float64 checksum.
     dp_check = None
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
 
         chk = stepper.opt.flat_p.double().sum().reshape(1)
@@ -489,7 +497,7 @@ def train_measure(args, world, rank, local, with_roofline=True):
                     "checksum": float(chk.item())}
     class stepper_graphs:   # noqa: N801  (tiny record read by the JSON line below)
         on = stepper._graph_state is not None
-    roof = _wgrad_roofline(train_nn, stepper, imgs, all_targets[0], args.family) if (rank == 0 and with_roofline) else None
+    roof = _wgrad_roofline(train_nn, stepper, imgs, all_targets[0], args.family) if (rank == 0 and with_roofline and args.full) else None
     barrier(world, False)
     out = None
     if rank == 0:
@@ -581,7 +589,7 @@ def run(args):
     if args.train:
         return train_main(args, world, rank, local)
     out = infer_measure(args, world, rank, local, light=False)
-    if args.default_run and not args.no_other_configs:
+    if args.full and args.default_run and not args.no_other_configs:
         other_configs(args, world, rank, local, out)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -647,8 +655,8 @@ def other_configs(args, world, rank, local, out):
 
 
 def infer_measure(args, world, rank, local, light=False):
-    """One inference measurement (the bench contract's timed region); returns rank 0's dict.  ``light``: no CPU baseline, no per-kernel
-    roofline table (the extra legs of the default run)."""
+    """One inference measurement (the bench contract's timed region); returns rank 0's dict.  The CPU baseline, the one-batch-in-flight
+    steps and the per-kernel roofline table run under --full only, and never with ``light`` (the extra legs of the --full default run)."""
     import torch
 
     from focoos_amd.model import BisenetFormer, FAIDetr, FAIMaskFormer
@@ -659,7 +667,8 @@ def infer_measure(args, world, rank, local, light=False):
     cfg = ModelRegistry.get_model_info(args.model)["config"]
     B = args.batch
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not light:
+    extras = args.full and not light
+    if rank == 0 and world == 1 and extras and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
     bf = args.family == "bisenetformer"
     mf = args.family == "fai_mf" or bf     # the two mask families share the engine interface (engine_maskdec.py)
@@ -676,7 +685,7 @@ def infer_measure(args, world, rank, local, light=False):
     # THROUGHPUT mode by default, all three families (engine.pipeline(): `depth` batches in flight, each a whole-batch plan on its own stream - batch
     # i+1's backbone beside batch i's decoder tail).  A step is still ONE batch through the whole path (D2D hand-over, graph replay, D2H of
     # the packed detections); the timed region is K such steps between two full synchronisations.  --pipeline 1 = one batch at a time
-    # (engine.forward()'s form: two half-batch parts side by side), also measured below and reported as `single_batch_in_flight`.
+    # (engine.forward()'s form: two half-batch parts side by side), also measured below under --full and reported as `single_batch_in_flight`.
     depth = args.pipeline if args.pipeline is not None else int(os.environ.get("FX_PIPELINE_DEPTH", "3"))
     pipe = None
     if depth > 1:
@@ -726,7 +735,7 @@ def infer_measure(args, world, rank, local, light=False):
     value = world * B * args.steps / dt
 
     single = None
-    if pipe is not None and depth > 1 and not light:
+    if pipe is not None and depth > 1 and extras:
         # the same K steps with ONE batch in flight (engine.forward()'s structure: two half-batch parts side by side, next batch after the join)
         pl1 = eng.plan(B, args.size, args.size, False, args.mf_full_masks, None) if mf else eng.plan(B, args.size, args.size, False, None)
         host1 = {k: torch.empty_like(getattr(pl1, k), device="cpu").pin_memory() for k in keys}
@@ -772,7 +781,7 @@ def infer_measure(args, world, rank, local, light=False):
     }
     if single is not None:
         out["single_batch_in_flight"] = single
-    if rank == 0 and not light:
+    if rank == 0 and extras:
         # ---- roofline of the dominant kernel (live, in-sequence HIP-event timing; world==1 or rank 0 only)
         ms = per_op_timing(eng, pl, args)
         by = {}

@@ -6,9 +6,9 @@
 #   tests:<pytest args>          python -m pytest <args> -q            (e.g. tests:'tests/test_gpu_kernels.py -k topk')
 #   suite                        the whole -m gpu directory, no -x
 #   probe:<bin>[:args]           scripts/probes/bin/<bin> args          (stand-alone HIP probes)
-#   bench[:ENV=V,ENV=V]          headline line (no CPU baseline / other configs), twice, with the per-op table of the first run
+#   bench[:ENV=V,ENV=V]          headline line with its roofline (--full, no CPU baseline / other configs), twice, with the per-op table of the first run
 #   ab:<cfg>|<cfg>|...           headline A/B, each cfg = "-" or comma-separated ENV=V; two interleaved repetitions
-#   benchfull                    the default `python bench.py` line exactly as the driver runs it
+#   benchfull                    the `python bench.py --full` line: headline + CPU baseline, roofline, other configs
 #   train[:<bench.py args>]      python bench.py --train <args>
 #   model:<name>[:args]          python bench.py --model <name> <args>
 #   prof[:ENV=V,...]             rocprofv3 --kernel-trace --stats of the headline (as timed) and with FX_PARTS_SERIAL=1 -> kernel_stats csv
@@ -41,7 +41,7 @@ for step in "$@"; do
       timeout 600 scripts/probes/bin/$bin $pa > $out/probe_$bin.txt 2>&1; echo "[probe $bin] rc=$?";;
     bench)
       for r in 1 2; do
-        env $(envs "$arg") timeout 400 python bench.py --no-cpu-baseline --no-other-configs $([ $r = 1 ] && echo --per-op $out/per_op.txt) > $out/bench_$r.json 2> $out/bench_$r.err
+        env $(envs "$arg") timeout 400 python bench.py --full --no-cpu-baseline --no-other-configs $([ $r = 1 ] && echo --per-op $out/per_op.txt) > $out/bench_$r.json 2> $out/bench_$r.err
         echo "[bench $arg run $r] $(line $out/bench_$r.json)"
       done;;
     ab)
@@ -49,17 +49,17 @@ for step in "$@"; do
       for rep in 1 2; do for cfg in "${cfgs[@]}"; do
         e=""; [ "$cfg" != "-" ] && e=$(envs "$cfg")
         f=$out/ab_$(echo "$cfg" | tr -c 'A-Za-z0-9_=\n' '_')_$rep.json
-        env $e timeout 400 python bench.py --no-cpu-baseline --no-other-configs --steps 30 --warmup 8 > $f 2>/dev/null
+        env $e timeout 400 python bench.py --full --no-cpu-baseline --no-other-configs --steps 30 --warmup 8 > $f 2>/dev/null
         echo "[ab rep$rep $cfg] $(line $f)"
       done; done;;
     benchfull)
-      timeout 1500 python bench.py > $out/bench_full.json 2> $out/bench_full.err; echo "[benchfull] rc=$? $(line $out/bench_full.json)";;
+      timeout 1500 python bench.py --full > $out/bench_full.json 2> $out/bench_full.err; echo "[benchfull] rc=$? $(line $out/bench_full.json)";;
     train)
       n=$(ls $out | grep -c '^train_'); f=$out/train_$n.json
-      timeout 900 python bench.py --train $arg > $f 2> $f.err; echo "[train $arg] rc=$? $(line $f)";;
+      timeout 900 python bench.py --train --full $arg > $f 2> $f.err; echo "[train $arg] rc=$? $(line $f)";;
     model)
       name=${arg%%:*}; ma=""; [ "$name" != "$arg" ] && ma=${arg#*:}
-      timeout 900 python bench.py --model $name $ma --no-cpu-baseline --no-other-configs > $out/model_$name.json 2> $out/model_$name.err; echo "[model $name $ma] rc=$? $(line $out/model_$name.json)";;
+      timeout 900 python bench.py --model $name $ma --full --no-cpu-baseline --no-other-configs > $out/model_$name.json 2> $out/model_$name.err; echo "[model $name $ma] rc=$? $(line $out/model_$name.json)";;
     prof)
       for mode in timed serial; do
         e=$(envs "$arg"); [ $mode = serial ] && e="$e FX_PARTS_SERIAL=1"

@@ -6,21 +6,21 @@ TAG=${TAG:-r06z}
 out=$PWD/gpurun_out/$TAG; mkdir -p $out
 ROOT=$PWD
 export TMPDIR=/tmp
-( time timeout 700 python bench.py --per-op $out/${TAG}_per_op_hipevent.txt > $out/${TAG}_bench.json 2> $out/${TAG}_bench.err ); echo "bench rc=$?"
-timeout 300 python bench.py --train --steps 12 --warmup 4 > $out/${TAG}_train_bench.json 2> $out/${TAG}_train_bench.err; echo "detr train rc=$?"
-timeout 300 python bench.py --train --norm BN --steps 12 --warmup 4 > $out/${TAG}_train_bn_bench.json 2> $out/${TAG}_train_bn_bench.err; echo "detr train BN rc=$?"
-timeout 400 python bench.py --train --model bisenetformer-l-ade --norm FrozenBN --steps 10 --warmup 3 > $out/${TAG}_bf_train_bench.json 2> $out/${TAG}_bf_train_bench.err; echo "bf train (fp16, FrozenBN) rc=$?"
-timeout 400 python bench.py --train --model bisenetformer-l-ade --norm BN --steps 10 --warmup 3 > $out/${TAG}_bf_train_bn_bench.json 2> $out/${TAG}_bf_train_bn_bench.err; echo "bf train (fp16, BN) rc=$?"
-timeout 400 python bench.py --train --model bisenetformer-l-ade --norm BN --dtype bf16 --steps 10 --warmup 3 > $out/${TAG}_bf_train_bn_bf16_bench.json 2> $out/${TAG}_bf_train_bn_bf16_bench.err; echo "bf train (bf16, BN) rc=$?"
-timeout 400 python bench.py --train --model fai-mf-l-coco-ins --steps 8 --warmup 3 > $out/${TAG}_mf_train_bench.json 2> $out/${TAG}_mf_train_bench.err; echo "mf train rc=$?"
-FX_TRAIN_GRAPH=1 timeout 300 python bench.py --train --steps 12 --warmup 4 > $out/${TAG}_train_graph_bench.json 2> $out/${TAG}_train_graph_bench.err; echo "detr train (graphs) rc=$?"
-timeout 300 python bench.py --no-cpu-baseline --no-other-configs --pipeline 1 > $out/${TAG}_bench_single_batch.json 2> $out/${TAG}_bench_single_batch.err; echo "headline, one batch in flight rc=$?"
+( time timeout 700 python bench.py --full --per-op $out/${TAG}_per_op_hipevent.txt > $out/${TAG}_bench.json 2> $out/${TAG}_bench.err ); echo "bench rc=$?"
+timeout 300 python bench.py --full --train --steps 12 --warmup 4 > $out/${TAG}_train_bench.json 2> $out/${TAG}_train_bench.err; echo "detr train rc=$?"
+timeout 300 python bench.py --full --train --norm BN --steps 12 --warmup 4 > $out/${TAG}_train_bn_bench.json 2> $out/${TAG}_train_bn_bench.err; echo "detr train BN rc=$?"
+timeout 400 python bench.py --full --train --model bisenetformer-l-ade --norm FrozenBN --steps 10 --warmup 3 > $out/${TAG}_bf_train_bench.json 2> $out/${TAG}_bf_train_bench.err; echo "bf train (fp16, FrozenBN) rc=$?"
+timeout 400 python bench.py --full --train --model bisenetformer-l-ade --norm BN --steps 10 --warmup 3 > $out/${TAG}_bf_train_bn_bench.json 2> $out/${TAG}_bf_train_bn_bench.err; echo "bf train (fp16, BN) rc=$?"
+timeout 400 python bench.py --full --train --model bisenetformer-l-ade --norm BN --dtype bf16 --steps 10 --warmup 3 > $out/${TAG}_bf_train_bn_bf16_bench.json 2> $out/${TAG}_bf_train_bn_bf16_bench.err; echo "bf train (bf16, BN) rc=$?"
+timeout 400 python bench.py --full --train --model fai-mf-l-coco-ins --steps 8 --warmup 3 > $out/${TAG}_mf_train_bench.json 2> $out/${TAG}_mf_train_bench.err; echo "mf train rc=$?"
+FX_TRAIN_GRAPH=1 timeout 300 python bench.py --full --train --steps 12 --warmup 4 > $out/${TAG}_train_graph_bench.json 2> $out/${TAG}_train_graph_bench.err; echo "detr train (graphs) rc=$?"
+timeout 300 python bench.py --full --no-cpu-baseline --no-other-configs --pipeline 1 > $out/${TAG}_bench_single_batch.json 2> $out/${TAG}_bench_single_batch.err; echo "headline, one batch in flight rc=$?"
 timeout 600 python -m pytest tests/test_gpu_baseline_configs.py -q -s > $out/${TAG}_baseline_config_parity.txt 2>&1; echo "baseline-config parity rc=$?"
 timeout 900 python -m pytest tests/test_gpu_train_baseline_configs.py -q -s > $out/${TAG}_train_baseline_config_parity.txt 2>&1; echo "training baseline-config parity rc=$?"
 timeout 600 python -m pytest tests/test_gpu_fp16.py -q -s > $out/${TAG}_fp16_tests.txt 2>&1; echo "fp16 tests rc=$?"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/${TAG}_smoke.txt 2>&1; echo "smoke rc=$?"
-timeout 300 python bench.py --model fai-mf-l-coco-ins --no-cpu-baseline --per-op $out/${TAG}_mf_per_op_hipevent.txt > $out/${TAG}_mf_bench.json 2> $out/${TAG}_mf_bench.err
-timeout 300 python bench.py --model bisenetformer-l-ade --no-cpu-baseline --per-op $out/${TAG}_bf_per_op_hipevent.txt > $out/${TAG}_bf_bench.json 2> $out/${TAG}_bf_bench.err
+timeout 300 python bench.py --full --model fai-mf-l-coco-ins --no-cpu-baseline --per-op $out/${TAG}_mf_per_op_hipevent.txt > $out/${TAG}_mf_bench.json 2> $out/${TAG}_mf_bench.err
+timeout 300 python bench.py --full --model bisenetformer-l-ade --no-cpu-baseline --per-op $out/${TAG}_bf_per_op_hipevent.txt > $out/${TAG}_bf_bench.json 2> $out/${TAG}_bf_bench.err
 # kernel stats twice: as timed (three batches in flight: durations under concurrency) and SERIAL (one whole-batch plan on one stream:
 # the durations the per-op table / `roofline.achieved` are measured at)
 cd /tmp

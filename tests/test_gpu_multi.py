@@ -1,5 +1,5 @@
 """Two-GPU checks (skipped on a one-GPU box; the driver's 8-GPU node runs them): the data-parallel training step over RCCL -
-`bench.py --train --gpus 2` spawns one process per GPU through focoos_amd.launch (the mirror of the reference's launch(),
+`bench.py --train --gpus 2 --full` (`--full`: the line carries `dp_check`) spawns one process per GPU through focoos_amd.launch (the mirror of the reference's launch(),
 focoos/utils/distributed/dist.py:38-95), every rank steps TrainStep on its shard, gradients are all-reduced over the nccl (= RCCL) backend.
 Asserted: the line reports two GPUs, the backend is nccl, and after the steps every rank holds bit-identical master weights."""
 import json
@@ -23,7 +23,7 @@ def _need_two():
 def test_bench_train_two_gpus_rccl(extra):
     _need_two()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--train", "--gpus", "2", "--steps", "5", "--warmup", "1", "--no-cpu-baseline"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--train", "--gpus", "2", "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline"] + extra
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

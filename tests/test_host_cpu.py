@@ -204,6 +204,24 @@ def test_bench_spawns_its_own_ranks():
     assert bad.returncode != 0 and "WORLD_SIZE=2 but --gpus 1" in (bad.stderr + bad.stdout)
 
 
+def test_bench_full_option(monkeypatch, capsys):
+    """`--full` is off by default (a plain run measures the headline and nothing else), and `--per-op`, the table of the per-kernel timing
+    pass that only `--full` runs, is refused without it instead of being silently ignored."""
+    import bench
+
+    base = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"]
+    monkeypatch.setattr(sys, "argv", base)
+    a = bench.parse()
+    assert a.full is False and a.default_run and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", base + ["--full", "--per-op", "t.txt"])
+    a = bench.parse()
+    assert a.full is True and a.default_run and a.per_op == "t.txt"
+    monkeypatch.setattr(sys, "argv", base + ["--per-op", "t.txt"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    assert "--full" in capsys.readouterr().err
+
+
 def _launch_probe(path):
     import torch.distributed as dist
 
