@@ -182,6 +182,11 @@ SIGNATURES = {
     "fx_mask_set_loss_workspace_bytes": [_i, _i, _i, _i],
     "fx_mask_set_loss_f32": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.c_float, C.c_float,
                              C.c_float, C.c_float, C.c_float, _vp, C.c_size_t, _vp, _vp],
+    "fx_mask_set_loss_cls_f32": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.c_float, _i, C.c_float,
+                                 C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, C.c_size_t, _vp, _vp],
+    "fx_mask_class_loss_workspace_bytes": [_i, _i],
+    "fx_mask_class_loss_f32": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, _vp, C.c_size_t, _vp, _vp],
+    "fx_mask_class_loss_bwd_f32": [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp, _i, _vp],
     "fx_dwconv3x3s2_nhwc_bf16": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "fx_dwconv3x3s2_nhwc_f32out": [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "fx_global_mean_nhwc_bf16": [_vp, _i, _vp, _i, _i, _i, _i, _vp],
@@ -218,6 +223,8 @@ SIGNATURES = {
     "fx_mha_masked_bwd_bf16": [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, C.c_size_t, _vp],
     "fx_mask_set_loss_bwd_f32": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.c_float, C.c_float,
                                  C.c_float, C.c_float, C.c_float, _vp, C.c_size_t, _vp, _vp, _i, _vp, _vp],
+    "fx_mask_set_loss_cls_bwd_f32": [_vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.c_float, _i, C.c_float,
+                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _vp, C.c_size_t, _vp, _vp, _i, _vp, _vp],
     "fx_planes_to_rows_bf16": [_vp, _i, _i, _vp, _i, _i, _i, _vp],
     "fx_dwconv3x3s2_bwd_nhwc_bf16": [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp],
     "fx_rowdot_nhwc_bf16": [_vp, _i, _vp, _i, C.c_float, _vp, _i, _i, _i, _i, _i, _vp],
@@ -290,7 +297,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 14  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 15  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:
@@ -316,6 +323,7 @@ def load(name: str = None) -> C.CDLL:
     lib.fx_mask_match_cost_workspace_bytes.restype = C.c_size_t
     lib.fx_mf_postprocess_workspace_bytes_fused.restype = C.c_size_t
     lib.fx_mask_set_loss_workspace_bytes.restype = C.c_size_t
+    lib.fx_mask_class_loss_workspace_bytes.restype = C.c_size_t
     lib.fx_topk_rows_workspace_bytes.restype = C.c_size_t
     lib.fx_coco_match_workspace_bytes.restype = C.c_size_t
     lib.fx_mf_eval_masks_workspace_bytes.restype = C.c_size_t

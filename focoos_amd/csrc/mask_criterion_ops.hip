@@ -324,6 +324,140 @@ __global__ __launch_bounds__(256) void mask_label_ce_kernel(const float* __restr
   }
 }
 
+// (1b) labels, the other values of SetCriterion.loss_class_type (loss.py:430-457), same shape as the pair above: one wave per (b, q) row,
+//     a float64 partial per row, no atomics.  mode (FX_CLASS_LOSS_*):
+//       FOCAL      focal_loss (:215-255) over the K+1 columns: ce = softmax cross-entropy of the row, p_t = exp(-ce),
+//                  alpha * ce * (1 - p_t)^gamma (alpha < 0: no alpha; a target equal to the reference's ignore_index 255 gives 0),
+//                  mean over the B*Q rows.
+//       BCE        binary_cross_entropy_with_logits over the FIRST K columns against the one-hot target without its no-object column
+//                  (a no-object row is all zeros), sum over (b, q, k) / num_masks.  A (K+1)-th column (cls_sigmoid heads) is not read.
+//       BCE_FOCAL  sigmoid_focal_loss(x, onehot, alpha, gamma) over the same K columns with the same reduction.
+//     Stable forms: with z = x (target 1) or -x (target 0), bce = softplus(-z) and 1 - p_t = sigmoid(-z) are computed directly (never as
+//     1 - sigmoid); the softmax ce is (max - x_y) + log(sum exp(x - max)), two non-negative terms, and 1 - p_t = -expm1(-ce).
+//     partial[row] = {row sum, the loss's divisor in row 0 and 0 elsewhere}: mask_loss_final_kernel's sum / sum then is sum / divisor.
+__device__ __forceinline__ int mask_row_target(const int32_t* __restrict__ tgt_labels, const int32_t* __restrict__ tgt_offsets,
+                                               const int32_t* __restrict__ pred_idx, const int32_t* __restrict__ tgt_idx, int b, int q, int K, int lane) {
+  const int t0 = tgt_offsets[b], T = tgt_offsets[b + 1] - t0;
+  int y = K;
+  for (int i = lane; i < T; i += 64)
+    if (pred_idx[t0 + i] == q) y = tgt_labels[t0 + tgt_idx[t0 + i]];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) y = min(y, __shfl_xor(y, o, 64));   // at most one lane found a match; K is the maximum
+  return y;
+}
+
+// one element of the two sigmoid losses and d loss / d x
+__device__ __forceinline__ void sigmoid_class_elem(float x, bool pos, int mode, float alpha, float gamma, float& loss, float& dx) {
+  const float z = pos ? x : -x;
+  const float l1p = log1pf(expf(-fabsf(z)));
+  const float bce = fmaxf(-z, 0.0f) + l1p;          // softplus(-z)
+  const float s = 1.0f / (1.0f + expf(z));          // sigmoid(-z) = 1 - p_t
+  float l = bce, dz = -s;
+  if (mode == FX_CLASS_LOSS_BCE_FOCAL) {
+    const float a_t = alpha >= 0.0f ? (pos ? alpha : 1.0f - alpha) : 1.0f;
+    const float pt = 1.0f / (1.0f + expf(-z));
+    const float m = a_t * powf(s, gamma);
+    l = m * bce;
+    dz = -m * (s + gamma * pt * bce);                // d/dz [bce * s^gamma]: bce' = -s, s' = -s p_t
+  }
+  loss = l;
+  dx = pos ? dz : -dz;
+}
+
+// softmax focal loss of one row and d loss / d ce; every lane returns the same values.  u = 1 - p_t.
+__device__ __forceinline__ void focal_class_row(const float* __restrict__ lp, int K, int y, float alpha, float gamma, int lane, float& mx, float& se,
+                                                float& u, float& loss, float& dce) {
+  mx = -INFINITY;
+  for (int c = lane; c <= K; c += 64) mx = fmaxf(mx, lp[c]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  se = 0.0f;
+  for (int c = lane; c <= K; c += 64) se += expf(lp[c] - mx);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+  u = loss = dce = 0.0f;
+  if (y == 255) return;                              // F.cross_entropy(ignore_index=255) of focal_loss
+  const float ce = (mx - lp[y]) + logf(se);
+  const float pt = expf(-ce), a = alpha >= 0.0f ? alpha : 1.0f;
+  u = -expm1f(-ce);
+  const float ug = powf(u, gamma);
+  loss = a * ce * ug;
+  dce = a * (ug + (u > 0.0f ? gamma * ce * powf(u, gamma - 1.0f) * pt : 0.0f));
+}
+
+__global__ __launch_bounds__(256) void mask_label_cls_kernel(const float* __restrict__ logits, int ldl, const int32_t* __restrict__ tgt_labels,
+                                                             const int32_t* __restrict__ tgt_offsets, const int32_t* __restrict__ pred_idx,
+                                                             const int32_t* __restrict__ tgt_idx, int n_rows, int Q, int K, int mode, float alpha,
+                                                             float gamma, double divisor, double* __restrict__ partial /*[B*Q][2]*/) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n_rows) return;
+  const int b = row / Q, q = row - b * Q;
+  const int y = mask_row_target(tgt_labels, tgt_offsets, pred_idx, tgt_idx, b, q, K, lane);
+  const float* lp = logits + (int64_t)row * ldl;
+  double sum;
+  if (mode == FX_CLASS_LOSS_FOCAL) {
+    float mx, se, u, l, d;
+    focal_class_row(lp, K, y, alpha, gamma, lane, mx, se, u, l, d);
+    sum = (double)l;
+  } else {
+    float acc = 0.0f;
+    for (int c = lane; c < K; c += 64) {
+      float l, d;
+      sigmoid_class_elem(lp[c], c == y, mode, alpha, gamma, l, d);
+      acc += l;
+    }
+    sum = (double)acc;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  }
+  if (lane == 0) {
+    partial[(int64_t)row * 2 + 0] = sum;
+    partial[(int64_t)row * 2 + 1] = row == 0 ? divisor : 0.0;
+  }
+}
+
+// dlogits[b,q,c] = g0 * w_ce / divisor * d loss / d x for the columns of the loss, 0 for every other column of the [B,Q,lddl] slab
+__global__ __launch_bounds__(256) void mask_label_cls_bwd_kernel(const float* __restrict__ logits, int ldl, const int32_t* __restrict__ tgt_labels,
+                                                                 const int32_t* __restrict__ tgt_offsets, const int32_t* __restrict__ pred_idx,
+                                                                 const int32_t* __restrict__ tgt_idx, int n_rows, int Q, int K, int mode, float alpha,
+                                                                 float gamma, float inv_divisor, const float* __restrict__ g, float w_ce,
+                                                                 float* __restrict__ dlogits, int lddl) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n_rows) return;
+  const int b = row / Q, q = row - b * Q;
+  const int y = mask_row_target(tgt_labels, tgt_offsets, pred_idx, tgt_idx, b, q, K, lane);
+  const float* lp = logits + (int64_t)row * ldl;
+  float* dp = dlogits + (int64_t)row * lddl;
+  const float coef = g[0] * w_ce * inv_divisor;
+  int cols;
+  if (mode == FX_CLASS_LOSS_FOCAL) {
+    float mx, se, u, l, d;
+    focal_class_row(lp, K, y, alpha, gamma, lane, mx, se, u, l, d);
+    cols = K + 1;
+    for (int c = lane; c < cols; c += 64) dp[c] = coef * d * (c == y ? -u : expf(lp[c] - mx) / se);   // softmax_y - 1 = -(1 - p_t)
+  } else {
+    cols = K;
+    for (int c = lane; c < cols; c += 64) {
+      float l, d;
+      sigmoid_class_elem(lp[c], c == y, mode, alpha, gamma, l, d);
+      dp[c] = coef * d;
+    }
+  }
+  for (int c = cols + lane; c < lddl; c += 64) dp[c] = 0.0f;
+}
+
+// columns of the logits a mode reads; -1: unknown mode
+static int mask_class_loss_cols(int mode, int K) {
+  if (mode == FX_CLASS_LOSS_CE || mode == FX_CLASS_LOSS_FOCAL) return K + 1;
+  if (mode == FX_CLASS_LOSS_BCE || mode == FX_CLASS_LOSS_BCE_FOCAL) return K;
+  return -1;
+}
+static double mask_class_loss_divisor(int mode, int n_rows, float num_masks) {
+  return mode == FX_CLASS_LOSS_FOCAL ? (double)n_rows : (double)num_masks;
+}
+
 // (2) masks: one workgroup per matched (prediction, target) pair.  Importance sampling: of the n_over uniformly drawn points keep
 // the k = num_points - n_extra with the smallest |logit| (torch.topk of -|logit|; ties -> lowest index), found by a 4-pass
 // radix select on the bit pattern of |x| with the samples recomputed per pass (4 taps each) instead of stored; then the
@@ -586,20 +720,28 @@ extern "C" size_t fx_mask_set_loss_workspace_bytes(int B, int Q, int sum_T, int 
   return ((size_t)B * Q * 2 + (size_t)sum_T * 4 + 1) * sizeof(double) + (size_t)sum_T * n_over * 5 + 16;
 }
 
-extern "C" int fx_mask_set_loss_f32(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H,
-                                    int W, const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx,
-                                    const int32_t* tgt_idx, const float* rand_over, int n_over, const float* rand_extra, int n_extra, int num_points,
-                                    int B, int Q, int K, float eos_coef, float num_masks, float w_ce, float w_mask, float w_dice, void* workspace,
-                                    size_t workspace_bytes, float* out3, fx_stream_t stream_) {
-  FX_CHECK_ARG(logits && pred_masks && tgt_offsets && workspace && out3 && B > 0 && Q > 0 && K > 0 && ldl >= K + 1 && h > 0 && w > 0 && H > 0 && W > 0);
+// cls_mode FX_CLASS_LOSS_CE is fx_mask_set_loss_f32 itself; the other modes swap the class-loss kernel and nothing else.
+static int mask_set_loss_impl(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H,
+                              int W, const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx,
+                              const int32_t* tgt_idx, const float* rand_over, int n_over, const float* rand_extra, int n_extra, int num_points,
+                              int B, int Q, int K, float eos_coef, int cls_mode, float focal_alpha, float focal_gamma, float num_masks, float w_ce,
+                              float w_mask, float w_dice, void* workspace, size_t workspace_bytes, float* out3, fx_stream_t stream_) {
+  FX_CHECK_ARG(K > 0 && mask_class_loss_cols(cls_mode, K) > 0);
+  FX_CHECK_ARG(logits && pred_masks && tgt_offsets && workspace && out3 && B > 0 && Q > 0 && ldl >= mask_class_loss_cols(cls_mode, K) && h > 0 && w > 0 &&
+               H > 0 && W > 0);
+  FX_CHECK_ARG(cls_mode == FX_CLASS_LOSS_CE || (tgt_labels && pred_idx && tgt_idx));
   FX_CHECK_ARG(sum_T >= 0 && num_points > 0 && n_extra >= 0 && n_extra <= num_points && n_over >= num_points - n_extra && num_masks > 0.0f);
   FX_CHECK_ARG(sum_T == 0 || (tgt_masks && tgt_labels && pred_idx && tgt_idx && (n_extra == 0 || rand_extra) && (num_points == n_extra || rand_over)));
   FX_CHECK_ARG(workspace_bytes >= fx_mask_set_loss_workspace_bytes(B, Q, sum_T, n_over) && ((uintptr_t)workspace % 8) == 0);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   double* ce_partial = reinterpret_cast<double*>(workspace);
   double* rows = ce_partial + (size_t)B * Q * 2;
-  hipLaunchKernelGGL(mask_label_ce_kernel, dim3((B * Q + 3) / 4), dim3(256), 0, stream, logits, ldl, tgt_labels, tgt_offsets, pred_idx, tgt_idx, B * Q, Q, K, eos_coef,
-                     ce_partial);
+  if (cls_mode == FX_CLASS_LOSS_CE)
+    hipLaunchKernelGGL(mask_label_ce_kernel, dim3((B * Q + 3) / 4), dim3(256), 0, stream, logits, ldl, tgt_labels, tgt_offsets, pred_idx, tgt_idx, B * Q, Q, K,
+                       eos_coef, ce_partial);
+  else
+    hipLaunchKernelGGL(mask_label_cls_kernel, dim3((B * Q + 3) / 4), dim3(256), 0, stream, logits, ldl, tgt_labels, tgt_offsets, pred_idx, tgt_idx, B * Q, Q, K,
+                       cls_mode, focal_alpha, focal_gamma, mask_class_loss_divisor(cls_mode, B * Q, num_masks), ce_partial);
   float* xs = reinterpret_cast<float*>(rows + (size_t)sum_T * 4 + 1);
   uint8_t* sel = reinterpret_cast<uint8_t*>(xs + (size_t)sum_T * n_over);
   if (sum_T > 0) {
@@ -613,6 +755,26 @@ extern "C" int fx_mask_set_loss_f32(const float* logits, int ldl, const float* p
   hipLaunchKernelGGL(mask_loss_final_kernel, dim3(1), dim3(256), 0, stream, ce_partial, B * Q, rows, sum_T, num_points, num_masks, w_ce, w_mask, w_dice,
                      out3, rows + (size_t)sum_T * 4);
   return fx_launch_status();
+}
+
+extern "C" int fx_mask_set_loss_f32(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H,
+                                    int W, const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx,
+                                    const int32_t* tgt_idx, const float* rand_over, int n_over, const float* rand_extra, int n_extra, int num_points,
+                                    int B, int Q, int K, float eos_coef, float num_masks, float w_ce, float w_mask, float w_dice, void* workspace,
+                                    size_t workspace_bytes, float* out3, fx_stream_t stream_) {
+  return mask_set_loss_impl(logits, ldl, pred_masks, h, w, tgt_masks, tgt_is_u8, H, W, tgt_labels, tgt_offsets, sum_T, pred_idx, tgt_idx, rand_over, n_over,
+                            rand_extra, n_extra, num_points, B, Q, K, eos_coef, FX_CLASS_LOSS_CE, 0.0f, 0.0f, num_masks, w_ce, w_mask, w_dice, workspace,
+                            workspace_bytes, out3, stream_);
+}
+
+extern "C" int fx_mask_set_loss_cls_f32(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H,
+                                        int W, const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx,
+                                        const int32_t* tgt_idx, const float* rand_over, int n_over, const float* rand_extra, int n_extra, int num_points,
+                                        int B, int Q, int K, float eos_coef, int cls_mode, float focal_alpha, float focal_gamma, float num_masks,
+                                        float w_ce, float w_mask, float w_dice, void* workspace, size_t workspace_bytes, float* out3, fx_stream_t stream_) {
+  return mask_set_loss_impl(logits, ldl, pred_masks, h, w, tgt_masks, tgt_is_u8, H, W, tgt_labels, tgt_offsets, sum_T, pred_idx, tgt_idx, rand_over, n_over,
+                            rand_extra, n_extra, num_points, B, Q, K, eos_coef, cls_mode, focal_alpha, focal_gamma, num_masks, w_ce, w_mask, w_dice,
+                            workspace, workspace_bytes, out3, stream_);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -648,22 +810,28 @@ __global__ __launch_bounds__(256) void mask_label_ce_bwd_kernel(const float* __r
   for (int c = lane; c <= K; c += 64) dp[c] = coef * (expf(lp[c] - mx) / se - (c == y ? 1.0f : 0.0f));
 }
 
-extern "C" int fx_mask_set_loss_bwd_f32(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H,
-                                        int W, const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx,
-                                        const int32_t* tgt_idx, const float* rand_over, int n_over, const float* rand_extra, int n_extra,
-                                        int num_points, int B, int Q, int K, float eos_coef, float num_masks, float w_ce, float w_mask, float w_dice,
-                                        const void* workspace, size_t workspace_bytes, const float* grad3, float* dlogits, int lddl, float* dmasks,
-                                        fx_stream_t stream_) {
+static int mask_set_loss_bwd_impl(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H,
+                                  int W, const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx,
+                                  const int32_t* tgt_idx, const float* rand_over, int n_over, const float* rand_extra, int n_extra,
+                                  int num_points, int B, int Q, int K, float eos_coef, int cls_mode, float focal_alpha, float focal_gamma, float num_masks,
+                                  float w_ce, float w_mask, float w_dice, const void* workspace, size_t workspace_bytes, const float* grad3, float* dlogits,
+                                  int lddl, float* dmasks, fx_stream_t stream_) {
   FX_CHECK_ARG(logits && pred_masks && tgt_offsets && workspace && grad3 && dlogits && dmasks && B > 0 && Q > 0 && K > 0);
-  FX_CHECK_ARG(ldl >= K + 1 && lddl >= K + 1 && h > 0 && w > 0 && H > 0 && W > 0 && sum_T >= 0 && num_points > 0 && n_extra >= 0 && n_extra <= num_points);
+  const int cls_cols = mask_class_loss_cols(cls_mode, K);
+  FX_CHECK_ARG(cls_cols > 0 && (cls_mode == FX_CLASS_LOSS_CE || (tgt_labels && pred_idx && tgt_idx)));
+  FX_CHECK_ARG(ldl >= cls_cols && lddl >= cls_cols && h > 0 && w > 0 && H > 0 && W > 0 && sum_T >= 0 && num_points > 0 && n_extra >= 0 && n_extra <= num_points);
   FX_CHECK_ARG(n_over >= num_points - n_extra && num_masks > 0.0f);
   FX_CHECK_ARG(sum_T == 0 || (tgt_masks && tgt_labels && pred_idx && tgt_idx && (n_extra == 0 || rand_extra) && (num_points == n_extra || rand_over)));
   FX_CHECK_ARG(workspace_bytes >= fx_mask_set_loss_workspace_bytes(B, Q, sum_T, n_over) && ((uintptr_t)workspace % 8) == 0);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const double* ce_partial = reinterpret_cast<const double*>(workspace);
   double* rows = const_cast<double*>(ce_partial) + (size_t)B * Q * 2;
-  hipLaunchKernelGGL(mask_label_ce_bwd_kernel, dim3((B * Q + 3) / 4), dim3(256), 0, stream, logits, ldl, tgt_labels, tgt_offsets, pred_idx, tgt_idx, B * Q, Q,
-                     K, eos_coef, rows + (size_t)sum_T * 4, grad3, w_ce, dlogits, lddl);
+  if (cls_mode == FX_CLASS_LOSS_CE)
+    hipLaunchKernelGGL(mask_label_ce_bwd_kernel, dim3((B * Q + 3) / 4), dim3(256), 0, stream, logits, ldl, tgt_labels, tgt_offsets, pred_idx, tgt_idx, B * Q, Q,
+                       K, eos_coef, rows + (size_t)sum_T * 4, grad3, w_ce, dlogits, lddl);
+  else
+    hipLaunchKernelGGL(mask_label_cls_bwd_kernel, dim3((B * Q + 3) / 4), dim3(256), 0, stream, logits, ldl, tgt_labels, tgt_offsets, pred_idx, tgt_idx, B * Q, Q,
+                       K, cls_mode, focal_alpha, focal_gamma, (float)(1.0 / mask_class_loss_divisor(cls_mode, B * Q, num_masks)), grad3, w_ce, dlogits, lddl);
   if (sum_T > 0) {
     const float c_bce = w_mask / (num_masks * (float)num_points), c_dice = w_dice / num_masks;
     const float* xs = reinterpret_cast<const float*>(rows + (size_t)sum_T * 4 + 1);
@@ -688,5 +856,74 @@ extern "C" int fx_mask_set_loss_bwd_f32(const float* logits, int ldl, const floa
     hipLaunchKernelGGL(mask_point_loss_bwd_kernel, dim3(sum_T, split), dim3(256), 0, stream, pred_masks, h, w, tgt_masks, tgt_is_u8, H, W, tgt_offsets, B, Q,
                        pred_idx, tgt_idx, rand_over, n_over, rand_extra, n_extra, num_points - n_extra, rows, xs, sel, c_bce, c_dice, grad3, dmasks);
   }
+  return fx_launch_status();
+}
+
+extern "C" int fx_mask_set_loss_bwd_f32(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H,
+                                        int W, const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx,
+                                        const int32_t* tgt_idx, const float* rand_over, int n_over, const float* rand_extra, int n_extra,
+                                        int num_points, int B, int Q, int K, float eos_coef, float num_masks, float w_ce, float w_mask, float w_dice,
+                                        const void* workspace, size_t workspace_bytes, const float* grad3, float* dlogits, int lddl, float* dmasks,
+                                        fx_stream_t stream_) {
+  return mask_set_loss_bwd_impl(logits, ldl, pred_masks, h, w, tgt_masks, tgt_is_u8, H, W, tgt_labels, tgt_offsets, sum_T, pred_idx, tgt_idx, rand_over,
+                                n_over, rand_extra, n_extra, num_points, B, Q, K, eos_coef, FX_CLASS_LOSS_CE, 0.0f, 0.0f, num_masks, w_ce, w_mask, w_dice,
+                                workspace, workspace_bytes, grad3, dlogits, lddl, dmasks, stream_);
+}
+
+extern "C" int fx_mask_set_loss_cls_bwd_f32(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H,
+                                            int W, const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx,
+                                            const int32_t* tgt_idx, const float* rand_over, int n_over, const float* rand_extra, int n_extra,
+                                            int num_points, int B, int Q, int K, float eos_coef, int cls_mode, float focal_alpha, float focal_gamma,
+                                            float num_masks, float w_ce, float w_mask, float w_dice, const void* workspace, size_t workspace_bytes,
+                                            const float* grad3, float* dlogits, int lddl, float* dmasks, fx_stream_t stream_) {
+  return mask_set_loss_bwd_impl(logits, ldl, pred_masks, h, w, tgt_masks, tgt_is_u8, H, W, tgt_labels, tgt_offsets, sum_T, pred_idx, tgt_idx, rand_over,
+                                n_over, rand_extra, n_extra, num_points, B, Q, K, eos_coef, cls_mode, focal_alpha, focal_gamma, num_masks, w_ce, w_mask,
+                                w_dice, workspace, workspace_bytes, grad3, dlogits, lddl, dmasks, stream_);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The class loss of one prediction set on its own (FOCAL / BCE / BCE_FOCAL; the CE loss is part of fx_mask_set_loss_f32): the kernels
+// above, then the row partials summed in a fixed order.  out1[0] = w_ce * loss_ce.
+__global__ __launch_bounds__(256) void mask_class_loss_final_kernel(const double* __restrict__ partial, int n_rows, float w_ce, float* __restrict__ out1) {
+  __shared__ double red[2][256];
+  double a = 0.0, d = 0.0;
+  for (int i = threadIdx.x; i < n_rows; i += 256) a += partial[2 * i], d += partial[2 * i + 1];
+  red[0][threadIdx.x] = a; red[1][threadIdx.x] = d;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[0][threadIdx.x] += red[0][threadIdx.x + o], red[1][threadIdx.x] += red[1][threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out1[0] = w_ce * (float)(red[0][0] / red[1][0]);
+}
+
+extern "C" size_t fx_mask_class_loss_workspace_bytes(int B, int Q) {
+  if (B <= 0 || Q <= 0) return 0;
+  return (size_t)B * Q * 2 * sizeof(double);
+}
+
+extern "C" int fx_mask_class_loss_f32(const float* logits, int ldl, const int32_t* tgt_labels, const int32_t* tgt_offsets, const int32_t* pred_idx,
+                                      const int32_t* tgt_idx, int B, int Q, int K, int mode, float focal_alpha, float focal_gamma, float num_masks,
+                                      float w_ce, void* workspace, size_t workspace_bytes, float* out1, fx_stream_t stream_) {
+  FX_CHECK_ARG(K > 0 && mode != FX_CLASS_LOSS_CE && mask_class_loss_cols(mode, K) > 0);
+  FX_CHECK_ARG(logits && tgt_labels && tgt_offsets && pred_idx && tgt_idx && workspace && out1 && B > 0 && Q > 0 && ldl >= mask_class_loss_cols(mode, K));
+  FX_CHECK_ARG(num_masks > 0.0f && workspace_bytes >= fx_mask_class_loss_workspace_bytes(B, Q) && ((uintptr_t)workspace % 8) == 0);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  double* partial = reinterpret_cast<double*>(workspace);
+  hipLaunchKernelGGL(mask_label_cls_kernel, dim3((B * Q + 3) / 4), dim3(256), 0, stream, logits, ldl, tgt_labels, tgt_offsets, pred_idx, tgt_idx, B * Q, Q, K, mode,
+                     focal_alpha, focal_gamma, mask_class_loss_divisor(mode, B * Q, num_masks), partial);
+  hipLaunchKernelGGL(mask_class_loss_final_kernel, dim3(1), dim3(256), 0, stream, partial, B * Q, w_ce, out1);
+  return fx_launch_status();
+}
+
+extern "C" int fx_mask_class_loss_bwd_f32(const float* logits, int ldl, const int32_t* tgt_labels, const int32_t* tgt_offsets, const int32_t* pred_idx,
+                                          const int32_t* tgt_idx, int B, int Q, int K, int mode, float focal_alpha, float focal_gamma, float num_masks,
+                                          float w_ce, const float* grad1, float* dlogits, int lddl, fx_stream_t stream_) {
+  FX_CHECK_ARG(K > 0 && mode != FX_CLASS_LOSS_CE && mask_class_loss_cols(mode, K) > 0);
+  FX_CHECK_ARG(logits && tgt_labels && tgt_offsets && pred_idx && tgt_idx && grad1 && dlogits && B > 0 && Q > 0 && num_masks > 0.0f);
+  FX_CHECK_ARG(ldl >= mask_class_loss_cols(mode, K) && lddl >= mask_class_loss_cols(mode, K));
+  hipLaunchKernelGGL(mask_label_cls_bwd_kernel, dim3((B * Q + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream_), logits, ldl, tgt_labels, tgt_offsets,
+                     pred_idx, tgt_idx, B * Q, Q, K, mode, focal_alpha, focal_gamma, (float)(1.0 / mask_class_loss_divisor(mode, B * Q, num_masks)), grad1, w_ce,
+                     dlogits, lddl);
   return fx_launch_status();
 }

@@ -4,6 +4,8 @@
   MaskHungarianMatcher.forward   focoos/models/fai_mf/loss.py:661-742 (== bisenetformer/loss.py)  -> fx_point_sample_f32 +
                                                                                                    fx_mask_match_cost_f32 + fx_lsa_f32
   SetCriterion.forward           focoos/models/fai_mf/loss.py:545-592                              -> fx_mask_set_loss_f32 per prediction set
+                                                                                                   (fx_mask_set_loss_cls_f32 when loss_class_type
+                                                                                                   is focal_loss / bce_loss / bce_focal_loss)
 
 Same argument / return structure as the reference (``outputs`` dict with pred_logits / pred_masks / aux_outputs, targets with
 ``labels`` / ``masks``; the matcher returns a list of (index_i, index_j) int64 tensors; the criterion the dict of weighted losses
@@ -14,6 +16,7 @@ for the loss.  Nothing leaves the GPU: no cost-matrix D2H copy, no host SciPy ca
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -126,11 +129,18 @@ class _MaskSetLossFn(torch.autograd.Function):
         ws = torch.empty(lib.fx_mask_set_loss_workspace_bytes(B, Q, tg.n, n_over) // 8 + 1, dtype=torch.float64, device=dev)
         out3 = torch.empty(3, dtype=torch.float32, device=dev)
         wd = crit.weight_dict
-        args = (logits.data_ptr(), K1, pm.data_ptr(), h, w, tg.masks.data_ptr(), tg.is_u8, tg.H, tg.W, tg.labels.data_ptr(), tg.offsets.data_ptr(), tg.n,
-                pi.data_ptr(), ti.data_ptr(), r_over.data_ptr(), n_over, r_extra.data_ptr(), n_extra, P, B, Q, K1 - 1, float(crit.eos_coef),
-                float(num_masks), float(wd.get("loss_ce", 1.0)), float(wd.get("loss_mask", 1.0)), float(wd.get("loss_dice", 1.0)), ws.data_ptr(),
+        ctx.cls = crit.loss_class_type != "ce_loss"
+        head = (logits.data_ptr(), K1, pm.data_ptr(), h, w, tg.masks.data_ptr(), tg.is_u8, tg.H, tg.W, tg.labels.data_ptr(), tg.offsets.data_ptr(), tg.n,
+                pi.data_ptr(), ti.data_ptr(), r_over.data_ptr(), n_over, r_extra.data_ptr(), n_extra, P, B, Q)
+        tail = (float(num_masks), float(wd.get("loss_ce", 1.0)), float(wd.get("loss_mask", 1.0)), float(wd.get("loss_dice", 1.0)), ws.data_ptr(),
                 ws.numel() * 8)
-        check(lib.fx_mask_set_loss_f32(*args, out3.data_ptr(), _stream(dev)), "fx_mask_set_loss_f32")
+        if ctx.cls:   # K = num_classes whatever the head's width (class_loss_columns checked it)
+            args = head + (int(crit.num_classes), float(crit.eos_coef), CLASS_LOSS_MODE[crit.loss_class_type], float(crit.focal_alpha),
+                           float(crit.focal_gamma)) + tail
+            check(lib.fx_mask_set_loss_cls_f32(*args, out3.data_ptr(), _stream(dev)), "fx_mask_set_loss_cls_f32")
+        else:
+            args = head + (K1 - 1, float(crit.eos_coef)) + tail
+            check(lib.fx_mask_set_loss_f32(*args, out3.data_ptr(), _stream(dev)), "fx_mask_set_loss_f32")
         ctx.args, ctx.keep = args, (tg, pi, ti, r_over, r_extra, ws)
         ctx.save_for_backward(logits, pm)
         return out3
@@ -142,24 +152,62 @@ class _MaskSetLossFn(torch.autograd.Function):
         g3 = g3.float().contiguous()
         dlogits = torch.empty_like(logits)
         dmasks = torch.zeros_like(pm)
-        check(lib.fx_mask_set_loss_bwd_f32(*ctx.args, g3.data_ptr(), dlogits.data_ptr(), logits.shape[-1], dmasks.data_ptr(), _stream(logits.device)),
-              "fx_mask_set_loss_bwd_f32")
+        bwd, name = (lib.fx_mask_set_loss_cls_bwd_f32, "fx_mask_set_loss_cls_bwd_f32") if ctx.cls else (lib.fx_mask_set_loss_bwd_f32, "fx_mask_set_loss_bwd_f32")
+        check(bwd(*ctx.args, g3.data_ptr(), dlogits.data_ptr(), logits.shape[-1], dmasks.data_ptr(), _stream(logits.device)), name)
         return dlogits, dmasks, None, None, None, None, None
+
+
+CLASS_LOSS_MODE = {"ce_loss": 0, "focal_loss": 1, "bce_loss": 2, "bce_focal_loss": 3}   # FX_CLASS_LOSS_* of include/focoos_amd.h
+
+
+def class_loss_columns(loss_class_type: str, cls_sigmoid: bool, num_classes: int, width: int) -> int:
+    """Columns of a ``[B, Q, width]`` logits tensor that SetCriterion.loss_labels (loss.py:413-462) feeds to its class loss; ValueError
+    where the reference itself fails on the shape.  The one-hot target of the two sigmoid losses has ``num_classes`` columns (the
+    no-object column is dropped, :440 / :449):
+      bce_loss        drops the logits' last column when cls_sigmoid and they are wider than the target (:441-442);
+      bce_focal_loss  passes the logits as they are (:450-456), so the ``num_classes + 1`` columns every head here emits
+                      (modelling.py:53; the inference path drops the last one after the sigmoid, :615-616) do not fit the target;
+      focal_loss / ce_loss  softmax over the columns, target index ``num_classes`` = no object."""
+    K = int(num_classes)
+    if loss_class_type == "bce_loss":
+        if width == K or (cls_sigmoid and width == K + 1):
+            return K
+        raise ValueError(f"bce_loss: logits [.., {width}]{' minus the dropped last column' if cls_sigmoid and width > K else ''} "
+                         f"against the one-hot target [.., {K}] (cls_sigmoid={bool(cls_sigmoid)}): the reference's "
+                         "binary_cross_entropy_with_logits rejects the shapes")
+    if loss_class_type == "bce_focal_loss":
+        if width == K:
+            return K
+        raise ValueError(f"bce_focal_loss: logits [.., {width}] against the one-hot target [.., {K}]: the reference passes the logits to "
+                         "sigmoid_focal_loss without dropping a column, which rejects the shapes")
+    if width < K + 1:
+        raise ValueError(f"{loss_class_type}: logits [.., {width}] have no column for the no-object class {K}")
+    if loss_class_type == "focal_loss" and width != K + 1:
+        raise NotImplementedError(f"focal_loss: the kernel takes the softmax over num_classes + 1 = {K + 1} columns, the logits have {width}")
+    return width
 
 
 class SetCriterion:
     def __init__(self, num_classes: int, matcher: MaskHungarianMatcher, weight_dict: Dict[str, float], losses=("labels", "masks"), eos_coef: float = 0.1,
                  num_points: int = 0, oversample_ratio: float = 3.0, importance_sample_ratio: float = 0.0, deep_supervision: bool = True,
-                 loss_class_type: str = "ce_loss", cls_sigmoid: bool = False, rand: Optional[Callable] = None):
-        if sorted(losses) != ["labels", "masks"] or loss_class_type != "ce_loss" or num_points <= 0:
-            raise NotImplementedError("engine criterion covers losses=['labels','masks'], loss_class_type='ce_loss', num_points > 0 (registry models)")
+                 use_focal: bool = False, loss_class_type: str = "ce_loss", focal_alpha: float = 0.75, focal_gamma: float = 2.0,
+                 cls_sigmoid: bool = False, rand: Optional[Callable] = None):
+        assert loss_class_type in CLASS_LOSS_MODE, "loss_class_type must be in ['ce_loss', 'focal_loss', 'bce_loss', 'bce_focal_loss']"
+        if sorted(losses) != ["labels", "masks"] or num_points <= 0:
+            raise NotImplementedError("engine criterion covers losses=['labels','masks'], num_points > 0 (registry models)")
+        if use_focal:   # deprecated in the reference (loss.py:400-407): the focal variant of whichever family was named
+            warnings.warn("use_focal is deprecated. Use loss_class_type instead", DeprecationWarning)
+            loss_class_type = {"ce_loss": "focal_loss", "bce_loss": "bce_focal_loss"}.get(loss_class_type, loss_class_type)
         self.num_classes, self.matcher, self.weight_dict, self.eos_coef = num_classes, matcher, weight_dict, eos_coef
         self.num_points, self.oversample_ratio, self.importance_sample_ratio = num_points, oversample_ratio, importance_sample_ratio
         self.deep_supervision = deep_supervision
+        self.use_focal, self.loss_class_type, self.focal_alpha, self.focal_gamma, self.cls_sigmoid = use_focal, loss_class_type, focal_alpha, focal_gamma, cls_sigmoid
         self.rand = rand or matcher.rand
 
     def _one_set(self, out, tg: _MaskTargets, num_masks: float, fixed=None) -> torch.Tensor:
         logits, pm = out["pred_logits"].float().contiguous(), out["pred_masks"].float().contiguous()
+        if self.loss_class_type != "ce_loss":
+            class_loss_columns(self.loss_class_type, self.cls_sigmoid, self.num_classes, logits.shape[-1])
         if fixed is None:
             with torch.no_grad():
                 pi, ti = self.matcher.match_packed(logits.detach(), pm.detach(), tg)

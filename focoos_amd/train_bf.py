@@ -638,12 +638,14 @@ class _CriterionHolder(nn.Module):
         w[-1] = eos
         self.register_buffer("empty_weight", w)
         P = int(config.get("criterion_num_points", 12544))
+        sig = bool(config.get("cls_sigmoid", False))   # modelling.py:660-682: sigmoid matcher costs + the BCE class loss over the first nc columns
         matcher = MaskHungarianMatcher(float(config.get("matcher_cost_class", 2)), float(config.get("matcher_cost_mask", 5)),
-                                       float(config.get("matcher_cost_dice", 5)), P, bool(config.get("cls_sigmoid", False)), rand=rand)
+                                       float(config.get("matcher_cost_dice", 5)), P, sig, rand=rand)
         self.fn = SetCriterion(nc, matcher, {"loss_ce": float(config.get("weight_dict_loss_ce", 2)), "loss_mask": float(config.get("weight_dict_loss_mask", 5)),
                                              "loss_dice": float(config.get("weight_dict_loss_dice", 5))},
                                eos_coef=eos, num_points=P, oversample_ratio=3.0, importance_sample_ratio=0.75,
-                               deep_supervision=bool(config.get("criterion_deep_supervision", True)), rand=rand)
+                               deep_supervision=bool(config.get("criterion_deep_supervision", True)),
+                               loss_class_type="bce_loss" if sig else "ce_loss", cls_sigmoid=sig, rand=rand)
 
     def forward(self, outputs, targets, fixed_matches=None):
         return self.fn(outputs, targets, fixed_matches)
@@ -664,8 +666,6 @@ class BisenetFormerTrainable(nn.Module):
         bb = config["backbone_config"]
         if bb.get("model_type") != "stdc" or bb.get("block_type", "cat") != "cat" or int(bb.get("block_num", 4)) != 4:
             raise _lib.FocoosAmdError("trainable graph covers the STDC backbone with CatBottleneck blocks of 4 convs (bisenetformer-*)")
-        if bool(config.get("cls_sigmoid", False)):
-            raise NotImplementedError("cls_sigmoid / bce class loss is not part of the engine criterion (registry models use softmax + CE)")
         md = int(config.get("transformer_predictor_out_dim", 128))
         self.pixel_decoder = BiseNet(lib, config)
         self.head = nn.Module()

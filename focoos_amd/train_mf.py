@@ -240,8 +240,6 @@ class FAIMaskFormerTrainable(nn.Module):
             raise _lib.FocoosAmdError("focoos_amd needs a ROCm GPU (gfx950); no CPU fallback exists")
         lib = _lib.load()
         self.config = dict(config)
-        if bool(config.get("cls_sigmoid", False)):
-            raise NotImplementedError("cls_sigmoid / bce class loss is not part of the engine criterion (registry models use softmax + CE)")
         self.pixel_decoder = TransformerFPN(lib, config)
         self.head = nn.Module()
         self.head.criterion = _CriterionHolder(config, rand)

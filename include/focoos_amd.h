@@ -30,10 +30,12 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 14
+#define FX_ABI_VERSION 15
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
+/* SetCriterion.loss_class_type of the mask families (fx_mask_set_loss_cls_f32, fx_mask_class_loss_f32): ce_loss, focal_loss, bce_loss, bce_focal_loss */
+enum { FX_CLASS_LOSS_CE = 0, FX_CLASS_LOSS_FOCAL = 1, FX_CLASS_LOSS_BCE = 2, FX_CLASS_LOSS_BCE_FOCAL = 3 };
 
 typedef void* fx_stream_t; /* hipStream_t */
 
@@ -496,6 +498,29 @@ int fx_mask_set_loss_f32(const float* logits, int ldl, const float* pred_masks, 
                          const float* rand_over, int n_over, const float* rand_extra, int n_extra, int num_points, int B, int Q, int K,
                          float eos_coef, float num_masks, float w_ce, float w_mask, float w_dice, void* workspace, size_t workspace_bytes,
                          float* out3, fx_stream_t stream);
+/* The same with the class loss selected by cls_mode (FX_CLASS_LOSS_*; ABI 15), loss.py:430-457; FX_CLASS_LOSS_CE is the call above.
+ *   FOCAL      focal_loss (:215-255): alpha * ce * (1 - exp(-ce))^gamma of the row's softmax cross-entropy over K+1 columns, mean over B*Q.
+ *   BCE        binary_cross_entropy_with_logits of the FIRST K columns against the one-hot target without its no-object column,
+ *              sum over (b, q, k) / num_masks; a (K+1)-th column (what a cls_sigmoid head emits) is not read.  No eos_coef weighting.
+ *   BCE_FOCAL  sigmoid_focal_loss(x, onehot, focal_alpha, focal_gamma) over the same K columns, same reduction.
+ * focal_alpha < 0 = no alpha factor, as in the reference.  ldl >= the columns read (K+1 or K); an unknown mode is FX_ERR_INVALID_ARGUMENT. */
+int fx_mask_set_loss_cls_f32(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H, int W,
+                             const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx, const int32_t* tgt_idx,
+                             const float* rand_over, int n_over, const float* rand_extra, int n_extra, int num_points, int B, int Q, int K,
+                             float eos_coef, int cls_mode, float focal_alpha, float focal_gamma, float num_masks, float w_ce, float w_mask,
+                             float w_dice, void* workspace, size_t workspace_bytes, float* out3, fx_stream_t stream);
+/* The FOCAL / BCE / BCE_FOCAL class loss alone: out1[0] = w_ce * loss_ce.  One wave per (b, q) row, float64 row partials in
+ * workspace (fx_mask_class_loss_workspace_bytes(), 8-byte aligned) summed in a fixed order: bit-reproducible, no atomics.  All
+ * pointers are required (with no targets at all: any valid 4-byte buffers; only tgt_offsets is read). */
+size_t fx_mask_class_loss_workspace_bytes(int B, int Q);
+int fx_mask_class_loss_f32(const float* logits, int ldl, const int32_t* tgt_labels, const int32_t* tgt_offsets, const int32_t* pred_idx,
+                           const int32_t* tgt_idx, int B, int Q, int K, int mode, float focal_alpha, float focal_gamma, float num_masks, float w_ce,
+                           void* workspace, size_t workspace_bytes, float* out1, fx_stream_t stream);
+/* Its gradient under the upstream gradient grad1 f32 [1] ON THE DEVICE: dlogits f32 [B,Q,lddl], EVERY column of every row written -
+ * the columns outside the loss (a dropped no-object column, leading-dimension padding) get exactly 0. */
+int fx_mask_class_loss_bwd_f32(const float* logits, int ldl, const int32_t* tgt_labels, const int32_t* tgt_offsets, const int32_t* pred_idx,
+                               const int32_t* tgt_idx, int B, int Q, int K, int mode, float focal_alpha, float focal_gamma, float num_masks,
+                               float w_ce, const float* grad1, float* dlogits, int lddl, fx_stream_t stream);
 
 /* ---- BiSeNetFormer path (focoos/models/bisenetformer/modelling.py, focoos/nn/backbone/stdc.py) -------
  * Depthwise 3x3 stride-2 pad-1 convolution on NHWC bf16: y[b,ho,wo,c] = bias[c] + sum_k w[k][c] * x[...] (w f32 [9][C] with the
@@ -873,6 +898,14 @@ int fx_mask_set_loss_bwd_f32(const float* logits, int ldl, const float* pred_mas
                              const float* rand_over, int n_over, const float* rand_extra, int n_extra, int num_points, int B, int Q, int K,
                              float eos_coef, float num_masks, float w_ce, float w_mask, float w_dice, const void* workspace, size_t workspace_bytes,
                              const float* grad3, float* dlogits, int lddl, float* dmasks, fx_stream_t stream);
+/* Gradients of fx_mask_set_loss_cls_f32: as above; for the FOCAL / BCE / BCE_FOCAL modes dlogits is written as by
+ * fx_mask_class_loss_bwd_f32 (all lddl columns of every row). */
+int fx_mask_set_loss_cls_bwd_f32(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H, int W,
+                                 const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx, const int32_t* tgt_idx,
+                                 const float* rand_over, int n_over, const float* rand_extra, int n_extra, int num_points, int B, int Q, int K,
+                                 float eos_coef, int cls_mode, float focal_alpha, float focal_gamma, float num_masks, float w_ce, float w_mask,
+                                 float w_dice, const void* workspace, size_t workspace_bytes, const float* grad3, float* dlogits, int lddl, float* dmasks,
+                                 fx_stream_t stream);
 
 /* rows[b][p][q] = bf16(planes[b][q][p]) (q < Q; zero for Q <= q < Qp, Qp % 8 == 0, Qp <= 240): the [B,Q,h*w] f32 mask-logit gradient as
  * pixel-major bf16 rows - the operand layout of the two GEMMs behind the backward of einsum("bqc,bchw->bqhw")
