@@ -122,6 +122,9 @@ SIGNATURES = {
     "fx_augment_images_u8": [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp],
     "fx_augment_labels": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp],
     "fx_resize_bilinear_u8": [_vp, _i, _i, _vp, _i, _i, _vp],
+    "fx_tile_gather_u8_f32": [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "fx_merge_detections_workspace_bytes": [_i, _i],
+    "fx_merge_detections_nms": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "fx_maxpool3x3s2_nhwc_bf16": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "fx_stem_conv12_u8_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "fx_stem_conv_pool_supported": [_i, _i, _i, _i],
@@ -297,7 +300,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 15  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 16  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:
@@ -327,6 +330,7 @@ def load(name: str = None) -> C.CDLL:
     lib.fx_topk_rows_workspace_bytes.restype = C.c_size_t
     lib.fx_coco_match_workspace_bytes.restype = C.c_size_t
     lib.fx_mf_eval_masks_workspace_bytes.restype = C.c_size_t
+    lib.fx_merge_detections_workspace_bytes.restype = C.c_size_t
     lib.fx_error_string.argtypes = [C.c_int]
     lib.fx_error_string.restype = C.c_char_p
     if lib.fx_abi_version() != FX_ABI_VERSION:

@@ -385,6 +385,24 @@ class FocoosModel:
             raise NotImplementedError("annotation/drawing is outside the hot path")
         return self(image, threshold=threshold)
 
+    def infer_tiled(self, image, tile: Union[None, int, Tuple[int, int]] = None, overlap: float = 0.2, threshold: Optional[float] = None,
+                    merge_threshold: float = 0.5, merge_metric: str = "iou", include_full: bool = True, batch_size: Optional[int] = None,
+                    max_detections: int = 300) -> FocoosDetections:
+        """Tiled RT-DETR inference of ONE large picture (an engine-native mode like ``infer_stream``; the reference has none): ``image`` (what
+        ``infer`` takes) is cut into overlapping windows of ``tile`` (int or (h, w), default ``model_info.im_size``; both the window cut from
+        the frame and the size the model runs at) that share at least ``overlap`` in [0, 1) of a tile with their neighbours
+        (``tiled.tile_grid``); ``include_full`` adds the whole frame resized to the tile, so objects larger than a tile are still found.
+        The views run through the engine in chunks of ``batch_size`` (default min(views, 32)), the boxes above ``threshold`` (as in
+        ``infer``) are moved into frame pixels and duplicates are removed by class-aware greedy NMS: a detection removes the lower-scored
+        ones of its class whose IoU (``merge_metric="iou"``) or intersection over the smaller area (``"ios"``) with it exceeds
+        ``merge_threshold`` in (0, 1].  Returns one ``FocoosDetections`` with at most ``max_detections`` integer xyxy boxes in frame
+        pixels, best first.  Cropping, resizing and merging run on the device (fx_tile_gather_u8_f32, fx_merge_detections_nms; tiled.py):
+        the frame goes up once, one packed result comes back.  Bad arguments raise ValueError; every family but fai_detr raises
+        NotImplementedError before anything touches the GPU."""
+        from .tiled import infer_tiled as _infer_tiled
+
+        return _infer_tiled(self, image, tile, overlap, threshold, merge_threshold, merge_metric, include_full, batch_size, max_detections)
+
     def train(self, args, data_train, data_val=None, hub=None):
         """focoos_model.py:221-274: fine-tune on ``data_train`` (indexable, entries = ports.DatasetEntry) with ``args`` (ports.TrainerArgs):
         one process per GPU, TrainStep on every rank, artifacts in ``args.output_dir/args.run_name``, weights reloaded into the engine."""

@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 15
+#define FX_ABI_VERSION 16
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -268,6 +268,42 @@ int fx_augment_labels(const void* src, const int64_t* src_off, const int32_t* pl
 /* Processor.get_torch_batch resize (focoos/processor/base_processor.py:285-288):
  * F.interpolate(bilinear, align_corners=False) of one HWC uint8 image to [Ho,Wo,3] float32. */
 int fx_resize_bilinear_u8(const uint8_t* x, int H, int W, float* y, int Ho, int Wo, fx_stream_t stream);
+
+/* ---- Tiled inference of one large frame (ABI 16; csrc/tile_ops.hip): FocoosModel.infer_tiled's device side.
+ * fx_tile_gather_u8_f32: frame = one uint8 HWC image [H][W][3]; windows = int32 [N][4] (x0, y0, w, h), a DEVICE array, windows_host the same
+ * values in host memory; y = float32 [N][Ho][Wo][3] on the 0..255 scale, every element written, one launch.  View n is, bit for bit, what
+ * fx_resize_bilinear_u8 writes for a contiguous copy of window n resized to (Ho, Wo): taps are clamped to the window, not to the frame, and a
+ * window of exactly (Ho, Wo) holds the frame's bytes as floats.  The host copy is validated (positive extents, inside the frame,
+ * N <= 65535, H, W, Ho, Wo <= 16384) before anything is launched.  16-byte stores when Wo % 4 == 0 and y is 16-byte aligned.  Anything
+ * outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched.  The same in both libraries. */
+int fx_tile_gather_u8_f32(const uint8_t* frame, int H, int W, const int32_t* windows, const int32_t* windows_host, int N, float* y, int Ho, int Wo,
+                          fx_stream_t stream);
+
+/* fx_merge_detections_nms: the packed per-view results as the engine plan holds them (det_scores f32 [N][T], det_labels i32 [N][T], det_boxes
+ * i32 xyxy [N][T][4], det_count i32 [N]; slot j of view n is a candidate iff j < det_count[n]) and the views' windows (int32 [N][4], x0 y0 w h:
+ * only the origins are read) -> ONE packed list in frame coordinates: out_scores f32 [max_detections], out_labels i32, out_boxes i32 xyxy
+ * [max_detections][4] (16-byte aligned), out_count i32 [1]; slots from the count on are zero.
+ *  - a candidate's box is its slot's box plus (x0, y0), clamped to [0, frame_w] x [0, frame_h];
+ *  - order: descending score, ties to the lower view, then the lower slot (a total order; scores compare as IEEE floats, NaN and -0 are
+ *    ordered by their bit pattern);
+ *  - only the FX_MERGE_NMS_CAP best candidates enter suppression, the others are dropped and their number is ADDED to *status (device
+ *    int32, zeroed by the caller);
+ *  - class-aware greedy NMS: walking the order, a live candidate i removes every later j of the same label with
+ *    (double)inter > (double)merge_threshold * (double)den, den = union (FX_MERGE_IOU) or min(area_i, area_j) (FX_MERGE_IOS); areas and
+ *    intersections are int64 of the integer boxes, each side of the comparison is one IEEE operation, so the result is a pure function of
+ *    the inputs.  A zero-area box removes nothing and is never removed;
+ *  - the first max_detections survivors, in order, are the result.
+ * Three launches (rank, 64 x 64 blocks of the pairwise mask, one wavefront that walks it), no atomics.  workspace: at least
+ * fx_merge_detections_workspace_bytes(N, T) bytes (0 for invalid N, T), 16-byte aligned, contents undefined on entry.  merge_threshold in
+ * (0, 1], frame_h, frame_w <= 16384 (so every operand is exact in fp64), N * T < 2^31, max_detections >= 1.  Null or misaligned pointers, a
+ * short workspace, anything outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched.  The same in both libraries. */
+#define FX_MERGE_NMS_CAP 4096 /* 64 words x 64 bits: one removed-mask word per lane of one wavefront */
+enum { FX_MERGE_IOU = 0, FX_MERGE_IOS = 1 };
+size_t fx_merge_detections_workspace_bytes(int N, int T);
+int fx_merge_detections_nms(const float* det_scores, const int32_t* det_labels, const int32_t* det_boxes, const int32_t* det_count,
+                            const int32_t* windows, int N, int T, int frame_h, int frame_w, float merge_threshold, int metric, int max_detections,
+                            float* out_scores, int32_t* out_labels, int32_t* out_boxes, int32_t* out_count, int32_t* status, void* workspace,
+                            size_t workspace_bytes, fx_stream_t stream);
 
 /* F.max_pool2d(k=3,s=2,p=1) (resnet.py:254) on NHWC bf16. */
 int fx_maxpool3x3s2_nhwc_bf16(const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, fx_stream_t stream);
