@@ -125,6 +125,8 @@ SIGNATURES = {
     "fx_tile_gather_u8_f32": [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp],
     "fx_merge_detections_workspace_bytes": [_i, _i],
     "fx_merge_detections_nms": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
+    "fx_annotate_labels_from_detections": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
+    "fx_annotate_u8": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _i, _i, _i, _i, _vp],
     "fx_maxpool3x3s2_nhwc_bf16": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "fx_stem_conv12_u8_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "fx_stem_conv_pool_supported": [_i, _i, _i, _i],
@@ -300,7 +302,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 16  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 17  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:

@@ -282,9 +282,15 @@ class FocoosModel:
     def device(self):
         return self.model.device
 
-    def infer_batch(self, inputs: list, threshold: Optional[float] = None) -> List[FocoosDetections]:
+    def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate: bool = False) -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
-        reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621)."""
+        reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``annotate``: every result
+        also carries ``.image``, the uint8 input at its original size with the detections drawn on it on the device (annotate.py);
+        non-uint8 inputs then raise ValueError."""
+        if annotate:
+            from .annotate import annotate_results, check_inputs
+
+            check_inputs(inputs)
         t0 = perf_counter()
         images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
         t1 = perf_counter()
@@ -300,33 +306,47 @@ class FocoosModel:
         else:
             out = self.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, self.model_info.classes)
         t3 = perf_counter()
+        if annotate:
+            annotate_results(self, inputs, images, pl, out)
+        t4 = perf_counter()
         for o in out:
-            o.latency = InferLatency(preprocess=round(t1 - t0, 3), inference=round(t2 - t1, 3), postprocess=round(t3 - t2, 3))
+            o.latency = InferLatency(preprocess=round(t1 - t0, 3), inference=round(t2 - t1, 3), postprocess=round(t3 - t2, 3),
+                                     annotate=round(t4 - t3, 3) if annotate else None)
         return out
 
-    def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None):
+    def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate: bool = False):
         """Throughput inference (round 6): iterate over ``batches`` (each a list of images of ONE common shape after preprocessing and one
         batch size) and yield each batch's ``List[FocoosDetections]`` in order, with up to ``depth`` batches in flight on the engine's
         pipeline (engine.pipeline(): batch i+1's backbone runs beside batch i's decoder tail; default depth 3).  Same results as
         ``infer_batch`` per batch, bit for bit - the lanes share nothing but the read-only weights; what changes is that the GPU is not
-        drained between batches (RT-DETR-L bs = 32: +8 % images/s, MaskFormer-L +15 %, BiSeNetFormer-L +36 %)."""
+        drained between batches (RT-DETR-L bs = 32: +8 % images/s, MaskFormer-L +15 %, BiSeNetFormer-L +36 %).
+        ``annotate``: as in ``infer_batch`` - each batch is drawn after its lane finished, from the lane's still-valid results and the
+        submitted frames, on the current stream; the detections are those of ``annotate=False``."""
         from collections import deque
+
+        from .annotate import annotate_results, check_inputs
 
         thr = threshold or self.processor.threshold
         if self.model.family == "fai_cls":
-            yield from self._infer_stream_cls(batches, thr, depth)
+            yield from self._infer_stream_cls(batches, thr, depth, annotate)
             return
         mask_family = self.model.family in ("fai_mf", "bisenetformer")
-        pipe, pending = None, deque()
+        pipe, pending, frames = None, deque(), {}
 
         def finish():
             ticket = pending.popleft()
             pl = pipe.wait(ticket)
             if mask_family:
-                return self.processor.pack_detections(pl, self.model_info.classes)
-            return self.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, self.model_info.classes)
+                out = self.processor.pack_detections(pl, self.model_info.classes)
+            else:
+                out = self.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, self.model_info.classes)
+            if annotate:      # the lane's results stay valid until the lane is submitted to again, which happens after this returns
+                annotate_results(self, *frames.pop(ticket), pl, out)
+            return out
 
         for inputs in batches:
+            if annotate:
+                check_inputs(inputs, "infer_stream")
             images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
             x = self.model._to_nhwc(images)
             sizes = torch.tensor(self.processor.get_image_sizes(inputs), dtype=torch.int32, device=x.device)
@@ -340,10 +360,12 @@ class FocoosModel:
             if len(pending) >= pipe.depth:      # the lane about to be reused still holds an unread result
                 yield finish()
             pending.append(pipe.submit(x, sizes, thr))
+            if annotate:
+                frames[pending[-1]] = (inputs, x)      # the submitted batch stays referenced until it is drawn
         while pending:
             yield finish()
 
-    def _infer_stream_cls(self, batches, thr: float, depth: Optional[int]):
+    def _infer_stream_cls(self, batches, thr: float, depth: Optional[int], annotate: bool = False):
         """infer_stream of the classifiers: a pipeline is reused only when (B, H, W, input dtype) all match - a uint8 batch and a resized
         float32 batch of one shape run on different plans (the input buffer's dtype is part of the plan).  Each lane's logits are copied
         into a pinned host buffer on the lane's stream; the sigmoid / threshold run on them on the host."""
@@ -351,12 +373,19 @@ class FocoosModel:
 
         pipe, key, pending = None, None, deque()
 
+        from .annotate import annotate_results, check_inputs
+
         def finish():
-            ticket, host = pending.popleft()
+            ticket, host, drawn = pending.popleft()
             pipe.wait(ticket)
-            return self.processor.pack_detections(host["logits"], self.model_info.classes, thr)
+            out = self.processor.pack_detections(host["logits"], self.model_info.classes, thr)
+            if drawn is not None:
+                annotate_results(self, *drawn, None, out)
+            return out
 
         for inputs in batches:
+            if annotate:
+                check_inputs(inputs, "infer_stream")
             images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
             x = self.model._to_nhwc(images)
             B, H, W, _ = x.shape
@@ -368,7 +397,7 @@ class FocoosModel:
             if len(pending) >= pipe.depth:      # the lane about to be reused still holds an unread result
                 yield finish()
             host = {"logits": torch.empty(B, self.model.num_classes, dtype=torch.float32, pin_memory=True)}
-            pending.append((pipe.submit(x, None, thr, host), host))
+            pending.append((pipe.submit(x, None, thr, host), host, (inputs, x) if annotate else None))
         while pending:
             yield finish()
 
@@ -377,17 +406,24 @@ class FocoosModel:
         return self.infer_batch(lst, threshold=kwargs.get("threshold"))[0]
 
     def infer(self, image, threshold: Optional[float] = None, annotate: bool = False) -> FocoosDetections:
+        """focoos_model.py:370-416: one picture (path, PIL image, array, tensor) -> FocoosDetections.  ``annotate``: ``.image`` is the
+        picture (np.uint8 [H, W, 3] RGB, original size) with the detections drawn on it on the device (annotate.py; the input itself
+        when nothing was detected) and ``.latency.annotate`` / ``.latency.imload`` are set."""
+        t0 = perf_counter()
         if isinstance(image, (str, os.PathLike)):
             from PIL import Image
 
             image = np.array(Image.open(image).convert("RGB"))
-        if annotate:
-            raise NotImplementedError("annotation/drawing is outside the hot path")
-        return self(image, threshold=threshold)
+        if not annotate:
+            return self(image, threshold=threshold)
+        imload = perf_counter() - t0
+        res = self.infer_batch([image], threshold=threshold, annotate=True)[0]
+        res.latency.imload = round(imload, 3)
+        return res
 
     def infer_tiled(self, image, tile: Union[None, int, Tuple[int, int]] = None, overlap: float = 0.2, threshold: Optional[float] = None,
                     merge_threshold: float = 0.5, merge_metric: str = "iou", include_full: bool = True, batch_size: Optional[int] = None,
-                    max_detections: int = 300) -> FocoosDetections:
+                    max_detections: int = 300, annotate: bool = False) -> FocoosDetections:
         """Tiled RT-DETR inference of ONE large picture (an engine-native mode like ``infer_stream``; the reference has none): ``image`` (what
         ``infer`` takes) is cut into overlapping windows of ``tile`` (int or (h, w), default ``model_info.im_size``; both the window cut from
         the frame and the size the model runs at) that share at least ``overlap`` in [0, 1) of a tile with their neighbours
@@ -398,10 +434,12 @@ class FocoosModel:
         ``merge_threshold`` in (0, 1].  Returns one ``FocoosDetections`` with at most ``max_detections`` integer xyxy boxes in frame
         pixels, best first.  Cropping, resizing and merging run on the device (fx_tile_gather_u8_f32, fx_merge_detections_nms; tiled.py):
         the frame goes up once, one packed result comes back.  Bad arguments raise ValueError; every family but fai_detr raises
-        NotImplementedError before anything touches the GPU."""
+        NotImplementedError before anything touches the GPU.  ``annotate``: ``.image`` is the frame with the merged detections drawn on
+        it (the resident frame is drawn on the device and copied back beside the packed result; annotate.py)."""
         from .tiled import infer_tiled as _infer_tiled
 
-        return _infer_tiled(self, image, tile, overlap, threshold, merge_threshold, merge_metric, include_full, batch_size, max_detections)
+        return _infer_tiled(self, image, tile, overlap, threshold, merge_threshold, merge_metric, include_full, batch_size, max_detections,
+                            annotate)
 
     def train(self, args, data_train, data_val=None, hub=None):
         """focoos_model.py:221-274: fine-tune on ``data_train`` (indexable, entries = ports.DatasetEntry) with ``args`` (ports.TrainerArgs):

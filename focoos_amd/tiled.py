@@ -156,7 +156,7 @@ def detect_views(model, views: torch.Tensor, sizes: torch.Tensor, batch_size: in
 
 def infer_tiled(fm, image, tile: Union[None, int, Tuple[int, int]] = None, overlap: float = 0.2, threshold: Optional[float] = None,
                 merge_threshold: float = 0.5, merge_metric: str = "iou", include_full: bool = True, batch_size: Optional[int] = None,
-                max_detections: int = 300):
+                max_detections: int = 300, annotate: bool = False):
     """FocoosModel.infer_tiled (see there)."""
     from ._lib import load
     from .ports import InferLatency
@@ -164,6 +164,8 @@ def infer_tiled(fm, image, tile: Union[None, int, Tuple[int, int]] = None, overl
     check_supported(fm)
     im = fm.model_info.im_size
     th, tw = check_arguments(tile, overlap, merge_threshold, merge_metric, batch_size, max_detections, im)
+    if annotate and int(max_detections) > 1024:
+        raise ValueError(f"infer_tiled: annotate=True draws at most 1024 detections, got max_detections={max_detections}")
     t0 = perf_counter()
     frame = frame_tensor(image)
     H, W = int(frame.shape[0]), int(frame.shape[1])
@@ -194,6 +196,16 @@ def infer_tiled(fm, image, tile: Union[None, int, Tuple[int, int]] = None, overl
         warnings.warn(f"infer_tiled: {dropped} of {dropped + NMS_CAP} candidates were dropped before suppression (only the {NMS_CAP} best enter "
                       "it): raise the threshold")
     t3 = perf_counter()
+    if annotate:       # the frame is resident: draw the merged, frame-pixel detections on it (a caller's own device tensor stays untouched)
+        from types import SimpleNamespace
+
+        from .annotate import annotator_of, to_host
+
+        res = SimpleNamespace(det_scores=o_s, det_labels=o_l, det_boxes=o_b, det_count=cs[:1])
+        drawn = annotator_of(fm).annotate(frame_d[None], res, 0, out=torch.empty_like(frame_d[None]) if frame.is_cuda else None)
+        out.image = to_host(drawn)[0]
+    t4 = perf_counter()
     # host wall clock: the gather is enqueued in `preprocess`, the device drains it, the engine and the merge in `inference`
-    out.latency = InferLatency(preprocess=round(t1 - t0, 3), inference=round(t2 - t1, 3), postprocess=round(t3 - t2, 3))
+    out.latency = InferLatency(preprocess=round(t1 - t0, 3), inference=round(t2 - t1, 3), postprocess=round(t3 - t2, 3),
+                               annotate=round(t4 - t3, 3) if annotate else None)
     return out

@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 16
+#define FX_ABI_VERSION 17
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -304,6 +304,54 @@ int fx_merge_detections_nms(const float* det_scores, const int32_t* det_labels, 
                             const int32_t* windows, int N, int T, int frame_h, int frame_w, float merge_threshold, int metric, int max_detections,
                             float* out_scores, int32_t* out_labels, int32_t* out_boxes, int32_t* out_count, int32_t* status, void* workspace,
                             size_t workspace_bytes, fx_stream_t stream);
+
+/* ---- Drawing the detections on uint8 frames on the device (ABI 17; csrc/annotate.hip): FocoosModel.infer(annotate=True).
+ * A label record is the filled rectangle (x0, y0, w, h) of one text line in frame pixels, its colour (R | G << 8 | B << 16) and nchar glyph
+ * indices (ASCII code - 32, 0..94); nchar = 0 (w = h = 0) draws nothing. */
+#define FX_ANN_LNAME 24    /* a class name contributes at most this many glyphs */
+#define FX_ANN_LMAX 32     /* glyph slots of a record: LNAME + ": " + "100" + "%" = 30, padded to a multiple of 4 */
+#define FX_ANN_GLYPHS 95   /* ASCII 32..126 */
+#define FX_ANN_MAX_DIM 16384
+enum { FX_ANN_BOXES = 1, FX_ANN_MASKS = 2, FX_ANN_LABELS = 4 };
+typedef struct fx_annotate_record {
+  int32_t x0, y0, w, h;
+  uint32_t colour;
+  int32_t nchar;
+  uint8_t glyph[FX_ANN_LMAX];
+} fx_annotate_record; /* 56 bytes */
+
+/* fx_annotate_labels_from_detections: the packed results (scores f32 [B][T], labels i32 [B][T], boxes i32 xyxy [B][T][4], count i32 [B]) ->
+ * rec [B][T], one thread per slot.  name_glyphs u8 [K][FX_ANN_LNAME] / name_len i32 [K] hold the class names as glyph indices (lengths are
+ * clamped to 0..LNAME; a label outside 0..K-1 has an empty name).  Text = name, ": ", pct, "%" with
+ * pct = min(100, (int)(score * 100 rounded to f32, + 0.5 rounded to f32)) (two separate IEEE operations, a negative or NaN product gives 0),
+ * printed without leading zeros.  colour = FOCOOS_PALETTE[label mod 5] (mod into 0..4).  Geometry (integers): pad = 2 s,
+ * w = nchar * gw * s + 2 pad, h = gh * s + 2 pad, x0 = clamp(box.x0, 0, max(0, W - w)), y0 = box.y0 - h when that is >= 0, else
+ * clamp(box.y0, 0, max(0, H - h)).  A slot >= clamp(count[b], 0, T) gets an all-zero record.  B, T >= 1, K >= 0, 1 <= H, W <= 16384,
+ * 1 <= s <= 8, 1 <= gw, gh <= 32; outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched.  The same in both libraries. */
+int fx_annotate_labels_from_detections(const float* scores, const int32_t* labels, const int32_t* boxes, const int32_t* count, int B, int T,
+                                       const uint8_t* name_glyphs, const int32_t* name_len, int K, int H, int W, int s, int gw, int gh,
+                                       fx_annotate_record* rec, fx_stream_t stream);
+
+/* fx_annotate_u8: dst [B][H][W][3] = src [B][H][W][3] (uint8 RGB; dst == src or disjoint buffers) with the detections of images b0 .. b0+B-1 of
+ * the result arrays drawn on them: frame b uses row b0 + b of det_count [..], det_labels / det_area [..][T], det_boxes [..][T][4],
+ * rec [..][T] and the mask planes mask_words + ((b0 + b) * T + j) * plane_stride_words (int32 words, row y at + y * words_per_row, pixel x =
+ * bit x % 32 of word x / 32; bits at x >= W are not read).  Only slots j < clamp(det_count, 0, T) draw.  Per pixel, in this order:
+ *  1. FX_ANN_BOXES: with the box clipped to the frame (x0' = max(x0, 0), x1' = min(x1, W - 1), likewise y; nothing when x1' < x0' or
+ *     y1' < y0'), the pixel is on the outline when it is inside the clipped box (inclusive) and min(x - x0', x1' - x, y - y0', y1' - y) < 2 s;
+ *     it takes FOCOOS_PALETTE[label mod 5] of the LOWEST slot that hits.
+ *  2. FX_ANN_MASKS: among the slots whose clipped box (inclusive) holds the pixel and whose mask bit is set there, the one with the smallest
+ *     det_area, ties to the lower slot: p = (p + c + 1) >> 1 per channel with that slot's palette colour, over the result of step 1.
+ *  3. FX_ANN_LABELS: inside the rectangle of a record (x0 <= x < x0 + w, y0 <= y < y0 + h, nchar > 0; lowest slot wins) the pixel is white
+ *     when, with pad = 2 s, cx = (x - x0 - pad) / s and cy = (y - y0 - pad) / s (both offsets >= 0), cx / gw < nchar, cy < gh and bit
+ *     cx % gw of atlas[glyph[cx / gw] * gh + cy] is set; the record's colour otherwise.
+ * atlas: u32 [FX_ANN_GLYPHS][gh], bit i of a row word = column i.  A thread owns 4 consecutive pixels of a row (three dword loads / stores
+ * when W % 4 == 0 and both bases are 4-byte aligned), a workgroup a tile of 4 rows x 256 pixels whose slots are culled into an LDS list
+ * that holds all T of them.  det_area / mask_words are read only with FX_ANN_MASKS, rec / atlas only with FX_ANN_LABELS (may be null
+ * otherwise).  1 <= B <= 65535, b0 >= 0, 1 <= T <= 1024, 1 <= H, W <= 16384, 1 <= s <= 8, 1 <= gw, gh <= 32, words_per_row >= ceil(W / 32),
+ * plane_stride_words >= H * words_per_row; outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched.  The same in both libraries. */
+int fx_annotate_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int b0, int T, const int32_t* det_count, const int32_t* det_labels,
+                   const int32_t* det_boxes, const int32_t* det_area, const int32_t* mask_words, int words_per_row, int64_t plane_stride_words,
+                   const fx_annotate_record* rec, const uint32_t* atlas, int gw, int gh, int s, int flags, fx_stream_t stream);
 
 /* F.max_pool2d(k=3,s=2,p=1) (resnet.py:254) on NHWC bf16. */
 int fx_maxpool3x3s2_nhwc_bf16(const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, fx_stream_t stream);
