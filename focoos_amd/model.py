@@ -282,15 +282,24 @@ class FocoosModel:
     def device(self):
         return self.model.device
 
-    def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate: bool = False) -> List[FocoosDetections]:
+    def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate: bool = False, tracker=None) -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
         reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``annotate``: every result
         also carries ``.image``, the uint8 input at its original size with the detections drawn on it on the device (annotate.py);
-        non-uint8 inputs then raise ValueError."""
+        non-uint8 inputs then raise ValueError.  ``tracker``: a ``tracking.DeviceTracker`` of ``len(inputs)`` streams, for callers who
+        feed one batch per call - image b is the next frame of stream b, and every tracked detection gets its ``track_id`` (the
+        detections themselves are those of ``tracker=None``)."""
         if annotate:
             from .annotate import annotate_results, check_inputs
 
             check_inputs(inputs)
+        if tracker is not None:
+            from .tracking import DeviceTracker, attach_ids, check_family, for_batch, warn_drops
+
+            check_family(self.model.family, "infer_batch")
+            if not isinstance(tracker, DeviceTracker):
+                raise TypeError(f"infer_batch: tracker must be a DeviceTracker, not {type(tracker).__name__}")
+            for_batch(tracker, len(inputs), self.model.device, "infer_batch")
         t0 = perf_counter()
         images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
         t1 = perf_counter()
@@ -299,12 +308,18 @@ class FocoosModel:
         pl = self.model.detect(images, sizes=sizes, threshold=thr)
         torch.cuda.current_stream(self.model.device).synchronize()
         t2 = perf_counter()
+        ids = None
+        if tracker is not None:      # one launch on the packed device results; the ids come back beside the packed copy
+            ids = tracker.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
         if self.model.family == "fai_cls":
             out = self.processor.pack_detections(pl.logits.cpu(), self.model_info.classes, thr)   # the one D2H copy of the batch's logits
         elif self.model.family in ("fai_mf", "bisenetformer"):
             out = self.processor.pack_detections(pl, self.model_info.classes)
         else:
             out = self.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, self.model_info.classes)
+        if ids is not None:
+            attach_ids(out, ids.cpu().tolist())
+            warn_drops(tracker, "infer_batch")
         t3 = perf_counter()
         if annotate:
             annotate_results(self, inputs, images, pl, out)
@@ -314,18 +329,26 @@ class FocoosModel:
                                      annotate=round(t4 - t3, 3) if annotate else None)
         return out
 
-    def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate: bool = False):
+    def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate: bool = False, track=None):
         """Throughput inference (round 6): iterate over ``batches`` (each a list of images of ONE common shape after preprocessing and one
         batch size) and yield each batch's ``List[FocoosDetections]`` in order, with up to ``depth`` batches in flight on the engine's
         pipeline (engine.pipeline(): batch i+1's backbone runs beside batch i's decoder tail; default depth 3).  Same results as
         ``infer_batch`` per batch, bit for bit - the lanes share nothing but the read-only weights; what changes is that the GPU is not
         drained between batches (RT-DETR-L bs = 32: +8 % images/s, MaskFormer-L +15 %, BiSeNetFormer-L +36 %).
         ``annotate``: as in ``infer_batch`` - each batch is drawn after its lane finished, from the lane's still-valid results and the
-        submitted frames, on the current stream; the detections are those of ``annotate=False``."""
+        submitted frames, on the current stream; the detections are those of ``annotate=False``.
+        ``track``: identity across frames on the device (tracking.py) - batch index b is stream b (camera b), consecutive batches
+        are consecutive frames.  ``True`` (the defaults), a ``TrackerConfig``, or a ``DeviceTracker`` whose state then outlives the call.
+        Each batch is one more launch after its lane finished (batches finish in order) and every tracked detection carries ``track_id``;
+        the detections themselves are those of ``track=None``.  The first batch fixes the batch size, another size raises ValueError;
+        a family without boxes raises NotImplementedError before anything touches the GPU; births dropped for want of a free slot warn
+        once per call."""
         from collections import deque
 
         from .annotate import annotate_results, check_inputs
+        from .tracking import TrackerConfig, attach_ids, for_batch, resolve, warn_drops
 
+        track = resolve(track, self.model.family, self.model.device)
         thr = threshold or self.processor.threshold
         if self.model.family == "fai_cls":
             yield from self._infer_stream_cls(batches, thr, depth, annotate)
@@ -336,10 +359,15 @@ class FocoosModel:
         def finish():
             ticket = pending.popleft()
             pl = pipe.wait(ticket)
+            ids = None
+            if track is not None:      # batches finish in order, so the frames reach the tracker in order
+                ids = track.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
             if mask_family:
                 out = self.processor.pack_detections(pl, self.model_info.classes)
             else:
                 out = self.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, self.model_info.classes)
+            if ids is not None:
+                attach_ids(out, ids.cpu().tolist())
             if annotate:      # the lane's results stay valid until the lane is submitted to again, which happens after this returns
                 annotate_results(self, *frames.pop(ticket), pl, out)
             return out
@@ -351,6 +379,8 @@ class FocoosModel:
             x = self.model._to_nhwc(images)
             sizes = torch.tensor(self.processor.get_image_sizes(inputs), dtype=torch.int32, device=x.device)
             B, H, W, _ = x.shape
+            if track is not None:
+                track = for_batch(track, B, x.device)      # created with the first batch, which fixes B
             if pipe is None or (pipe.B, pipe.H, pipe.W) != (B, H, W):
                 while pending:
                     yield finish()
@@ -364,6 +394,8 @@ class FocoosModel:
                 frames[pending[-1]] = (inputs, x)      # the submitted batch stays referenced until it is drawn
         while pending:
             yield finish()
+        if track is not None and not isinstance(track, TrackerConfig):
+            warn_drops(track)
 
     def _infer_stream_cls(self, batches, thr: float, depth: Optional[int], annotate: bool = False):
         """infer_stream of the classifiers: a pipeline is reused only when (B, H, W, input dtype) all match - a uint8 batch and a resized

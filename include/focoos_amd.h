@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 17
+#define FX_ABI_VERSION 18
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -352,6 +352,44 @@ int fx_annotate_labels_from_detections(const float* scores, const int32_t* label
 int fx_annotate_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int b0, int T, const int32_t* det_count, const int32_t* det_labels,
                    const int32_t* det_boxes, const int32_t* det_area, const int32_t* mask_words, int words_per_row, int64_t plane_stride_words,
                    const fx_annotate_record* rec, const uint32_t* atlas, int gw, int gh, int s, int flags, fx_stream_t stream);
+
+/* ---- Identity across frames on the device (ABI 18; csrc/track_ops.hip): FocoosModel.infer_stream(track=...).
+ * A ByteTrack-shaped tracker over the packed results (det_scores f32 [B][T], det_labels i32 [B][T], det_boxes i32 xyxy [B][T][4], 16-byte
+ * aligned, det_count i32 [B]; slot j of stream b is a detection iff j < clamp(det_count[b], 0, T)).  Batch index b is stream b.  The state is
+ * structure-of-arrays device buffers owned by the caller: trk_id / trk_label / trk_tsu / trk_hits i32 [B][max_tracks] (id 0 = free slot, tsu =
+ * frames since the last match), trk_box / trk_vel f32 [B][max_tracks][4] (xyxy, 16-byte aligned), next_id i32 [B] (starts at 1) and a sticky
+ * status i32 [B].  A detection coordinate is clamped to [0, 16384] when it is read (the engine's boxes lie inside frames of at most that size).
+ *
+ * fx_track_update, for every stream, in one launch (one workgroup per stream, plain stores, no atomics):
+ *  1. predict: every live slot box += vel (four fp32 adds); its integer box is clamp(rint(box), 0, 16384) per coordinate, half to even.
+ *  2. a detection is HIGH when score >= high, LOW when low <= score < high (fp32 comparisons), otherwise it takes no part.
+ *  3. stage 1: eligible pairs are (live slot, HIGH detection) of equal label with both areas non-zero and
+ *     (double)inter > (double)match_iou * (double)union, areas and intersections int64 of the integer boxes.  The eligible pairs are walked
+ *     in the order IoU descending (compared exactly: inter_a * union_b against inter_b * union_a in int64, operands below 2^57), then slot id
+ *     ascending, then detection slot ascending; a pair is taken when both of its sides are still free.
+ *  4. stage 2: the slots still unmatched whose tsu was 0 before this update against the LOW detections, same rule, second_iou.
+ *  5. a matched slot: vel = vel + alpha * (float(det) - box) per coordinate (subtract, multiply, add: three separately rounded fp32
+ *     operations), then box = float(det), tsu = 0, hits += 1.
+ *  6. an unmatched live slot: tsu += 1; when tsu > track_buffer the slot is freed (every field of it becomes 0).
+ *  7. birth: the unmatched HIGH detections with score >= new_thresh and a non-zero area, in ascending slot, each take the lowest free slot
+ *     (slots freed in step 6 included): id = next_id++, label, box = float(det), vel = 0, hits = 1, tsu = 0.  Without a free slot the
+ *     detection is dropped and 1 is added to status[b].
+ * track_ids i32 [B][T], every element written: the id of the slot a detection was matched to or born into when that slot has
+ * hits >= min_hits, otherwise -1; -1 from det_count[b] on.
+ * Limits: 1 <= B <= FX_TRACK_MAX_STREAMS, 1 <= T, max_tracks <= FX_TRACK_MAX_SLOTS; 0 < low <= high <= 1, high <= new_thresh < inf, both IoU
+ * thresholds in (0, 1], track_buffer >= 0, min_hits >= 1, 0 <= alpha <= 1.  Null or misaligned pointers or anything else outside the
+ * contract: FX_ERR_INVALID_ARGUMENT, nothing launched, nothing written.
+ *
+ * fx_track_reset: stream b (0 <= b < B), or every stream when b = -1, gets all slots free (all fields 0), next_id 1, status 0.
+ * The same in both libraries. */
+#define FX_TRACK_MAX_SLOTS 1024
+#define FX_TRACK_MAX_STREAMS 65535
+int fx_track_update(const float* det_scores, const int32_t* det_labels, const int32_t* det_boxes, const int32_t* det_count, int B, int T,
+                    int32_t* trk_id, int32_t* trk_label, int32_t* trk_tsu, int32_t* trk_hits, float* trk_box, float* trk_vel, int32_t* next_id,
+                    int32_t* status, int max_tracks, float high, float low, float new_thresh, float match_iou, float second_iou,
+                    int track_buffer, int min_hits, float alpha, int32_t* track_ids, fx_stream_t stream);
+int fx_track_reset(int32_t* trk_id, int32_t* trk_label, int32_t* trk_tsu, int32_t* trk_hits, float* trk_box, float* trk_vel, int32_t* next_id,
+                   int32_t* status, int B, int max_tracks, int b, fx_stream_t stream);
 
 /* F.max_pool2d(k=3,s=2,p=1) (resnet.py:254) on NHWC bf16. */
 int fx_maxpool3x3s2_nhwc_bf16(const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, fx_stream_t stream);
