@@ -15,6 +15,16 @@ static inline int fx_launch_status() {
   return e == hipSuccess ? FX_OK : FX_ERR_LAUNCH;
 }
 
+// Raises a kernel's dynamic-LDS limit to `smem` bytes unless `granted` (the caller's cache of what the kernel already has: a `static int`
+// per launcher instantiation, 0 at first) covers it.  false: the runtime refused (nothing cached, the next launch asks again).
+static inline bool fx_ensure_dyn_smem(const void* kern, int smem, int& granted) {
+  if (smem > granted) {
+    if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return false;
+    granted = smem;
+  }
+  return true;
+}
+
 // ---- the 16-bit storage element of activations / packed weights / activation gradients -----------------------------------------
 // Default build: bfloat16.  -DFX_FP16=1 (the second library, libfocoos_amd_fp16.so: BASELINE configs[4] names fp16 - the reference trains
 // under torch.autocast(float16) + GradScaler, trainer/trainer.py:645,735-773): IEEE half, 11 significand bits instead of 8, exponent range

@@ -9,9 +9,7 @@
 //     <= 256 registers - two workgroups share a CU (2 x 78 KiB of LDS at W = 320) and one's halo fetch / store phase runs beside the
 //     other's MFMAs: the layer is a stream of 512-pixel tiles whose 2-5 k cycles of MFMA work hide behind the memory phases.
 // Tile: 512 pixels x N channels (N = 32: one weight block, N = 64: two), 4 waves over the pixels (4 x 4 pixel blocks of 32).
-#include <type_traits>
-
-#include "pw_common.h"
+#include "kplane_common.h"
 
 struct C32Args {
   const bf16_t* x;
@@ -22,16 +20,6 @@ struct C32Args {
   int HLp;            // halo rows of this launch rounded up to whole 64-row DMA blocks (<= HLP)
   unsigned x_bytes;
 };
-
-template <int OFF>
-__device__ __forceinline__ void c32_ldg(bf16x8& dst, unsigned voff, const bf16_t* sbase) {
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "+v"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
-}
-typedef __attribute__((address_space(3))) const bf16x8 c32_lds_frag_t;
-template <int IMM>
-__device__ __forceinline__ bf16x8 c32_lds_read(int addr) {
-  return *reinterpret_cast<c32_lds_frag_t*>((size_t)(unsigned)(addr + IMM));
-}
 
 template <int TN, int HLP, int ACT>
 __global__ __launch_bounds__(256, 2) void conv3x3_c32_kernel(const C32Args p) {
@@ -57,7 +45,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_kernel(const C32Args p) {
     c3_static_for<PF>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       ar[i][a] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      c32_ldg<(i & 3) * 1024>(ar[i][a], wvoff, wbase[a] + (i >> 2) * 2048);
+      kp_ldg<(i & 3) * 1024>(ar[i][a], wvoff, wbase[a] + (i >> 2) * 2048);
     });
   }
   if (wave == 0 && lane < 4) *reinterpret_cast<uint4*>(smem + lane * PLANE + HLP * 16) = make_uint4(0, 0, 0, 0);   // zero rows
@@ -119,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_kernel(const C32Args p) {
     }
   bf16x8 xb[2][TM];
 #pragma unroll
-  for (int b = 0; b < TM; ++b) xb[0][b] = c32_lds_read<0>(addr[0][b]);
+  for (int b = 0; b < TM; ++b) xb[0][b] = kp_lds_read<0>(addr[0][b]);
 #pragma unroll 1
   for (int g = 0; g < 3; ++g) {
     const int gn = g < 2 ? g + 1 : 0;    // taps of the NEXT cycle (behind the last one: cycle 0 again - reads that nothing uses)
@@ -143,13 +131,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_kernel(const C32Args p) {
         for (int b = 0; b < TM; ++b) {
           acc[a][b] = FX_MFMA_32x32x16(ar[s][a], xb[s & 1][b], acc[a][b]);
           if (a == 0) {   // fragment b of the next k-step
-            if constexpr (s + 1 < PF) xb[(s + 1) & 1][b] = c32_lds_read<((s + 1) % KJ) * PLANE>(addr[(s + 1) / KJ][b]);
-            else xb[0][b] = c32_lds_read<0>(addrn[0][b]);
+            if constexpr (s + 1 < PF) xb[(s + 1) & 1][b] = kp_lds_read<((s + 1) % KJ) * PLANE>(addr[(s + 1) / KJ][b]);
+            else xb[0][b] = kp_lds_read<0>(addrn[0][b]);
           }
           if constexpr (s < G) {   // address of block b at tap s of the next cycle
             if (a == TN - 1) addrn[s][b] = (mask9[b] & bitn[s]) ? row0[b] + offn[s] : zaddr;
           }
-          if (b == TM - 1) c32_ldg<(s & 3) * 1024>(ar[s][a], wvoff, wnext[a] + (s >> 2) * 2048);
+          if (b == TM - 1) kp_ldg<(s & 3) * 1024>(ar[s][a], wvoff, wnext[a] + (s >> 2) * 2048);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -166,7 +154,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_kernel(const C32Args p) {
   for (int i = 0; i < PF; ++i) {
     if constexpr (TN == 1) c3_wait<0>(ar[i][0]); else c3_wait<0>(ar[i][0], ar[i][1]);
   }
-  // ---- epilogue: activation, v_permlane32_swap pairs -> 16 contiguous bytes per lane, row stores
+  // ---- epilogue: activation, v_permlane32_swap pairs -> 16 contiguous bytes per lane, row stores (kp_store16, kplane_common.h)
 #pragma unroll
   for (int b = 0; b < TM; ++b) {
     const int m = m0 + (wave * TM + b) * 32 + l32;
@@ -175,27 +163,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_kernel(const C32Args p) {
 #pragma unroll
     for (int a = 0; a < TN; ++a)
 #pragma unroll
-      for (int g2 = 0; g2 < 2; ++g2) {
-        unsigned pk[2][2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          float v[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            v[e] = acc[a][b][4 * (2 * g2 + q) + e];
-            if constexpr (ACT == FX_ACT_RELU) v[e] = fmaxf(v[e], 0.0f);
-          }
-          pk[q][0] = pack_bf16x2(v[0], v[1]);
-          pk[q][1] = pack_bf16x2(v[2], v[3]);
-        }
-#pragma unroll
-        for (int w = 0; w < 2; ++w) {
-          const auto sw = __builtin_amdgcn_permlane32_swap(pk[0][w], pk[1][w], false, false);
-          pk[0][w] = sw[0];
-          pk[1][w] = sw[1];
-        }
-        if (live) *reinterpret_cast<uint4*>(yrow + a * 32 + g2 * 16) = make_uint4(pk[0][0], pk[0][1], pk[1][0], pk[1][1]);
-      }
+      for (int g2 = 0; g2 < 2; ++g2) kp_store16<ACT>(yrow + a * 32 + g2 * 16, acc[a][b], g2, live);
   }
 }
 
@@ -204,11 +172,8 @@ static int launch_c32(C32Args& a, hipStream_t stream) {
   constexpr int BM = 512, PLANE = (HLP + 1) * 16;
   const int smem = 4 * PLANE;
   auto kern = conv3x3_c32_kernel<TN, HLP, ACT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return FX_ERR_RUNTIME;
-    attr_set = true;
-  }
+  static int attr_smem = 0;
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(kern), smem, attr_smem)) return FX_ERR_RUNTIME;
   hipLaunchKernelGGL(kern, dim3((a.M + BM - 1) / BM), dim3(256), smem, stream, a);
   return fx_launch_status();
 }

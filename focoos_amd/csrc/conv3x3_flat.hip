@@ -289,12 +289,7 @@ __global__ __launch_bounds__((WN* WM + LOADER) * 64, 1) void conv3x3_flat_kernel
     const int m = m0 + row;
     if (m < p.M) {
       const uint4 v = *reinterpret_cast<const uint4*>(T + row * (BN * 2) + (pw_swz<RLT>(row, lc) << 4));
-      size_t yo = (size_t)m * p.ldy;
-      if (p.y_bstride) {
-        const int bb = m / p.HW;
-        yo = (size_t)bb * p.y_bstride + (size_t)(m - bb * p.HW) * p.ldy;
-      }
-      *reinterpret_cast<uint4*>(p.y + yo + n0 + lc * 8) = v;
+      *reinterpret_cast<uint4*>(p.y + fx_y_row_offset(m, p.ldy, p.HW, p.y_bstride) + n0 + lc * 8) = v;
     }
   }
 }
@@ -311,10 +306,7 @@ static int launch_c3(C3Args& a, hipStream_t stream) {
   if (!LOADER && a.C != CC) return FX_ERR_UNSUPPORTED;
   auto kern = conv3x3_flat_kernel<KT, CC, TN, TM, WN, WM, ACT, RESMODE, LOADER>;
   static int attr_smem = 0;
-  if (smem > attr_smem) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return FX_ERR_RUNTIME;
-    attr_smem = smem;
-  }
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(kern), smem, attr_smem)) return FX_ERR_RUNTIME;
   hipLaunchKernelGGL(kern, dim3(((a.M + BM - 1) / BM) * (a.N / BN)), dim3((NW + LOADER) * 64), smem, stream, a);
   return fx_launch_status();
 }

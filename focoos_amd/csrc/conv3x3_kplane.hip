@@ -17,11 +17,10 @@
 //   * masked (pixel, tap) pairs read a zero row that every plane carries at row index HLP (an address select, as before);
 //   * per k-step the memory instructions are spread one per MFMA slot: fragment reads behind the MFMAs of weight block 0, ring
 //     refills behind the last MFMA of each weight block, next-tap address setup behind the MFMAs of the last weight block;
-//   * weight loads use the scalar-base form (global_load ... v_off, s[base]) - the per-tap pointer update is SALU work;
-//   * SiLU = x * rcp(1 + exp(-x)) with the hardware reciprocal (1 ulp in fp32, far below the bf16 rounding of the output).
-#include <type_traits>
-
-#include "pw_common.h"
+//   * weight loads use the scalar-base form (global_load ... v_off, s[base]; kp_ldg) - the per-tap pointer update is SALU work;
+//   * SiLU = x * rcp(1 + exp(-x)) with the hardware reciprocal (1 ulp in fp32, far below the bf16 rounding of the output; kp_act).
+// kp_ldg / kp_lds_read / kp_act / kp_store16 are shared with the other kernels of the family: kplane_common.h.
+#include "kplane_common.h"
 
 struct C3KArgs {
   const bf16_t* x;
@@ -36,24 +35,6 @@ struct C3KArgs {
   unsigned x_bytes, r_bytes;
   unsigned long long* dbg;   // probe builds only (ABL & 16)
 };
-
-template <int OFF>
-__device__ __forceinline__ void c3k_ldg(bf16x8& dst, unsigned voff, const bf16_t* sbase) {
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "+v"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
-}
-
-typedef __attribute__((address_space(3))) const bf16x8 c3k_lds_frag_t;
-// fragment read at an integer LDS byte address (+ immediate): no "base + offset" VALU add per read
-template <int IMM>
-__device__ __forceinline__ bf16x8 c3k_lds_read(int addr) {
-  return *reinterpret_cast<c3k_lds_frag_t*>((size_t)(unsigned)(addr + IMM));
-}
-
-__device__ __forceinline__ float c3k_act(float v, std::integral_constant<int, FX_ACT_RELU>) { return fmaxf(v, 0.0f); }
-__device__ __forceinline__ float c3k_act(float v, std::integral_constant<int, FX_ACT_SILU>) {
-  return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-}
-__device__ __forceinline__ float c3k_act(float v, std::integral_constant<int, FX_ACT_NONE>) { return v; }
 
 // TN x TM 32x32 accumulator blocks per wave (TN weight blocks x TM pixel blocks), WN x WM consumer waves + the loader wave.
 // HLP: rows per plane (compile time: the k-step offsets are immediates); a launch needs BM + 2W + 2 <= HLP.
@@ -179,7 +160,7 @@ __global__ __launch_bounds__((WN* WM + LD) * 64, LD ? 1 : 2) void conv3x3_kplane
       c3_static_for<PF>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         ar[i][a] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        c3k_ldg<i * 1024>(ar[i][a], wvoff, w0);
+        kp_ldg<i * 1024>(ar[i][a], wvoff, w0);
       });
     }
     stamp2();
@@ -247,7 +228,7 @@ __global__ __launch_bounds__((WN* WM + LD) * 64, LD ? 1 : 2) void conv3x3_kplane
       }
       bf16x8 xb[2][TM];
 #pragma unroll
-      for (int b = 0; b < TM; ++b) xb[0][b] = c3k_lds_read<0>(addr[b]);
+      for (int b = 0; b < TM; ++b) xb[0][b] = kp_lds_read<0>(addr[b]);
       if constexpr (ABL & 2) {
 #pragma unroll
         for (int b = 0; b < TM; ++b) xb[1][b] = xb[0][b];
@@ -277,15 +258,15 @@ __global__ __launch_bounds__((WN* WM + LD) * 64, LD ? 1 : 2) void conv3x3_kplane
               acc[a][b] = FX_MFMA_32x32x16(ar[j][a], xb[j & 1][b], acc[a][b]);
               if constexpr (!(ABL & 2)) {
                 if (a == 0) {   // fragment b of the next k-step (k-step 0 of the next tap behind the last one)
-                  if constexpr (j + 1 < KJ) xb[(j + 1) & 1][b] = c3k_lds_read<(j + 1) * PLANE>(addr[b]);
-                  else xb[0][b] = c3k_lds_read<0>(addrn[b]);
+                  if constexpr (j + 1 < KJ) xb[(j + 1) & 1][b] = kp_lds_read<(j + 1) * PLANE>(addr[b]);
+                  else xb[0][b] = kp_lds_read<0>(addrn[b]);
                 }
               }
               if constexpr (j == 0) {   // address of block b at the next tap: 4 VALU ops behind an MFMA of the last weight block
                 if (a == TN - 1) addrn[b] = (mask9[b] & bitn) ? row0[b] + offn : zaddr;
               }
               if constexpr (!(ABL & 1)) {
-                if (b == TM - 1) c3k_ldg<j * 1024>(ar[j][a], wvoff, wnext[a]);
+                if (b == TM - 1) kp_ldg<j * 1024>(ar[j][a], wvoff, wnext[a]);
               }
               __builtin_amdgcn_sched_barrier(0);
             }
@@ -303,43 +284,18 @@ __global__ __launch_bounds__((WN* WM + LD) * 64, LD ? 1 : 2) void conv3x3_kplane
       if constexpr (TN == 1) c3_wait<0>(ar[i][0]); else c3_wait<0>(ar[i][0], ar[i][1]);
     }
     if constexpr (RESMODE == 0) {
-      // No residual: straight from the accumulators to memory.  A lane owns 4 consecutive channels (8 bytes) of pixel l32 per
-      // (n-block, 8-channel group gq); v_permlane32_swap pairs group 2g of the lower half-wave with group 2g+1 of the upper one,
-      // after which every lane holds 16 contiguous bytes of its pixel row: 16 dwordx4 stores per wave, no LDS tile, no barrier.
+      // No residual: straight from the accumulators to memory (kp_store16, kplane_common.h): 16 dwordx4 stores per wave, no LDS tile,
+      // no barrier.
       stamp();
 #pragma unroll
       for (int b = 0; b < TM; ++b) {
         const int m = m0 + (wm * TM + b) * 32 + l32;
-        size_t yo = (size_t)m * p.ldy;
-        if (p.y_bstride) {
-          const int bb = m / p.HW;
-          yo = (size_t)bb * p.y_bstride + (size_t)(m - bb * p.HW) * p.ldy;
-        }
-        bf16_t* yrow = p.y + yo + n0 + wn * TN * 32 + half * 8;
+        bf16_t* yrow = p.y + fx_y_row_offset(m, p.ldy, p.HW, p.y_bstride) + n0 + wn * TN * 32 + half * 8;
         const bool live = m < p.M && !((ABL & 8) && p.H > 0);
 #pragma unroll
         for (int a = 0; a < TN; ++a)
 #pragma unroll
-          for (int g = 0; g < 2; ++g) {
-            unsigned pk[2][2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-              float v[4];
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = c3k_act(acc[a][b][4 * (2 * g + q) + e], std::integral_constant<int, ACT>{});
-              pk[q][0] = pack_bf16x2(v[0], v[1]);
-              pk[q][1] = pack_bf16x2(v[2], v[3]);
-            }
-            // lower lanes keep group 2g and receive the partner's group 2g (channels +4); upper lanes receive the partner's
-            // group 2g+1 and keep their own
-#pragma unroll
-            for (int w = 0; w < 2; ++w) {   // lanes 32-63 of pk[0] <-> lanes 0-31 of pk[1]
-              const auto sw = __builtin_amdgcn_permlane32_swap(pk[0][w], pk[1][w], false, false);
-              pk[0][w] = sw[0];
-              pk[1][w] = sw[1];
-            }
-            if (live) *reinterpret_cast<uint4*>(yrow + a * 32 + g * 16) = make_uint4(pk[0][0], pk[0][1], pk[1][0], pk[1][1]);
-          }
+          for (int g = 0; g < 2; ++g) kp_store16<ACT>(yrow + a * 32 + g * 16, acc[a][b], g, live);
       }
       stamp();
     } else {
@@ -368,7 +324,7 @@ __global__ __launch_bounds__((WN* WM + LD) * 64, LD ? 1 : 2) void conv3x3_kplane
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             if constexpr (RESMODE == 1) v[e] += r[e];                                  // act(conv + residual)
-            v[e] = c3k_act(v[e], std::integral_constant<int, ACT>{});
+            v[e] = kp_act<ACT>(v[e]);
             if constexpr (RESMODE == 2) v[e] += r[e];                                  // act(conv) + residual
             if constexpr (RESMODE == 3) v[e] = r[e] > 0.0f ? v[e] : 0.0f;              // act(conv) * (residual > 0): ReLU backward
           }
@@ -387,12 +343,7 @@ __global__ __launch_bounds__((WN* WM + LD) * 64, LD ? 1 : 2) void conv3x3_kplane
     const int m = m0 + row;
     if (m < p.M && !((ABL & 8) && p.H > 0)) {
       const uint4 v = *reinterpret_cast<const uint4*>(T + row * (BN * 2) + (pw_swz<RLT>(row, lc) << 4));
-      size_t yo = (size_t)m * p.ldy;
-      if (p.y_bstride) {
-        const int bb = m / p.HW;
-        yo = (size_t)bb * p.y_bstride + (size_t)(m - bb * p.HW) * p.ldy;
-      }
-      *reinterpret_cast<uint4*>(p.y + yo + n0 + lc * 8) = v;
+      *reinterpret_cast<uint4*>(p.y + fx_y_row_offset(m, p.ldy, p.HW, p.y_bstride) + n0 + lc * 8) = v;
     }
   }
   if constexpr (ABL & 16) {
@@ -413,10 +364,7 @@ static int launch_c3k(C3KArgs& a, hipStream_t stream) {
   if (smem > 160 * 1024) return FX_ERR_UNSUPPORTED;
   auto kern = conv3x3_kplane_kernel<TN, TM, WN, WM, HLP, ACT, RESMODE, ABL, LD>;
   static int attr_smem = 0;
-  if (smem > attr_smem) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return FX_ERR_RUNTIME;
-    attr_smem = smem;
-  }
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(kern), smem, attr_smem)) return FX_ERR_RUNTIME;
   hipLaunchKernelGGL(kern, dim3(((a.M + BM - 1) / BM) * (a.N / BN)), dim3((NW + LD) * 64), smem, stream, a);
   return fx_launch_status();
 }

@@ -24,9 +24,7 @@
 // DMA the same launches take 51 / 40 / 45 us and the stride-1 kernel needs 43 / 32 / 37 us for the same FLOPs: a (plane, 64-channel) chunk
 // is a quarter of the stride-1 chunk's work behind each barrier, and a second loader wave (NLD = 2) does not change the time.
 // Weights: the same fragment-ordered copy as the stride-1 kernel (k = tap * C + channel), read through the 4-slot register ring.
-#include <type_traits>
-
-#include "pw_common.h"
+#include "kplane_common.h"
 
 struct C3S2Args {
   const bf16_t* x;
@@ -39,19 +37,6 @@ struct C3S2Args {
   int64_t y_bstride;  // elements between images of y (0: contiguous)
   unsigned x_bytes;
 };
-
-template <int OFF>
-__device__ __forceinline__ void s2k_ldg(bf16x8& dst, unsigned voff, const bf16_t* sbase) {
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "+v"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
-}
-typedef __attribute__((address_space(3))) const bf16x8 s2k_lds_frag_t;
-template <int IMM>
-__device__ __forceinline__ bf16x8 s2k_lds_read(int addr) {
-  return *reinterpret_cast<s2k_lds_frag_t*>((size_t)(unsigned)(addr + IMM));
-}
-__device__ __forceinline__ float s2k_act(float v, std::integral_constant<int, FX_ACT_RELU>) { return fmaxf(v, 0.0f); }
-__device__ __forceinline__ float s2k_act(float v, std::integral_constant<int, FX_ACT_SILU>) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-__device__ __forceinline__ float s2k_act(float v, std::integral_constant<int, FX_ACT_NONE>) { return v; }
 
 // tap `ti` of parity plane (py, px): original filter tap t9 = dy * 3 + dx, LDS row offset (ry * Wo + rx) in bytes, border-mask bit
 struct S2Tap { int t9, off, bit; };
@@ -162,7 +147,7 @@ __global__ __launch_bounds__((WN* WM + NLD) * 64, 1) void conv3x3s2_kplane_kerne
       c3_static_for<PF>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         ar[i][a] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        s2k_ldg<i * 1024>(ar[i][a], wvoff, w0);
+        kp_ldg<i * 1024>(ar[i][a], wvoff, w0);
       });
     }
     dma_chunk(0, smem, wave, NW);   // this wave's share of the first chunk
@@ -216,7 +201,7 @@ __global__ __launch_bounds__((WN* WM + NLD) * 64, 1) void conv3x3s2_kplane_kerne
       }
       bf16x8 xb[2][TM];
 #pragma unroll
-      for (int b = 0; b < TM; ++b) xb[0][b] = s2k_lds_read<0>(addr[b]);
+      for (int b = 0; b < TM; ++b) xb[0][b] = kp_lds_read<0>(addr[b]);
 #pragma unroll 1
       for (int ti = 0; ti < ntap; ++ti) {
         const bool last_tap = ti == ntap - 1;
@@ -237,13 +222,13 @@ __global__ __launch_bounds__((WN* WM + NLD) * 64, 1) void conv3x3s2_kplane_kerne
             for (int b = 0; b < TM; ++b) {
               acc[a][b] = FX_MFMA_32x32x16(ar[j][a], xb[j & 1][b], acc[a][b]);
               if (a == 0) {   // fragment b of the next k-step (k-step 0 of the next tap behind the last one)
-                if constexpr (j + 1 < KJ) xb[(j + 1) & 1][b] = s2k_lds_read<(j + 1) * PLANE>(addr[b]);
-                else xb[0][b] = s2k_lds_read<0>(addrn[b]);
+                if constexpr (j + 1 < KJ) xb[(j + 1) & 1][b] = kp_lds_read<(j + 1) * PLANE>(addr[b]);
+                else xb[0][b] = kp_lds_read<0>(addrn[b]);
               }
               if constexpr (j == 0) {
                 if (a == TN - 1) addrn[b] = (mask4[b] & bitn) ? row0[b] + offn : zaddr;
               }
-              if (b == TM - 1) s2k_ldg<j * 1024>(ar[j][a], wvoff, wnext[a]);
+              if (b == TM - 1) kp_ldg<j * 1024>(ar[j][a], wvoff, wnext[a]);
               __builtin_amdgcn_sched_barrier(0);
             }
           }
@@ -258,38 +243,16 @@ __global__ __launch_bounds__((WN* WM + NLD) * 64, 1) void conv3x3s2_kplane_kerne
     for (int i = 0; i < PF; ++i) {
       if constexpr (TN == 1) c3_wait<0>(ar[i][0]); else c3_wait<0>(ar[i][0], ar[i][1]);
     }
-    // straight from the accumulators to memory (conv3x3_kplane.hip, RESMODE 0): v_permlane32_swap pairs -> 16-byte row stores
+    // straight from the accumulators to memory (kp_store16, kplane_common.h): v_permlane32_swap pairs -> 16-byte row stores
 #pragma unroll
     for (int b = 0; b < TM; ++b) {
       const int m = m0 + (wm * TM + b) * 32 + l32;
-      size_t yo = (size_t)m * p.ldy;
-      if (p.y_bstride) {
-        const int bb = m / p.HW;
-        yo = (size_t)bb * p.y_bstride + (size_t)(m - bb * p.HW) * p.ldy;
-      }
-      bf16_t* yrow = p.y + yo + n0 + wn * TN * 32 + half * 8;
+      bf16_t* yrow = p.y + fx_y_row_offset(m, p.ldy, p.HW, p.y_bstride) + n0 + wn * TN * 32 + half * 8;
       const bool live = m < p.M;
 #pragma unroll
       for (int a = 0; a < TN; ++a)
 #pragma unroll
-        for (int g = 0; g < 2; ++g) {
-          unsigned pk[2][2];
-#pragma unroll
-          for (int q = 0; q < 2; ++q) {
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = s2k_act(acc[a][b][4 * (2 * g + q) + e], std::integral_constant<int, ACT>{});
-            pk[q][0] = pack_bf16x2(v[0], v[1]);
-            pk[q][1] = pack_bf16x2(v[2], v[3]);
-          }
-#pragma unroll
-          for (int w = 0; w < 2; ++w) {   // lanes 32-63 of pk[0] <-> lanes 0-31 of pk[1]
-            const auto sw = __builtin_amdgcn_permlane32_swap(pk[0][w], pk[1][w], false, false);
-            pk[0][w] = sw[0];
-            pk[1][w] = sw[1];
-          }
-          if (live) *reinterpret_cast<uint4*>(yrow + a * 32 + g * 16) = make_uint4(pk[0][0], pk[0][1], pk[1][0], pk[1][1]);
-        }
+        for (int g = 0; g < 2; ++g) kp_store16<ACT>(yrow + a * 32 + g * 16, acc[a][b], g, live);
     }
   }
 }
@@ -305,10 +268,7 @@ static int launch_c3s2(C3S2Args& a, hipStream_t stream) {
   if (smem > 160 * 1024) return FX_ERR_UNSUPPORTED;
   auto kern = conv3x3s2_kplane_kernel<TN, TM, WN, WM, HLP, ACT, NLD>;
   static int attr_smem = 0;
-  if (smem > attr_smem) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return FX_ERR_RUNTIME;
-    attr_smem = smem;
-  }
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(kern), smem, attr_smem)) return FX_ERR_RUNTIME;
   hipLaunchKernelGGL(kern, dim3(((a.M + BM - 1) / BM) * (a.N / BN)), dim3((NW + NLD) * 64), smem, stream, a);
   return fx_launch_status();
 }

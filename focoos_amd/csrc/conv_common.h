@@ -1,4 +1,5 @@
-// Shared definitions of the implicit-GEMM convolution kernels (conv_igemm.hip, conv_igemm_dma.hip).
+// Shared definitions of the convolution kernels: the launch arguments and routing interface of every family, the LDS swizzle and
+// buffer-load helpers of the implicit-GEMM kernels (conv_igemm.hip, conv_igemm_dma.hip), the output-row address.
 #pragma once
 #include "common.h"
 
@@ -47,6 +48,16 @@ __device__ __forceinline__ uint4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned b
 }
 #define FX_OOB 0xFFFFFFF0u
 
+// Element offset of output row m (pixel m of the flattened [B, Ho, Wo] range, HW = Ho * Wo) in y: rows are ldy apart; with a batch
+// stride (ConvArgs.y_bstride != 0: the images of y are slices of a larger buffer) image bb starts at bb * y_bstride.
+__device__ __forceinline__ size_t fx_y_row_offset(int m, int ldy, int HW, int64_t y_bstride) {
+  size_t yo = (size_t)m * ldy;
+  if (y_bstride) {
+    const int bb = m / HW;
+    yo = (size_t)bb * y_bstride + (size_t)(m - bb * HW) * ldy;
+  }
+  return yo;
+}
 
 // Every launcher of a routed kernel family has this signature: the validated arguments, the fragment-order weight copy (NULL for the
 // implicit-GEMM kernels) and the epilogue mode conv_route computed (fx_c3_epilogue_mode).  conv_route (conv_igemm.hip) alone chooses

@@ -229,6 +229,8 @@ __global__ __launch_bounds__(256, (BK == 32 ? 4 : 2)) void conv_igemm_kernel(con
 #pragma unroll
           for (int i = 0; i < 8; ++i) v[i] = mf[i] > 0.0f ? v[i] : 0.0f;
         }
+        // fx_y_row_offset (conv_common.h) written out: with the helper's form (default first, the batch-stride case overriding it) hipcc
+        // lays this epilogue's branches out differently and adds n in a 64-bit add of its own - longer code for the same values
         int64_t yoff;
         if (p.y_bstride) {
           int bb = m / HoWo;
@@ -255,13 +257,9 @@ static int launch_conv(const ConvArgs& c, const bf16_t*, int, hipStream_t stream
   constexpr int STAGE = (BM + BN) * BK * 2;
   constexpr int EPI = 64 * (BN + 4) * 4;  // the epilogue stages 64 rows at a time
   constexpr int SMEM = (NSTAGE * STAGE > EPI) ? NSTAGE * STAGE : EPI;
-  static bool attr_set = false;
   auto kern = conv_igemm_kernel<BM, BN, BK, WM, WN, POOL, NSTAGE>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
-      return FX_ERR_RUNTIME;
-    attr_set = true;
-  }
+  static int attr_smem = 0;
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM, attr_smem)) return FX_ERR_RUNTIME;
   ConvArgs a = c;
   a.nNt = (a.N + BN - 1) / BN;
   int nMt = (a.M + BM - 1) / BM;

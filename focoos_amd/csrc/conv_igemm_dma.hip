@@ -217,6 +217,8 @@ __global__ __launch_bounds__(WM* WN * 64, 1) void conv_igemm_dma_kernel(const Co
 #pragma unroll
           for (int i = 0; i < 8; ++i) v[i] = rf[i] > 0.0f ? v[i] : 0.0f;
         }
+        // fx_y_row_offset (conv_common.h) written out: with the helper's form (default first, the batch-stride case overriding it) hipcc
+        // lays this epilogue's branches out differently and adds n in a 64-bit add of its own - longer code for the same values
         int64_t yoff;
         if (p.y_bstride) {
           const int bb = m / HoWo;
@@ -243,13 +245,9 @@ static int launch_dma(const ConvArgs& c, hipStream_t stream) {
   constexpr int STAGE = (BM + BN) * 128;
   constexpr int EPI = 64 * (BN + 4) * 4;
   constexpr int SMEM = (2 * STAGE > EPI) ? 2 * STAGE : EPI;
-  static bool attr_set = false;
   auto kern = conv_igemm_dma_kernel<BM, BN, WM, WN>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
-      return FX_ERR_RUNTIME;
-    attr_set = true;
-  }
+  static int attr_smem = 0;
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM, attr_smem)) return FX_ERR_RUNTIME;
   ConvArgs a = c;
   a.nNt = (a.N + BN - 1) / BN;
   const int nMt = (a.M + BM - 1) / BM;

@@ -310,13 +310,9 @@ template <int K1A, int K1B, int N2, bool QUAD = false>
 static int launch_pw_chain(const PwChainArgs& a, hipStream_t stream) {
   constexpr int BM = 64;
   constexpr int SMEM = BM * (K1A + K1B) * 2 + BM * 512;
-  static bool attr_set = false;
   auto kern = pw_chain_kernel<K1A, K1B, N2, BM, QUAD>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
-      return FX_ERR_RUNTIME;
-    attr_set = true;
-  }
+  static int attr_smem = 0;
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM, attr_smem)) return FX_ERR_RUNTIME;
   hipLaunchKernelGGL(kern, dim3((a.M + BM - 1) / BM), dim3(256), SMEM, stream, a);
   return fx_launch_status();
 }

@@ -12,13 +12,11 @@
 //   * epilogue: bias (accumulator init) + residual / activation in registers, v_permlane32_swap pairs -> 16-byte row stores straight to
 //     memory (no output tile in LDS, no barrier);
 //   * residual: read in the epilogue with the SAME 16-byte-per-lane addressing as the stores (one row block ahead), and taken back to
-//     the accumulator layout by the same v_permlane32_swap pairs (the swap is its own inverse).  (First form of this kernel: a fifth
-//     wave DMA-ing a 64 KiB residual tile into LDS per n-tile, two barriers per n-tile, one workgroup per CU - 9.7 us per n-tile where
+//     the accumulator layout by the same v_permlane32_swap pairs (kp_swap_rows, kplane_common.h: the swap is its own inverse).
+//     (First form of this kernel: a fifth wave DMA-ing a 64 KiB residual tile into LDS per n-tile, two barriers per n-tile, one workgroup per CU - 9.7 us per n-tile where
 //     the MFMAs take 2; now the workgroup is four waves and two of them share a CU, one's epilogue beside the other's K loop.)
 // Per 128-pixel tile of branch2c: 64 KiB in + 4 x (64 KiB residual + 64 KiB out) against 4 x 2 us of MFMAs: HBM-bound as it should be.
-#include <type_traits>
-
-#include "pw_common.h"
+#include "kplane_common.h"
 
 #ifndef FX_PWK_RES_DEPTH
 #define FX_PWK_RES_DEPTH 3
@@ -39,19 +37,6 @@ struct PWKArgs {
   unsigned x_bytes, r_bytes;
   int rot;            // 1: workgroup i walks its n-tiles starting at tile i % count (round 6, see the kernel)
 };
-
-template <int OFF>
-__device__ __forceinline__ void pwk_ldg(bf16x8& dst, unsigned voff, const bf16_t* sbase) {
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "+v"(dst) : "v"(voff), "s"(sbase), "n"(OFF) : "memory");
-}
-typedef __attribute__((address_space(3))) const bf16x8 pwk_lds_frag_t;
-template <int IMM>
-__device__ __forceinline__ bf16x8 pwk_lds_read(int addr) {
-  return *reinterpret_cast<pwk_lds_frag_t*>((size_t)(unsigned)(addr + IMM));
-}
-__device__ __forceinline__ float pwk_act(float v, std::integral_constant<int, FX_ACT_RELU>) { return fmaxf(v, 0.0f); }
-__device__ __forceinline__ float pwk_act(float v, std::integral_constant<int, FX_ACT_SILU>) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-__device__ __forceinline__ float pwk_act(float v, std::integral_constant<int, FX_ACT_NONE>) { return v; }
 
 // K: reduction length (256 / 512), resident.  4 waves side by side over a 256-channel n-tile (2 x 4 accumulator blocks each:
 // 128 pixels x 64 channels).  RESMODE: 0 none, 1 act(conv + residual), 3 act(conv) * (residual > 0).  Four waves at <= 256
@@ -115,7 +100,7 @@ __global__ __launch_bounds__(256, TM == 4 ? 2 : 3) void conv_pw_kplane_kernel(co
     c3_static_for<PF>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       ar[i][a] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      pwk_ldg<i * 1024>(ar[i][a], wvoff, w0);
+      kp_ldg<i * 1024>(ar[i][a], wvoff, w0);
     });
   }
   const int lds0 = (int)(unsigned)(size_t)((__attribute__((address_space(3))) unsigned char*)smem);
@@ -141,7 +126,7 @@ __global__ __launch_bounds__(256, TM == 4 ? 2 : 3) void conv_pw_kplane_kernel(co
       }
     bf16x8 xb[2][TM];
 #pragma unroll
-    for (int b = 0; b < TM; ++b) xb[0][b] = pwk_lds_read<0>(addr[b]);
+    for (int b = 0; b < TM; ++b) xb[0][b] = kp_lds_read<0>(addr[b]);
     // KS / 4 ring cycles of 4 k-steps; the refills of a cycle request the same slots of the next cycle (first cycle of the next
     // n-tile behind the last one; last n-tile: a harmless re-read)
 #pragma unroll 1
@@ -160,11 +145,11 @@ __global__ __launch_bounds__(256, TM == 4 ? 2 : 3) void conv_pw_kplane_kernel(co
           for (int b = 0; b < TM; ++b) {
             if constexpr (!(ABL & 8)) acc[a][b] = FX_MFMA_32x32x16(ar[j][a], xb[j & 1][b], acc[a][b]);
             if (a == 0) {   // fragment b of the next k-step (behind the last one of the n-tile: k-step 0 again, unused)
-              if constexpr (j + 1 < PF) xb[(j + 1) & 1][b] = pwk_lds_read<(j + 1) * PLANE>(addr[b] + aoff);
-              else xb[0][b] = pwk_lds_read<PF * PLANE>(addr[b] + (last ? -PF * PLANE : aoff));
+              if constexpr (j + 1 < PF) xb[(j + 1) & 1][b] = kp_lds_read<(j + 1) * PLANE>(addr[b] + aoff);
+              else xb[0][b] = kp_lds_read<PF * PLANE>(addr[b] + (last ? -PF * PLANE : aoff));
             }
             if constexpr (!(ABL & 1)) {
-              if (b == TM - 1) pwk_ldg<j * 1024>(ar[j][a], wvoff, wnext[a]);
+              if (b == TM - 1) kp_ldg<j * 1024>(ar[j][a], wvoff, wnext[a]);
             }
             __builtin_amdgcn_sched_barrier(0);
           }
@@ -206,24 +191,17 @@ __global__ __launch_bounds__(256, TM == 4 ? 2 : 3) void conv_pw_kplane_kernel(co
       }
       const int row = b * 32 + l32;
       const int m = m0 + row;
-      size_t yo = (size_t)m * p.ldy;
-      if (p.y_bstride) {
-        const int bb = m / p.HW;
-        yo = (size_t)bb * p.y_bstride + (size_t)(m - bb * p.HW) * p.ldy;
-      }
-      bf16_t* yrow = p.y + yo + n0 + wave * TN * 32 + half * 8;
+      bf16_t* yrow = p.y + fx_y_row_offset(m, p.ldy, p.HW, p.y_bstride) + n0 + wave * TN * 32 + half * 8;
       const bool live = m < p.M;
 #pragma unroll
       for (int a = 0; a < TN; ++a)
 #pragma unroll
         for (int g2 = 0; g2 < 2; ++g2) {
           unsigned pk[2][2], rq[2][2] = {{0u, 0u}, {0u, 0u}};
-          if constexpr (RESMODE != 0) {   // store layout -> accumulator layout: the inverse of the swaps below
+          if constexpr (RESMODE != 0) {   // store layout -> accumulator layout: the same swap (its own inverse, kplane_common.h)
             const uint4 R = rr[b % RS][a * 2 + g2];
-            const auto s0 = __builtin_amdgcn_permlane32_swap(R.x, R.z, false, false);
-            const auto s1 = __builtin_amdgcn_permlane32_swap(R.y, R.w, false, false);
-            rq[0][0] = s0[0]; rq[1][0] = s0[1];
-            rq[0][1] = s1[0]; rq[1][1] = s1[1];
+            rq[0][0] = R.x; rq[0][1] = R.y; rq[1][0] = R.z; rq[1][1] = R.w;
+            kp_swap_rows(rq);
           }
 #pragma unroll
           for (int q = 0; q < 2; ++q) {
@@ -235,18 +213,13 @@ __global__ __launch_bounds__(256, TM == 4 ? 2 : 3) void conv_pw_kplane_kernel(co
             for (int e = 0; e < 4; ++e) {
               v[e] = acc[a][b][4 * gq + e];
               if constexpr (RESMODE == 1) v[e] += r[e];
-              v[e] = pwk_act(v[e], std::integral_constant<int, ACT>{});
+              v[e] = kp_act<ACT>(v[e]);
               if constexpr (RESMODE == 3) v[e] = r[e] > 0.0f ? v[e] : 0.0f;
             }
             pk[q][0] = pack_bf16x2(v[0], v[1]);
             pk[q][1] = pack_bf16x2(v[2], v[3]);
           }
-#pragma unroll
-          for (int w = 0; w < 2; ++w) {   // lanes 32-63 of pk[0] <-> lanes 0-31 of pk[1]: 16 contiguous bytes per lane
-            const auto sw = __builtin_amdgcn_permlane32_swap(pk[0][w], pk[1][w], false, false);
-            pk[0][w] = sw[0];
-            pk[1][w] = sw[1];
-          }
+          kp_swap_rows(pk);   // 16 contiguous bytes per lane
           if (live && !((ABL & 2) && p.M > 0)) *reinterpret_cast<uint4*>(yrow + a * 32 + g2 * 16) = make_uint4(pk[0][0], pk[0][1], pk[1][0], pk[1][1]);
         }
     }
@@ -277,10 +250,7 @@ static int launch_pwk(PWKArgs& a, hipStream_t stream) {
   a.rot = rot;
   auto kern = conv_pw_kplane_kernel<K, ACT, RESMODE, TM, ABL>;
   static int attr_smem = 0;
-  if (smem > attr_smem) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return FX_ERR_RUNTIME;
-    attr_smem = smem;
-  }
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(kern), smem, attr_smem)) return FX_ERR_RUNTIME;
   hipLaunchKernelGGL(kern, dim3(mt, groups), dim3(256), smem, stream, a);
   return fx_launch_status();
 }

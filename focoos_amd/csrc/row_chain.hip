@@ -513,11 +513,7 @@ __global__ __launch_bounds__(512, 4) void row_chain_kernel(const fx_rc_stage* __
 extern "C" int fx_row_chain(const fx_rc_stage* program_device, int n_stages, int rows, int lds_bytes, fx_stream_t stream_) {
   FX_CHECK_ARG(program_device && n_stages > 0 && n_stages <= 64 && rows > 0 && lds_bytes > 0 && lds_bytes % 16 == 0 && lds_bytes + RC_SCRATCH <= 160 * 1024);
   static int attr_smem = 0;
-  if (lds_bytes + RC_SCRATCH > attr_smem) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(row_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes + RC_SCRATCH) != hipSuccess)
-      return FX_ERR_RUNTIME;
-    attr_smem = lds_bytes + RC_SCRATCH;
-  }
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(row_chain_kernel), lds_bytes + RC_SCRATCH, attr_smem)) return FX_ERR_RUNTIME;
   // diagnostic (scripts/dev/rc_stage_stamps.py): FX_RC_DBG = address of a device buffer of 64 x u64 that receives the s_memtime stamps of
   // workgroup 0 at every stage boundary; unset (the product): null, the kernel skips the stamps
   static unsigned long long* const dbg = reinterpret_cast<unsigned long long*>((uintptr_t)strtoull(getenv("FX_RC_DBG") ? getenv("FX_RC_DBG") : "0", nullptr, 0));

@@ -245,13 +245,9 @@ __global__ __launch_bounds__(256, 2) void score_head_kernel(const ScoreHeadArgs 
 template <int TN2>
 static int launch_score_head(const ScoreHeadArgs& a, hipStream_t stream) {
   constexpr int SMEM = 64 * 512 + 4 * 64 * 4;
-  static bool attr_set = false;
   auto kern = score_head_kernel<TN2>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM) != hipSuccess)
-      return FX_ERR_RUNTIME;
-    attr_set = true;
-  }
+  static int attr_smem = 0;
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(kern), SMEM, attr_smem)) return FX_ERR_RUNTIME;
   hipLaunchKernelGGL(kern, dim3((a.M + 63) / 64), dim3(256), SMEM, stream, a);
   return fx_launch_status();
 }

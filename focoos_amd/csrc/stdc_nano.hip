@@ -6,7 +6,7 @@
 // the work per byte is tiny and what matters is that every input byte leaves HBM once.  The conv kernel therefore stages a 2-D input tile
 // (output tile 32 columns x TR rows, plus the halo) in LDS once and reads all nine taps from there; the whole weight matrix (<= 18 fragments)
 // sits in registers for the life of the workgroup.
-#include "common.h"
+#include "kplane_common.h"
 
 // ------------------------------------------------------------------------------------------------
 // Stem, 16 output channels: two lanes per output pixel, 8 channels each; the [27][16] fp32 weight table in LDS (float4 reads: two distinct
@@ -78,7 +78,7 @@ extern "C" int fx_stem16_conv3x3s2(const void* x, int in_f32, const float* w, co
 // zeros outside the image) is copied into LDS with 16-byte loads, every input byte once per tile (halo re-read: 1.2x at stride 1, 1.1x at
 // stride 2).  Phase 2: per row block, KS = 9*C/16 MFMAs with A = the weight fragment of k-step ks (registers; N = 16 runs with the upper
 // 16 rows of A zero) and B = the 16 channels of that k-step's tap for the 32 pixels (one ds_read_b128 per lane).  Epilogue: bias, ReLU,
-// v_permlane32_swap pairs -> 16 contiguous bytes per lane (the conv3x3_c32.hip store).
+// v_permlane32_swap pairs -> 16 contiguous bytes per lane (kp_store16, kplane_common.h).
 struct C16Args {
   const bf16_t* x;
   const bf16_t* wf;      // [KS][64 lanes][8]: fragment-order weights of a 32-row weight block (fx_conv_desc.w_frag), rows >= N zero
@@ -150,25 +150,7 @@ __global__ __launch_bounds__(256) void conv3x3_c16_kernel(const C16Args p) {
 #pragma unroll
     for (int g2 = 0; g2 < 2; ++g2) {
       if (g2 * 16 >= p.N) break;
-      unsigned pk[2][2];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[e] = acc[m][4 * (2 * g2 + q) + e];
-          if constexpr (RELU) v[e] = fmaxf(v[e], 0.0f);
-        }
-        pk[q][0] = pack_bf16x2(v[0], v[1]);
-        pk[q][1] = pack_bf16x2(v[2], v[3]);
-      }
-#pragma unroll
-      for (int w = 0; w < 2; ++w) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(pk[0][w], pk[1][w], false, false);
-        pk[0][w] = sw[0];
-        pk[1][w] = sw[1];
-      }
-      if (live) *reinterpret_cast<uint4*>(yrow + g2 * 16) = make_uint4(pk[0][0], pk[0][1], pk[1][0], pk[1][1]);
+      kp_store16<RELU ? FX_ACT_RELU : FX_ACT_NONE>(yrow + g2 * 16, acc[m], g2, live);
     }
   }
 }
@@ -179,11 +161,8 @@ static int launch_c16(C16Args& a, int B, hipStream_t stream) {
   constexpr int IR = (TR - 1) * S + 3, IC = (TC - 1) * S + 3;
   constexpr int smem = IR * IC * C * 2;
   auto kern = conv3x3_c16_kernel<C, S, RELU>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) return FX_ERR_RUNTIME;
-    attr_set = true;
-  }
+  static int attr_smem = 0;
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(kern), smem, attr_smem)) return FX_ERR_RUNTIME;
   a.tiles_x = (a.Wo + TC - 1) / TC;
   const int tiles = a.tiles_x * ((a.Ho + TR - 1) / TR);
   hipLaunchKernelGGL(kern, dim3(tiles, B), dim3(256), smem, stream, a);

@@ -16,8 +16,8 @@
 //            the stand-alone kernel's; ReLU, ZERO outside the conv1_1 image (conv1_2's padding), bf16 -> LDS in conv3x3_c32's k-plane layout;
 //   phase 2  conv1_2 from those planes (tap (dy, dx) of position t = position t + dy * 66 + dx, no border masks), weights = the layer's fragment-order
 //            image (18 KiB) in LDS, a wave = one tile row = two 32-column blocks; bias-initialised accumulators, k-steps 0..17 in conv3x3_c32's order:
-//            bit-identical to it; ReLU, v_permlane32_swap pairs -> 16-byte row stores.
-#include "pw_common.h"
+//            bit-identical to it; ReLU, v_permlane32_swap pairs (kp_swap_rows, kplane_common.h) -> 16-byte row stores.
+#include "kplane_common.h"
 
 struct Stem12Args {
   const unsigned char* x;   // uint8 HWC images [B,H,W,3]
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(512, 4) void stem12_kernel(const Stem12Args p) {
       const bool live = yr < p.H1 && xc < p.W1;
       bf16_t* yrow = p.y + ((size_t)(b * p.H1 + yr) * p.W1 + xc) * p.ldy + half * 8;
 #pragma unroll
-      for (int g2 = 0; g2 < 2; ++g2) {
+      for (int g2 = 0; g2 < 2; ++g2) {   // kp_store16<FX_ACT_RELU> written out down to the swap: through the helper hipcc schedules one more s_nop
         unsigned q[2][2];
 #pragma unroll
         for (int q2 = 0; q2 < 2; ++q2) {
@@ -207,12 +207,7 @@ __global__ __launch_bounds__(512, 4) void stem12_kernel(const Stem12Args p) {
           q[q2][0] = pack_bf16x2(fmaxf(acc[bb][e], 0.0f), fmaxf(acc[bb][e + 1], 0.0f));
           q[q2][1] = pack_bf16x2(fmaxf(acc[bb][e + 2], 0.0f), fmaxf(acc[bb][e + 3], 0.0f));
         }
-#pragma unroll
-        for (int w2 = 0; w2 < 2; ++w2) {
-          const auto sw = __builtin_amdgcn_permlane32_swap(q[0][w2], q[1][w2], false, false);
-          q[0][w2] = sw[0];
-          q[1][w2] = sw[1];
-        }
+        kp_swap_rows(q);
         if (live) *reinterpret_cast<uint4*>(yrow + g2 * 16) = make_uint4(q[0][0], q[0][1], q[1][0], q[1][1]);
       }
     }
@@ -236,11 +231,8 @@ extern "C" int fx_stem_conv12_u8_bf16(const void* x_u8, const float* w1, const f
   const int64_t grid = (int64_t)B * a.nbands * a.nstrips;
   if (grid >= (1ll << 31) || (int64_t)B * H * W * 3 >= (1ll << 31)) return FX_ERR_UNSUPPORTED;
   a.x_bytes = (unsigned)((int64_t)B * H * W * 3);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(stem12_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, S12_SMEM) != hipSuccess) return FX_ERR_RUNTIME;
-    attr_set = true;
-  }
+  static int attr_smem = 0;
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(stem12_kernel), S12_SMEM, attr_smem)) return FX_ERR_RUNTIME;
   hipLaunchKernelGGL(stem12_kernel, dim3((int)grid), dim3(512), S12_SMEM, reinterpret_cast<hipStream_t>(stream_), a);
   return fx_launch_status();
 }

@@ -851,6 +851,47 @@ def test_pointwise_flat_batch_stride(lib, flat_small_shapes):
     assert (got[:, 20:20 + H * W] - ref).abs().max() / ref.abs().max() < 1.2e-2
 
 
+# B,H,W,C,N,stride,label prefix: 3x3 layers without a residual writing into slices of a larger buffer.  Stride 2 runs on conv3x3s2_kplane.hip
+# (direct-store epilogue: accumulators -> 16-byte row stores).  Stride 1: conv_route keeps every batch-strided 3x3 / s1 layer off the halo
+# kernels (conv3x3_kplane.hip, conv3x3_flat.hip), so through the C ABI this layer runs on the implicit-GEMM tiles; the case pins that
+# routing and checks the slices of what runs.
+KPLANE_BATCH_STRIDE_CASES = [
+    (3, 16, 16, 64, 64, 1, "conv_igemm<"),
+    (3, 16, 16, 128, 128, 2, "conv3x3s2_kplane<128>"),
+]
+
+
+@pytest.mark.parametrize("case", KPLANE_BATCH_STRIDE_CASES)
+def test_conv3x3_kplane_batch_stride(lib, case, flat_small_shapes):
+    """y_batch_stride != 0, ldy > N and a row offset through the 3x3 layers (the output-row address fx_y_row_offset of the k-plane
+    kernels' direct-store epilogue): every image's rows land in its slice of a NaN-filled [B, S, ldy] buffer and nothing else is written."""
+    B, H, W, Cc, N, stride, label = case
+    Ho, Wo = H // stride, W // stride
+    S, off, ldy = Ho * Wo + 50, 20, N + 16
+    g = torch.Generator().manual_seed(11 + stride)
+    x = torch.randn(B, H, W, Cc, generator=g) + torch.linspace(-1, 1, W)[None, None, :, None] + torch.linspace(-0.5, 0.5, H)[None, :, None, None]
+    W4 = torch.randn(N, Cc, 3, 3, generator=g) / math.sqrt(Cc * 9) + torch.linspace(-0.03, 0.03, 9).view(1, 1, 3, 3)
+    bias = torch.randn(N, generator=g) * 0.5
+    d = FxConvDesc()   # the routing label of this layer: which kernel the case checks
+    probe = torch.zeros(16, dtype=torch.bfloat16, device=DEV)
+    d.x = d.w = d.y = d.w_frag = probe.data_ptr()
+    d.B, d.H, d.W, d.C, d.ldx = B, H, W, Cc, Cc
+    d.Ho, d.Wo, d.N, d.ldy = Ho, Wo, N, ldy
+    d.KH, d.KW, d.stride, d.pad, d.act, d.y_batch_stride = 3, 3, stride, 1, FX_ACT["relu"], S * ldy
+    out = C.create_string_buffer(64)
+    check(lib.fx_conv2d_variant(C.byref(d), out, 64), "variant")
+    assert out.value.decode().startswith(label), out.value.decode()
+    buf = torch.full((B, S, ldy), float("nan"), dtype=torch.bfloat16, device=DEV)
+    run_conv(lib, x, W4, bias, stride, "relu", ldy=ldy, ybs=S * ldy, y_buf=buf, y_off=off * ldy, frag=True)
+    got = buf.float().cpu()
+    ref = ref_conv(x, W4, bias, stride, "relu").reshape(B, Ho * Wo, N)
+    assert torch.isnan(got[:, :off]).all() and torch.isnan(got[:, off + Ho * Wo:]).all()
+    assert torch.isnan(got[:, :, N:]).all()
+    rows = got[:, off:off + Ho * Wo, :N]
+    assert not torch.isnan(rows).any()
+    assert (rows - ref).abs().max() / ref.abs().max() < 1.2e-2
+
+
 
 # Both sides of every M threshold of the production routing (conv_route in conv_igemm.hip, c3k in conv3x3_kplane.hip, launch_pwk in
 # conv_pw_kplane.hip, fx_launch_pw_flat in conv3x3_flat.hip), reached by shapes whose natural M = B*H*W lands there - no FX_* variable
