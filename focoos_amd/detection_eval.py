@@ -598,12 +598,11 @@ def collect(focoos_model, data_test, indices: Sequence[int], batch_size: int) ->
     model = focoos_model.model
     eng, dev, K = model.engine, model.device, model.num_classes
     top_k = focoos_model.processor.top_k
-    before = set(eng.plans.keys())
     indices = list(indices)
     npig = torch.zeros(K, _NA, dtype=torch.int64, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     outs, pos = [], 0
-    try:
+    with eng.scoped_plans():
         for batch in _batches(data_test, indices, batch_size):
             x = torch.stack([img for _, img in batch]).to(dev).contiguous()
             pl = eng.forward(x)
@@ -618,10 +617,6 @@ def collect(focoos_model, data_test, indices: Sequence[int], batch_size: int) ->
         if cat is None:
             return MatchRecords(K)
         return records_from_device(indices[:pos], *cat, npig, K)
-    finally:
-        torch.cuda.synchronize(dev)
-        for k in [k for k in eng.plans.keys() if k not in before and not getattr(eng, "retain_plans", False)]:
-            del eng.plans[k]
 
 
 def _dist_worker(model_info, cfg, state, device_seed, args, data_test, out_path):

@@ -20,7 +20,9 @@ re-parameterised into one 3x3), biases fp32; scores / boxes / sampling offsets f
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import functools
 import math
 import os
 import weakref
@@ -37,6 +39,19 @@ BN_EPS = 1e-5
 DEFAULT_STREAMS = 2   # batch parts per step (two half-batch parts replayed concurrently: +9 %; see _MultiPlan).  FX_STREAMS=1: one part
 MIN_PART_BATCH = 4
 DEFAULT_PIPELINE_DEPTH = 3   # batches in flight of the throughput mode (_Pipeline); 2 / 3 / 4 measured 5 002-5 115 / 5 084-5 112 / 5 095-5 133 img/s in one call
+
+
+def resolve_parts(B: int, nsplit: Optional[int], two_queue_safe: bool) -> int:
+    """Batch parts of one step of ``B`` images: the requested ``nsplit`` (None: FX_STREAMS, default DEFAULT_STREAMS); 1 when the library
+    must stay on one hardware queue (``_lib.two_queue_safe()`` false); else counted down to a divisor of B that leaves every part at
+    least MIN_PART_BATCH images."""
+    if nsplit is None:
+        nsplit = int(os.environ.get("FX_STREAMS", str(DEFAULT_STREAMS)))
+    if nsplit > 1 and not two_queue_safe:
+        nsplit = 1
+    while nsplit > 1 and (B % nsplit or B // nsplit < MIN_PART_BATCH):
+        nsplit -= 1
+    return nsplit
 
 
 class NT:
@@ -231,7 +246,14 @@ class _Publisher:
 
 
 class _EngineBase:
-    """Device handle, weight-packing helpers and the ResNet-vd backbone weights shared by the model families."""
+    """Device handle, weight-packing helpers, the ResNet-vd backbone weights and the run machinery (plan table, pipeline, forward) shared
+    by the model families.  A family declares what differs as data and keeps thin ``plan`` / ``pipeline`` / ``forward`` wrappers with its
+    own signatures."""
+
+    plan_cls = None                       # the family's plan class (assigned below its definition)
+    split_batch = True                    # False: a step is never cut into batch parts (ClsEngine)
+    plan_options: Tuple[str, ...] = ()    # per-plan switches; None resolves to the engine attribute of the same name
+    forward_fills_sizes = False           # forward() writes the plan's image-size table (RT-DETR: the boxes are scaled to it)
 
     def __init__(self, config: Dict, device: str = "cuda:0"):
         if not torch.cuda.is_available():
@@ -265,6 +287,10 @@ class _EngineBase:
 
     def _end_load(self) -> None:
         self.plans.clear()
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        self._pack_all(self._begin_load(sd))
+        self._end_load()
 
     def publish_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
         """Refill every packed buffer from ``sd`` - the keys and shapes of the last ``load_state_dict``, tensors ON the engine's device
@@ -303,6 +329,61 @@ class _EngineBase:
         t = getattr(self, name).repeat(B, 1).contiguous()
         self._replicas.append((weakref.ref(t), name, B))
         return t
+
+    # ---- run machinery.  ``self.plans`` holds plans under ("plan", ...) keys and pipelines under ("pipeline", ...) keys.
+    def _options(self, opts: Dict) -> Dict[str, bool]:
+        return {k: bool(getattr(self, k) if opts.get(k) is None else opts[k]) for k in self.plan_options}
+
+    def _plan(self, B: int, H: int, W: int, f32_input: bool, nsplit: Optional[int], **opts):
+        opts = self._options(opts)
+        n = resolve_parts(B, nsplit, _lib.two_queue_safe()) if self.split_batch else 1
+        key = ("plan", B, H, W, f32_input, n, *opts.values())
+        if key not in self.plans:
+            self.plans[key] = (self.plan_cls(self, B, H, W, f32_input, **opts) if n <= 1
+                               else _MultiPlan(self, self.plan_cls, B, H, W, f32_input, n, **opts))
+        return self.plans[key]
+
+    def _pipeline(self, B: int, H: int, W: int, depth: Optional[int], f32_input: bool, nsplit: int, **opts) -> "_Pipeline":
+        opts = self._options(opts)
+        if depth is None:
+            depth = int(os.environ.get("FX_PIPELINE_DEPTH", str(DEFAULT_PIPELINE_DEPTH)))
+        if not _lib.two_queue_safe():     # a packed-fp32 build must stay on one hardware queue (two-queue hazard)
+            depth, nsplit = 1, 1
+        key = ("pipeline", B, H, W, f32_input, nsplit, depth, *opts.values())
+        if key not in self.plans:
+            self.plans[key] = _Pipeline(self, self.plan_cls, B, H, W, f32_input, depth, nsplit, **opts)
+        return self.plans[key]
+
+    def _forward(self, images: torch.Tensor, sizes: Optional[torch.Tensor], threshold: Optional[float], forced, use_graph: bool, **opts):
+        """One batch on the engine's main stream; teacher forcing and ``use_graph=False`` run on a single-part plan."""
+        assert images.dim() == 4 and images.shape[-1] == 3 and images.is_contiguous() and images.device == self.dev
+        f32 = images.dtype == torch.float32
+        assert f32 or images.dtype == torch.uint8
+        B, H, W, _ = images.shape
+        pl = self._plan(B, H, W, f32, 1 if (forced is not None or not use_graph) else None, **opts)
+        cur = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            _copy_in(pl, images, sizes, self.forward_fills_sizes)
+            pl.run(self.stream.cuda_stream, threshold if threshold is not None else self.threshold, forced, use_graph)
+        cur.wait_stream(self.stream)
+        return pl
+
+    def drop_plans_except(self, keep) -> None:
+        for k in [k for k in self.plans if k not in keep]:
+            del self.plans[k]
+
+    @contextlib.contextmanager
+    def scoped_plans(self):
+        """The plans (and pipelines) created inside the block are released when it ends, after the device has finished with them -
+        unless ``retain_plans`` is set (validation.Validator keeps them from one validation to the next)."""
+        before = set(self.plans)
+        try:
+            yield
+        finally:
+            torch.cuda.synchronize(self.dev)
+            if not self.retain_plans:
+                self.drop_plans_except(before)
 
     def _rec(self, x):
         if getattr(self, "_slots", None) is not None:
@@ -399,6 +480,8 @@ class _EngineBase:
 
 
 class DetrEngine(StdcEngineMixin, _EngineBase):
+    forward_fills_sizes = True
+
     def __init__(self, config: Dict, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0"):
         super().__init__(config, device)
         # backbone: ResNet-vd (fai-detr-l-*) or STDC (fai-detr-m-coco; engine_stdc.py)
@@ -423,10 +506,6 @@ class DetrEngine(StdcEngineMixin, _EngineBase):
         self.load_state_dict(state_dict)
 
     # ------------------------------------------------------------------ weight packing
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        self._pack_all(self._begin_load(sd))
-        self._end_load()
-
     def _pack_all(self, sd: Dict[str, torch.Tensor]) -> None:
         """The packing sequence, for host tensors (load_state_dict) and device tensors (publish_state_dict) alike: whatever it composes
         with torch stays on the device of ``sd``."""
@@ -599,53 +678,70 @@ class DetrEngine(StdcEngineMixin, _EngineBase):
     def plan(self, B: int, H: int, W: int, f32_input: bool = False, nsplit: Optional[int] = None):
         """nsplit > 1: the batch is cut into nsplit parts whose launch sequences are captured as concurrent branches of
         one hipGraph (default from FX_STREAMS, see _MultiPlan)."""
-        if nsplit is None:
-            nsplit = int(os.environ.get("FX_STREAMS", str(DEFAULT_STREAMS)))
-        if nsplit > 1 and not _lib.two_queue_safe():
-            nsplit = 1
-        while nsplit > 1 and (B % nsplit or B // nsplit < MIN_PART_BATCH):
-            nsplit -= 1
-        key = (B, H, W, f32_input, nsplit)
-        if key not in self.plans:
-            self.plans[key] = _Plan(self, B, H, W, f32_input) if nsplit <= 1 else _MultiPlan(self, _Plan, B, H, W, f32_input, nsplit)
-        return self.plans[key]
+        return self._plan(B, H, W, f32_input, nsplit)
 
     def pipeline(self, B: int, H: int, W: int, depth: Optional[int] = None, f32_input: bool = False, nsplit: int = 1) -> "_Pipeline":
         """Throughput mode (round 6): `depth` batches in flight, each on its OWN plan (own activation / output buffers) and its own stream
         of the device pool - batch i+1's backbone runs beside batch i's decoder tail, and a whole-batch plan (nsplit = 1) launches every
         layer once at twice the M of a half-batch part.  See _Pipeline.  depth: FX_PIPELINE_DEPTH, default 3."""
-        if depth is None:
-            depth = int(os.environ.get("FX_PIPELINE_DEPTH", str(DEFAULT_PIPELINE_DEPTH)))
-        if not _lib.two_queue_safe():     # a packed-fp32 build must stay on one hardware queue (two-queue hazard, DESIGN 5)
-            depth, nsplit = 1, 1
-        key = ("pipeline", B, H, W, f32_input, nsplit, depth)
-        if key not in self.plans:
-            self.plans[key] = _Pipeline(self, _Plan, B, H, W, f32_input, depth, nsplit)
-        return self.plans[key]
+        return self._pipeline(B, H, W, depth, f32_input, nsplit)
 
     def forward(self, images: torch.Tensor, sizes: Optional[torch.Tensor] = None, threshold: Optional[float] = None,
                 forced_topk: Optional[torch.Tensor] = None, use_graph: bool = True) -> "_Plan":
         """images: uint8 [B,H,W,3] (fused normalise path) or float32 [B,H,W,3] (0..255 scale), on the engine device.
         Returns the plan whose output buffers (probs, boxes, det_*) hold the results (valid until the next call)."""
-        assert images.dim() == 4 and images.shape[-1] == 3 and images.is_contiguous() and images.device == self.dev
-        f32 = images.dtype == torch.float32
-        assert f32 or images.dtype == torch.uint8
-        B, H, W, _ = images.shape
-        pl = self.plan(B, H, W, f32, 1 if (forced_topk is not None or not use_graph) else None)
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            pl.input.copy_(images, non_blocking=True)
-            if sizes is None:
-                pl.sizes.copy_(torch.tensor([[H, W]] * B, dtype=torch.int32), non_blocking=False)
-            else:
-                pl.sizes.copy_(sizes.to(torch.int32), non_blocking=True)
-            pl.run(self.stream.cuda_stream, threshold if threshold is not None else self.threshold, forced_topk, use_graph)
-        cur.wait_stream(self.stream)
-        return pl
+        return self._forward(images, sizes, threshold, forced_topk, use_graph)
 
 
-class _PlanBase:
+def _copy_in(pl, images: torch.Tensor, sizes: Optional[torch.Tensor] = None, fill_sizes: bool = True) -> None:
+    """A batch into a plan's input buffers on the current stream (``forward`` and ``_Pipeline.submit``).  Without ``sizes`` the image-size
+    table gets the plan's own [H, W] per image, from a host tensor (a synchronous copy)."""
+    pl.input.copy_(images, non_blocking=True)
+    if not fill_sizes:
+        return
+    if sizes is None:
+        pl.sizes.copy_(torch.tensor([[pl.H, pl.W]] * pl.B, dtype=torch.int32), non_blocking=False)
+    else:
+        pl.sizes.copy_(sizes.to(torch.int32), non_blocking=True)
+
+
+class _GraphOwner:
+    """What _PlanBase and _MultiPlan share: ``graph`` (one hipGraph, or a list of them) captured for the threshold ``graph_thr``."""
+
+    graph = None
+    graph_thr = None
+
+    def _capture(self, warm_up, bodies) -> List[C.c_void_p]:
+        """``warm_up()`` outside capture (first-use initialisation must not happen under capture), a synchronise of the current stream,
+        then each ``(stream, body)`` of ``bodies`` in turn: ``body()`` captured on ``stream``.  Returns the graphs."""
+        warm_up()
+        torch.cuda.current_stream(self.dev).synchronize()
+        graphs = []
+        for stream, body in bodies:
+            check(self.lib.fx_graph_begin(C.c_void_p(stream)), "fx_graph_begin")
+            try:
+                body()
+            finally:
+                g = C.c_void_p()
+                rc = self.lib.fx_graph_end(C.c_void_p(stream), C.byref(g))
+            check(rc, "fx_graph_end")
+            graphs.append(g)
+        return graphs
+
+    def _destroy_graphs(self) -> None:
+        graphs, self.graph = self.graph, None
+        for g in (graphs if isinstance(graphs, list) else [graphs]):
+            if g is not None:
+                check(self.lib.fx_graph_destroy(g), "fx_graph_destroy")
+
+    def __del__(self):
+        try:
+            self._destroy_graphs()
+        except Exception:
+            pass
+
+
+class _PlanBase(_GraphOwner):
     """Buffers + the static launch sequence for one (batch, height, width); helpers shared by the model families."""
 
     size_multiple = 32
@@ -666,8 +762,6 @@ class _PlanBase:
         self.meta: Dict[int, dict] = {}   # op index -> {kind, variant, flops} for bench.py
         self.bufs: Dict[str, NT] = {}
         self._win = None
-        self.graph = None
-        self.graph_thr = None
         self._thr_cell = None
         self._build()
 
@@ -942,32 +1036,27 @@ class _PlanBase:
 
     def capture_and_launch(self, stream: int, thr: float):
         if self.graph is None or self.graph_thr != thr:
-            if self.graph is not None:
-                check(self.lib.fx_graph_destroy(self.graph), "fx_graph_destroy")
-                self.graph = None
-            self._launch(self.ops, stream, thr)  # warm-up (first-use initialisation must not happen under capture)
-            torch.cuda.current_stream(self.dev).synchronize()
-            check(self.lib.fx_graph_begin(C.c_void_p(stream)), "fx_graph_begin")
-            try:
-                self._launch(self.ops, stream, thr)
-            finally:
-                g = C.c_void_p()
-                rc = self.lib.fx_graph_end(C.c_void_p(stream), C.byref(g))
-            check(rc, "fx_graph_end")
-            self.graph, self.graph_thr = g, thr
+            self._destroy_graphs()
+            launch = functools.partial(self._launch, self.ops, stream, thr)
+            self.graph, self.graph_thr = self._capture(launch, [(stream, launch)])[0], thr
         check(self.lib.fx_graph_launch(self.graph, C.c_void_p(stream)), "fx_graph_launch")
+
+    def _run_forced(self, stream: int, thr: float, forced):
+        """Teacher forcing (parity tests): launch ``ops`` eagerly and overwrite a data-dependent choice with ``forced`` on the way."""
+        raise _lib.FocoosAmdError(f"{type(self).__name__} has no teacher forcing")
+
+    def run(self, stream: int, thr: float, forced=None, use_graph: bool = True):
+        if forced is not None:
+            self._run_forced(stream, thr, forced)
+        elif not use_graph:
+            self._launch(self.ops, stream, thr)
+        else:
+            self.capture_and_launch(stream, thr)
 
     def time_graph(self, stream: int, iters: int) -> float:
         ms = C.c_float(0)
         check(self.lib.fx_graph_time(self.graph, C.c_void_p(stream), iters, C.byref(ms)), "fx_graph_time")
         return ms.value
-
-    def __del__(self):
-        try:
-            if self.graph is not None:
-                self.lib.fx_graph_destroy(self.graph)
-        except Exception:
-            pass
 
 
 class _Plan(StdcPlanMixin, _PlanBase):
@@ -1263,16 +1352,13 @@ class _Plan(StdcPlanMixin, _PlanBase):
             return args[:8] + (C.c_float(thr),) + args[9:]
         return args
 
-    def run(self, stream: int, thr: float, forced_topk: Optional[torch.Tensor] = None, use_graph: bool = True):
-        if forced_topk is not None:
-            self._launch(self.ops[: self.split_at], stream, thr)
-            self.enc_topk.copy_(forced_topk.to(device=self.dev, dtype=torch.int32))
-            self._launch(self.ops[self.split_at:], stream, thr)
-            return
-        if not use_graph:
-            self._launch(self.ops, stream, thr)
-            return
-        self.capture_and_launch(stream, thr)
+    def _run_forced(self, stream: int, thr: float, forced_topk: torch.Tensor):
+        self._launch(self.ops[: self.split_at], stream, thr)
+        self.enc_topk.copy_(forced_topk.to(device=self.dev, dtype=torch.int32))
+        self._launch(self.ops[self.split_at:], stream, thr)
+
+
+DetrEngine.plan_cls = _Plan
 
 
 class _Pipeline:
@@ -1318,11 +1404,7 @@ class _Pipeline:
         pl, st = self.lanes[t % self.depth]
         st.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(st):
-            pl.input.copy_(images, non_blocking=True)
-            if sizes is None:
-                pl.sizes.copy_(torch.tensor([[self.H, self.W]] * self.B, dtype=torch.int32), non_blocking=False)
-            else:
-                pl.sizes.copy_(sizes, non_blocking=True)
+            _copy_in(pl, images, sizes)
             pl.run(st.cuda_stream, threshold if threshold is not None else self.eng.threshold, None, True)
             if host is not None:
                 for k, h in host.items():
@@ -1344,7 +1426,7 @@ class _Pipeline:
             st.synchronize()
 
 
-class _MultiPlan:
+class _MultiPlan(_GraphOwner):
     """One step = `n` batch parts (default 2, FX_STREAMS), each a complete plan of B/n images with its own activation buffers, replayed
     concurrently on `n` streams so that an HBM-bound layer of one part overlaps an MFMA-bound layer of another and fills its tail
     wave: RT-DETR bs=32 3281 -> 3580 img/s.  Round 1 measured this and REJECTED it for correctness (30 of 40 replays had wrong decoder
@@ -1364,8 +1446,6 @@ class _MultiPlan:
         self.side = [_device_stream(self.dev, 1 + i + stream_offset) for i in range(n - 1)]
         if os.environ.get("FX_PARTS_SERIAL") == "1":   # profiling aid: the same parts back to back on ONE stream (per-kernel durations without overlap)
             self.side = [eng.stream] * (n - 1)
-        self.graph = None
-        self.graph_thr = None
         # bench.py's per-op view: the parts' launch lists back to back
         self.ops = [op for p in self.parts for op in p.ops]
         self.meta = {}
@@ -1399,9 +1479,7 @@ class _MultiPlan:
         if forced is not None:
             raise _lib.FocoosAmdError("teacher forcing runs on a single-part plan (plan(..., nsplit=1))")
         if not use_graph:
-            for p in self.parts:
-                p._launch(p.ops, stream, thr)
-            return
+            return self._launch_parts(stream, thr)
         mode = os.environ.get("FX_MULTI_MODE", "graphs")
         if mode == "branches":
             return self._run_branches(stream, thr)
@@ -1410,24 +1488,11 @@ class _MultiPlan:
         # occasionally lets a small decoder kernel read stale data: 1 image in 32 differed in 1 of 4 replays.  Per-stream
         # linear graphs use the ordinary in-queue ordering and were bit-stable over hundreds of replays.)
         if self.graph is None or self.graph_thr != thr:
-            for g in (self.graph or []):
-                check(self.lib.fx_graph_destroy(g), "fx_graph_destroy")
-            self.graph = None
-            graphs = []
+            self._destroy_graphs()
             streams = [stream] + [s.cuda_stream for s in self.side]
-            for p in self.parts:  # warm-up outside capture
-                p._launch(p.ops, stream, thr)
-            torch.cuda.current_stream(self.dev).synchronize()
-            for p, st in zip(self.parts, streams):
-                check(self.lib.fx_graph_begin(C.c_void_p(st)), "fx_graph_begin")
-                try:
-                    p._launch(p.ops, st, thr)
-                finally:
-                    g = C.c_void_p()
-                    rc = self.lib.fx_graph_end(C.c_void_p(st), C.byref(g))
-                check(rc, "fx_graph_end")
-                graphs.append(g)
-            self.graph, self.graph_thr = graphs, thr
+            # (all parts warm up on the caller's stream, outside capture; then each is captured on its own stream)
+            bodies = [(st, functools.partial(p._launch, p.ops, st, thr)) for p, st in zip(self.parts, streams)]
+            self.graph, self.graph_thr = self._capture(functools.partial(self._launch_parts, stream, thr), bodies), thr
         for s in self.side:
             check(self.lib.fx_stream_fork(C.c_void_p(stream), C.c_void_p(s.cuda_stream)), "fx_stream_fork")
         check(self.lib.fx_graph_launch(self.graph[0], C.c_void_p(stream)), "fx_graph_launch")
@@ -1436,16 +1501,15 @@ class _MultiPlan:
         for s in self.side:
             check(self.lib.fx_stream_join(C.c_void_p(stream), C.c_void_p(s.cuda_stream)), "fx_stream_join")
 
+    def _launch_parts(self, stream: int, thr: float):
+        for p in self.parts:
+            p._launch(p.ops, stream, thr)
+
     def _run_branches(self, stream: int, thr: float):
         if self.graph is None or self.graph_thr != thr:
-            if self.graph is not None:
-                check(self.lib.fx_graph_destroy(self.graph), "fx_graph_destroy")
-                self.graph = None
-            for p in self.parts:  # warm-up (first-use initialisation must not happen under capture)
-                p._launch(p.ops, stream, thr)
-            torch.cuda.current_stream(self.dev).synchronize()
-            check(self.lib.fx_graph_begin(C.c_void_p(stream)), "fx_graph_begin")
-            try:
+            self._destroy_graphs()
+
+            def branches():
                 for s in self.side:
                     check(self.lib.fx_stream_fork(C.c_void_p(stream), C.c_void_p(s.cuda_stream)), "fx_stream_fork")
                 self.parts[0]._launch(self.parts[0].ops, stream, thr)
@@ -1453,17 +1517,6 @@ class _MultiPlan:
                     p._launch(p.ops, s.cuda_stream, thr)
                 for s in self.side:
                     check(self.lib.fx_stream_join(C.c_void_p(stream), C.c_void_p(s.cuda_stream)), "fx_stream_join")
-            finally:
-                g = C.c_void_p()
-                rc = self.lib.fx_graph_end(C.c_void_p(stream), C.byref(g))
-            check(rc, "fx_graph_end")
-            self.graph, self.graph_thr = g, thr
-        check(self.lib.fx_graph_launch(self.graph, C.c_void_p(stream)), "fx_graph_launch")
 
-    def __del__(self):
-        try:
-            for g in (self.graph if isinstance(self.graph, list) else [self.graph]):
-                if g is not None:
-                    self.lib.fx_graph_destroy(g)
-        except Exception:
-            pass
+            self.graph, self.graph_thr = self._capture(functools.partial(self._launch_parts, stream, thr), [(stream, branches)])[0], thr
+        check(self.lib.fx_graph_launch(self.graph, C.c_void_p(stream)), "fx_graph_launch")

@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import _lib
-from .engine import DEFAULT_STREAMS, MIN_PART_BATCH, NT, PackedConv, _EngineBase, _MultiPlan, _PlanBase
+from .engine import NT, PackedConv, _EngineBase, _PlanBase
 from .engine_maskdec import MaskDecoderPlanMixin, pack_masked_decoder, pos_embed_sine_normalized
 from .engine_stdc import StdcEngineMixin, StdcPlanMixin, _bn_scale_shift
 
@@ -32,6 +32,8 @@ FX_ACT_SIGMOID = 4
 
 
 class BfEngine(StdcEngineMixin, _EngineBase):
+    plan_options = ("full_masks",)
+
     def __init__(self, config: Dict, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0", full_masks: bool = False):
         super().__init__(config, device)
         bb = config["backbone_config"]
@@ -62,10 +64,6 @@ class BfEngine(StdcEngineMixin, _EngineBase):
     _pos_embed_sine_normalized = staticmethod(pos_embed_sine_normalized)
 
     # ------------------------------------------------------------------ weight packing
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        self._pack_all(self._begin_load(sd))
-        self._end_load()
-
     def _pack_all(self, sd: Dict[str, torch.Tensor]) -> None:
         """The packing sequence, for host tensors (load_state_dict) and device tensors (publish_state_dict) alike."""
         P: Dict[str, PackedConv] = {}
@@ -101,50 +99,18 @@ class BfEngine(StdcEngineMixin, _EngineBase):
 
     # ------------------------------------------------------------------ run
     def plan(self, B: int, H: int, W: int, f32_input: bool = False, full_masks: Optional[bool] = None, nsplit: Optional[int] = None):
-        full = self.full_masks if full_masks is None else bool(full_masks)
-        if nsplit is None:
-            nsplit = int(os.environ.get("FX_STREAMS", str(DEFAULT_STREAMS)))
-        if nsplit > 1 and not _lib.two_queue_safe():
-            nsplit = 1
-        while nsplit > 1 and (B % nsplit or B // nsplit < MIN_PART_BATCH):
-            nsplit -= 1
-        key = (B, H, W, f32_input, full, nsplit)
-        if key not in self.plans:
-            self.plans[key] = (_BfPlan(self, B, H, W, f32_input, full) if nsplit <= 1
-                               else _MultiPlan(self, _BfPlan, B, H, W, f32_input, nsplit, full_masks=full))
-        return self.plans[key]
+        return self._plan(B, H, W, f32_input, nsplit, full_masks=full_masks)
 
     def pipeline(self, B: int, H: int, W: int, depth: Optional[int] = None, f32_input: bool = False, nsplit: int = 1, full_masks: Optional[bool] = None):
         """Throughput mode: `depth` batches in flight, each on its own whole-batch plan and stream (engine._Pipeline; see DetrEngine.pipeline)."""
-        from .engine import DEFAULT_PIPELINE_DEPTH, _Pipeline
-
-        full = self.full_masks if full_masks is None else bool(full_masks)
-        if depth is None:
-            depth = int(os.environ.get("FX_PIPELINE_DEPTH", str(DEFAULT_PIPELINE_DEPTH)))
-        if not _lib.two_queue_safe():
-            depth, nsplit = 1, 1
-        key = ("pipeline", B, H, W, f32_input, full, nsplit, depth)
-        if key not in self.plans:
-            self.plans[key] = _Pipeline(self, _BfPlan, B, H, W, f32_input, depth, nsplit, full_masks=full)
-        return self.plans[key]
+        return self._pipeline(B, H, W, depth, f32_input, nsplit, full_masks=full_masks)
 
     def forward(self, images: torch.Tensor, threshold: Optional[float] = None, forced_attn: Optional[Sequence[torch.Tensor]] = None,
                 use_graph: bool = True, full_masks: Optional[bool] = None) -> "_BfPlan":
         """images: uint8 [B,H,W,3] (fused normalise path) or float32 [B,H,W,3] (0..255 scale) on the engine device; the model runs
         at the image size (BisenetFormerProcessor.preprocess does not resize, bisenetformer/processor.py:91-93).  Returns the plan
         whose output buffers (probs, mask_probs, [masks], winner, det_*) hold the results until the next call."""
-        assert images.dim() == 4 and images.shape[-1] == 3 and images.is_contiguous() and images.device == self.dev
-        f32 = images.dtype == torch.float32
-        assert f32 or images.dtype == torch.uint8
-        B, H, W, _ = images.shape
-        pl = self.plan(B, H, W, f32, full_masks, 1 if (forced_attn is not None or not use_graph) else None)
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            pl.input.copy_(images, non_blocking=True)
-            pl.run(self.stream.cuda_stream, threshold if threshold is not None else self.threshold, forced_attn, use_graph)
-        cur.wait_stream(self.stream)
-        return pl
+        return self._forward(images, None, threshold, forced_attn, use_graph, full_masks=full_masks)
 
 
 class _BfPlan(StdcPlanMixin, MaskDecoderPlanMixin, _PlanBase):
@@ -226,3 +192,6 @@ class _BfPlan(StdcPlanMixin, MaskDecoderPlanMixin, _PlanBase):
         # ---- masked-attention decoder over (cp32, cp16), heads, outputs and post-process (engine_maskdec.py)
         dn, emb = self.build_masked_decoder([cp32, cp16], mf, e.md_eff)
         self.build_mask_outputs(dn, emb, mf, e.md_eff, self.full_masks, predict_all_pixels=e.predict_all_pixels)
+
+
+BfEngine.plan_cls = _BfPlan

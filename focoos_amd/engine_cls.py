@@ -14,7 +14,6 @@ the pooled vector are fx_pooled_linear_f32 (f32 weights); Dropout is the identit
 csrc/stdc_nano.hip, everything else on the kernels the other STDC families use."""
 from __future__ import annotations
 
-import os
 from typing import Dict, Optional
 
 import torch
@@ -28,6 +27,8 @@ FX_ACT_NONE, FX_ACT_RELU = 0, 1
 
 
 class ClsEngine(StdcEngineMixin, _EngineBase):
+    split_batch = False
+
     def __init__(self, config: Dict, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0"):
         bb = config.get("backbone_config") or {}
         nl = int(config.get("num_layers", 1))
@@ -55,8 +56,8 @@ class ClsEngine(StdcEngineMixin, _EngineBase):
     def feature_channels(self) -> int:
         return {2: 1, 3: 4, 4: 8, 5: 16}[self.last_stage] * self.base   # STDC out_feature_channels (stdc.py:240-245)
 
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        sd = {k: v.detach().cpu() for k, v in sd.items()}
+    def _pack_all(self, sd: Dict[str, torch.Tensor]) -> None:
+        """The packing sequence, for host tensors (load_state_dict) and device tensors (publish_state_dict) alike."""
         P: Dict[str, PackedConv] = {}
         self.vec: Dict[str, torch.Tensor] = {}
         self._pack_stdc(sd, P, prefix=BACKBONE, last_stage=self.last_stage)
@@ -69,42 +70,18 @@ class ClsEngine(StdcEngineMixin, _EngineBase):
         if self.head[0][0].shape[1] != self.feature_channels():
             raise _lib.FocoosAmdError(f"head input {self.head[0][0].shape[1]} != {self.feature_channels()} channels of {self.cfg.get('features')}")
         self.P = P
-        self.plans.clear()
 
     def plan(self, B: int, H: int, W: int, f32_input: bool = False) -> "_ClsPlan":
-        key = (B, H, W, f32_input)
-        if key not in self.plans:
-            self.plans[key] = _ClsPlan(self, B, H, W, f32_input)
-        return self.plans[key]
+        return self._plan(B, H, W, f32_input, 1)
 
     def pipeline(self, B: int, H: int, W: int, depth: Optional[int] = None, f32_input: bool = False):
         """Throughput mode: `depth` batches in flight, each on its own whole-batch plan and stream (engine._Pipeline)."""
-        from .engine import DEFAULT_PIPELINE_DEPTH, _Pipeline
-
-        if depth is None:
-            depth = int(os.environ.get("FX_PIPELINE_DEPTH", str(DEFAULT_PIPELINE_DEPTH)))
-        if not _lib.two_queue_safe():
-            depth = 1
-        key = ("pipeline", B, H, W, f32_input, depth)
-        if key not in self.plans:
-            self.plans[key] = _Pipeline(self, _ClsPlan, B, H, W, f32_input, depth)
-        return self.plans[key]
+        return self._pipeline(B, H, W, depth, f32_input, 1)
 
     def forward(self, images: torch.Tensor, use_graph: bool = True) -> "_ClsPlan":
         """images: uint8 [B,H,W,3] or float32 [B,H,W,3] (0..255 scale) on the engine device, at the size the model runs at (the
         processor resizes to im_size).  Returns the plan; ``plan.logits`` (f32 [B, num_classes]) holds the result until the next call."""
-        assert images.dim() == 4 and images.shape[-1] == 3 and images.is_contiguous() and images.device == self.dev
-        f32 = images.dtype == torch.float32
-        assert f32 or images.dtype == torch.uint8
-        B, H, W, _ = images.shape
-        pl = self.plan(B, H, W, f32)
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            pl.input.copy_(images, non_blocking=True)
-            pl.run(self.stream.cuda_stream, self.threshold, None, use_graph)
-        cur.wait_stream(self.stream)
-        return pl
+        return self._forward(images, None, None, None, use_graph)
 
 
 class _ClsPlan(StdcPlanMixin, _PlanBase):
@@ -127,8 +104,5 @@ class _ClsPlan(StdcPlanMixin, _PlanBase):
             v = out
         self.logits = v
 
-    def run(self, stream: int, thr: float, forced=None, use_graph: bool = True):
-        if not use_graph:
-            self._launch(self.ops, stream, thr)
-            return
-        self.capture_and_launch(stream, thr)
+
+ClsEngine.plan_cls = _ClsPlan

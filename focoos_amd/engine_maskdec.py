@@ -394,19 +394,13 @@ class MaskDecoderPlanMixin:
             return args[:9] + (C.c_float(thr),) + args[10:]
         return args
 
-    def run(self, stream: int, thr: float, forced_attn: Optional[Sequence[torch.Tensor]] = None, use_graph: bool = True):
-        if forced_attn is not None:
-            # teacher-forced attention masks (parity tests): overwrite each layer's bitmap right after it is produced
-            assert len(forced_attn) == len(self.force_points)
-            prev = 0
-            for i, (pt, m) in enumerate(zip(self.force_points, forced_attn)):
-                self._launch(self.ops[prev:pt], stream, thr)
-                bits = pack_mask_bits(m.reshape(self.B * self.eng.nq, -1), self.attn_bits[i].shape[1])
-                self.attn_bits[i].copy_(bits.to(self.dev))
-                prev = pt
-            self._launch(self.ops[prev:], stream, thr)
-            return
-        if not use_graph:
-            self._launch(self.ops, stream, thr)
-            return
-        self.capture_and_launch(stream, thr)
+    def _run_forced(self, stream: int, thr: float, forced_attn: Sequence[torch.Tensor]):
+        # teacher-forced attention masks (parity tests): overwrite each layer's bitmap right after it is produced
+        assert len(forced_attn) == len(self.force_points)
+        prev = 0
+        for i, (pt, m) in enumerate(zip(self.force_points, forced_attn)):
+            self._launch(self.ops[prev:pt], stream, thr)
+            bits = pack_mask_bits(m.reshape(self.B * self.eng.nq, -1), self.attn_bits[i].shape[1])
+            self.attn_bits[i].copy_(bits.to(self.dev))
+            prev = pt
+        self._launch(self.ops[prev:], stream, thr)

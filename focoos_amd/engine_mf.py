@@ -32,12 +32,14 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .engine import DEFAULT_STREAMS, MIN_PART_BATCH, NT, PackedConv, _EngineBase, _MultiPlan, _PlanBase
+from .engine import NT, PackedConv, _EngineBase, _PlanBase
 from .engine_stdc import StdcEngineMixin, StdcPlanMixin
 from .engine_maskdec import MaskDecoderPlanMixin, pack_mask_bits, pack_masked_decoder, pos_embed_sine_normalized  # noqa: F401  (pack_mask_bits re-exported)
 
 
 class MfEngine(StdcEngineMixin, _EngineBase):
+    plan_options = ("full_masks",)
+
     def __init__(self, config: Dict, state_dict: Dict[str, torch.Tensor], device: str = "cuda:0", full_masks: bool = False):
         super().__init__(config, device)
         # backbone: ResNet-vd (fai-mf-l-*) or STDC (fai-mf-m-ade; engine_stdc.py)
@@ -72,10 +74,6 @@ class MfEngine(StdcEngineMixin, _EngineBase):
         self.load_state_dict(state_dict)
 
     # ------------------------------------------------------------------ weight packing
-    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
-        self._pack_all(self._begin_load(sd))
-        self._end_load()
-
     def _pack_all(self, sd: Dict[str, torch.Tensor]) -> None:
         """The packing sequence, for host tensors (load_state_dict) and device tensors (publish_state_dict) alike."""
         P: Dict[str, PackedConv] = {}
@@ -152,50 +150,18 @@ class MfEngine(StdcEngineMixin, _EngineBase):
 
     # ------------------------------------------------------------------ run
     def plan(self, B: int, H: int, W: int, f32_input: bool = False, full_masks: Optional[bool] = None, nsplit: Optional[int] = None):
-        full = self.full_masks if full_masks is None else bool(full_masks)
-        if nsplit is None:
-            nsplit = int(os.environ.get("FX_STREAMS", str(DEFAULT_STREAMS)))
-        if nsplit > 1 and not _lib.two_queue_safe():
-            nsplit = 1
-        while nsplit > 1 and (B % nsplit or B // nsplit < MIN_PART_BATCH):
-            nsplit -= 1
-        key = (B, H, W, f32_input, full, nsplit)
-        if key not in self.plans:
-            self.plans[key] = (_MfPlan(self, B, H, W, f32_input, full) if nsplit <= 1
-                               else _MultiPlan(self, _MfPlan, B, H, W, f32_input, nsplit, full_masks=full))
-        return self.plans[key]
+        return self._plan(B, H, W, f32_input, nsplit, full_masks=full_masks)
 
     def pipeline(self, B: int, H: int, W: int, depth: Optional[int] = None, f32_input: bool = False, nsplit: int = 1, full_masks: Optional[bool] = None):
         """Throughput mode: `depth` batches in flight, each on its own whole-batch plan and stream (engine._Pipeline; see DetrEngine.pipeline)."""
-        from .engine import DEFAULT_PIPELINE_DEPTH, _Pipeline
-
-        full = self.full_masks if full_masks is None else bool(full_masks)
-        if depth is None:
-            depth = int(os.environ.get("FX_PIPELINE_DEPTH", str(DEFAULT_PIPELINE_DEPTH)))
-        if not _lib.two_queue_safe():
-            depth, nsplit = 1, 1
-        key = ("pipeline", B, H, W, f32_input, full, nsplit, depth)
-        if key not in self.plans:
-            self.plans[key] = _Pipeline(self, _MfPlan, B, H, W, f32_input, depth, nsplit, full_masks=full)
-        return self.plans[key]
+        return self._pipeline(B, H, W, depth, f32_input, nsplit, full_masks=full_masks)
 
     def forward(self, images: torch.Tensor, threshold: Optional[float] = None, forced_attn: Optional[Sequence[torch.Tensor]] = None,
                 use_graph: bool = True, full_masks: Optional[bool] = None) -> "_MfPlan":
         """images: uint8 [B,H,W,3] (fused normalise path) or float32 [B,H,W,3] (0..255 scale) on the engine device; the
         model runs at the image size (MaskFormerProcessor.preprocess does not resize, fai_mf/processor.py:96).  Returns the
         plan whose output buffers (probs, mask_probs, [masks], det_*) hold the results until the next call."""
-        assert images.dim() == 4 and images.shape[-1] == 3 and images.is_contiguous() and images.device == self.dev
-        f32 = images.dtype == torch.float32
-        assert f32 or images.dtype == torch.uint8
-        B, H, W, _ = images.shape
-        pl = self.plan(B, H, W, f32, full_masks, 1 if (forced_attn is not None or not use_graph) else None)
-        cur = torch.cuda.current_stream(self.dev)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            pl.input.copy_(images, non_blocking=True)
-            pl.run(self.stream.cuda_stream, threshold if threshold is not None else self.threshold, forced_attn, use_graph)
-        cur.wait_stream(self.stream)
-        return pl
+        return self._forward(images, None, threshold, forced_attn, use_graph, full_masks=full_masks)
 
 
 class _MfPlan(StdcPlanMixin, MaskDecoderPlanMixin, _PlanBase):
@@ -250,3 +216,5 @@ class _MfPlan(StdcPlanMixin, MaskDecoderPlanMixin, _PlanBase):
         dn, emb = self.build_masked_decoder(msf, mf, e.md)
         self.build_mask_outputs(dn, emb, mf, e.md, self.full_masks, predict_all_pixels=e.predict_all_pixels)
 
+
+MfEngine.plan_cls = _MfPlan

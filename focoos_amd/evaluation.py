@@ -256,8 +256,7 @@ def accumulate(focoos_model, data_test, indices: Sequence[int], task: str, ignor
     eng = model.engine
     dev = model.device
     K = model.num_classes
-    before = set(eng.plans.keys())
-    try:
+    with eng.scoped_plans():
         if task == "semseg":
             conf = torch.zeros((K + 1) * (K + 1), dtype=torch.int64, device=dev)
             status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -281,10 +280,6 @@ def accumulate(focoos_model, data_test, indices: Sequence[int], task: str, ignor
             counts[1] += ((1 - true) * pred).sum(0)
             counts[2] += (true * (1 - pred)).sum(0)
         return counts
-    finally:
-        torch.cuda.synchronize(dev)
-        for k in [k for k in eng.plans.keys() if k not in before and not getattr(eng, "retain_plans", False)]:
-            del eng.plans[k]
 
 
 def metrics_from(task: str, counts: torch.Tensor, names: Sequence[str]) -> "OrderedDict":

@@ -115,7 +115,7 @@ class Validator:
         self.kind, metric = evaluator_for(eval_model.family, task)
         self.tracker = BestTracker(metric, early_stop, patience)
         eng = eval_model.engine
-        self._plans_before = set(eng.plans.keys())
+        self._plans_before = set(eng.plans)
         eng.retain_plans = True      # the evaluators release the plans they create; a run keeps them from one validation to the next
         os.makedirs(folder, exist_ok=True)
         open(os.path.join(folder, METRICS_NAME), "w").close()
@@ -151,5 +151,4 @@ class Validator:
         """Whatever ended the run: the engine's plan table is what it was before it."""
         eng = self.model.engine
         eng.retain_plans = False
-        for k in [k for k in eng.plans.keys() if k not in self._plans_before]:
-            del eng.plans[k]
+        eng.drop_plans_except(self._plans_before)

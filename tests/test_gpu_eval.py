@@ -214,5 +214,28 @@ def test_classification_eval(tmp_path):
     assert json.loads((tmp_path / "cls_eval" / "metrics.json").read_text())[0]["classification/F1"] == res["F1"]
 
 
+def test_scoped_plans_releases_what_the_block_created():
+    from focoos_amd.model import ModelManager
+
+    eng = ModelManager.get("fai-cls-n-coco", device=DEV, seed=1).model.engine
+    x = torch.stack([torch.from_numpy(synth_image_structured(i, 64, 96)) for i in range(2)]).contiguous().to(DEV)
+    kept = eng.forward(x)
+    before = dict(eng.plans)
+    assert any(p is kept for p in before.values())
+    for retain in (False, True):
+        eng.retain_plans = retain
+        with eng.scoped_plans():
+            assert eng.forward(x) is kept                      # an existing plan is reused ...
+            eng.forward(x.float())                             # ... a new input dtype and the pipeline get entries of their own
+            eng.pipeline(2, 64, 96, 2)
+            assert len(eng.plans) == len(before) + 2
+        created = set(eng.plans) - set(before)
+        assert len(created) == (2 if retain else 0)
+        assert all(eng.plans[k] is p for k, p in before.items())   # what existed before is the same object afterwards
+    eng.retain_plans = False
+    eng.drop_plans_except(set(before))
+    assert set(eng.plans) == set(before) and eng.forward(x) is kept
+
+
 def test_runtime_report():
     print(f"MEASURED test_gpu_eval.py runtime so far {time.perf_counter() - T0:.1f} s")

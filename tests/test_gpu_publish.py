@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 from focoos_amd import _lib  # noqa: E402
 from focoos_amd.engine import BN_EPS, DetrEngine, PackedConv, _EngineBase, _fold_bn, publish_table  # noqa: E402
 from focoos_amd.engine_bf import BfEngine  # noqa: E402
+from focoos_amd.engine_cls import ClsEngine  # noqa: E402
 from focoos_amd.engine_mf import MfEngine  # noqa: E402
 from focoos_amd.registry import ModelRegistry  # noqa: E402
 from focoos_amd.synth import synth_image_structured, synth_state_dict  # noqa: E402
@@ -184,6 +185,8 @@ ENGINES = [
     ("fai-detr-m-coco", "fai_detr", DetrEngine, (128, 128), ("probs", "boxes")),
     ("bisenetformer-l-ade", "bisenetformer", BfEngine, (96, 128), ("probs", "mask_probs")),
     ("fai-mf-l-coco-ins", "fai_mf", MfEngine, (96, 128), ("probs", "mask_probs")),
+    ("fai-cls-n-coco", "fai_cls", ClsEngine, (64, 96), ("logits",)),   # STDC-nano: the 16-channel fragment images and their stem
+    ("fai-cls-m-coco", "fai_cls", ClsEngine, (64, 96), ("logits",)),   # STDC base 64
 ]
 
 
