@@ -90,8 +90,11 @@ extern "C" int fx_rowmax_f32(const float* x, int ldx, float* out, int rows, int 
 #define TOPK_THREADS 1024
 #define TOPK_MAXK 1024
 
+// -0.0 is keyed as +0.0: the two compare equal, so among zeros of either sign the lower index wins like among any equal values (the plain
+// image would put every +0.0 ahead of every -0.0 whatever their indices); a selected zero is therefore returned as +0.0.
 __device__ __forceinline__ uint32_t f32_key(float f) {
   uint32_t u = __float_as_uint(f);
+  u = u == 0x80000000u ? 0u : u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float key_f32(uint32_t k) {

@@ -360,6 +360,7 @@ extern "C" int fx_mha_masked_bf16(const void* q, int ldq, const void* k, int ldk
                                   fx_stream_t stream_) {
   FX_CHECK_ARG(q && k && v && out && B > 0 && Lq > 0 && Lk > 0 && heads > 0);
   FX_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0 && ldq >= heads * 32 && ldo >= heads * 32);
+  FX_CHECK_ARG(ldk >= heads * 32 && ldv >= heads * 32);  // a row of K / V shorter than the heads it holds would be read past its end
   FX_CHECK_ARG(!mask_bits || ld_mask_words >= (Lk + 31) / 32);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   dim3 grid((Lq + 127) / 128, B * heads), block(256);

@@ -490,7 +490,8 @@ typedef struct fx_rc_stage {
 int fx_row_chain(const fx_rc_stage* program_device, int n_stages, int rows, int lds_bytes, fx_stream_t stream);
 
 /* torch.topk(scores, k, dim=1) for f32 rows (modelling.py:1214; processor.py:147): for each of B rows
- * of length n writes the k largest values (descending; ties -> lower index first) and their indices. */
+ * of length n writes the k largest values (descending; ties -> lower index first) and their indices.
+ * -0.0 and +0.0 are equal values (the lower index first, like any tie); a selected zero of either sign is written as +0.0. */
 int fx_topk_rows_f32(const float* scores, int ld, int B, int n, int k, float* out_val, int32_t* out_idx, fx_stream_t stream);
 /* Same result, two-level for long rows (n > 8192: chunk top-ks on B * ceil(n / 8192) workgroups, then the top-k of the candidates; exact incl.
  * tie order); workspace: fx_topk_rows_workspace_bytes() (0: the one-level form is used). */

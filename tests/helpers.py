@@ -148,6 +148,87 @@ def gemm_ref64(x, w, bias=None, act=None, residual=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Guarded device buffers and the per-element gate of the small kernels' direct tests (tests/test_gpu_train_token_ops.py,
+# tests/test_gpu_infer_token_ops.py).  The element type is an argument: nothing here reads process state.
+GR = 2                      # guard rows before and after every buffer
+U32 = 2.0 ** -24            # unit roundoff of fp32
+_SENT = {1: 0x5A, 2: 0x5A5A, 4: 0x5A5A5A5A}
+
+
+def _bits(t):
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def eps_floor(dtype):
+    """(eps, floor) of ONE rounding to `dtype`: |x - round(x)| <= eps * |x| + floor.  The floor is where the relative statement ends:
+    2^-25 for fp16 (half the spacing of its subnormals), 2^-126 for bf16 and fp32 (fp32 intermediates below the smallest normal may be
+    flushed)."""
+    return {torch.float16: (2.0 ** -11, 2.0 ** -25), torch.bfloat16: (2.0 ** -8, 2.0 ** -126), torch.float32: (U32, 2.0 ** -126)}[dtype]
+
+
+def rnd(ref, dtype):
+    e, fl = eps_floor(dtype)
+    return e * ref.abs() + fl
+
+
+class Buf:
+    """[rows][ld] device tensor of which [rows][cols] is the logical region, between GR guard rows.  With `data` it is an input (padding
+    NaN; for integer types, which have none, the sentinel); without, an output (sentinel everywhere; `prefill` then sets the logical
+    region, for kernels that accumulate or update in place)."""
+
+    def __init__(self, rows, cols, ld, dtype, data=None, prefill=None, device="cuda:0"):
+        assert ld >= cols
+        self.rows, self.cols, self.ld = rows, cols, ld
+        self.full = torch.empty(rows + 2 * GR, ld, dtype=dtype, device=device)
+        self.sent = _SENT[self.full.element_size()]
+        if data is not None:
+            if dtype.is_floating_point:
+                self.full.fill_(float("nan"))
+            else:
+                _bits(self.full).fill_(self.sent)
+            self.full[GR:GR + rows, :cols] = data.reshape(rows, cols).to(device=device, dtype=dtype)
+        else:
+            _bits(self.full).fill_(self.sent)
+            if prefill is not None:
+                self.full[GR:GR + rows, :cols] = prefill.reshape(rows, cols).to(device=device, dtype=dtype)
+
+    @property
+    def ptr(self):
+        return self.full[GR].data_ptr()
+
+    def get(self):
+        return self.full[GR:GR + self.rows, :self.cols].cpu()
+
+    def assert_guards(self, written=None):
+        """Everything outside the logical region - or, with `written` (bool [rows]), outside those rows of it - keeps the sentinel."""
+        b = _bits(self.full).cpu().clone()
+        region = b[GR:GR + self.rows, :self.cols]
+        if written is None:
+            region.fill_(self.sent)
+        else:
+            region[written] = self.sent
+        assert bool((b == self.sent).all()), "a guard or an unwritten element changed"
+
+
+def needed_c(got, ref, mag, dtype, extra=None):
+    """Smallest c with |got - ref| <= RND(ref) (one rounding to `dtype`; or `extra`) + c * mag everywhere; inf where got is not finite."""
+    got, ref, mag = got.double(), ref.double(), mag.double()
+    assert got.shape == ref.shape == mag.shape, (got.shape, ref.shape, mag.shape)
+    assert bool(torch.isfinite(ref).all())
+    err = torch.where(torch.isfinite(got), (got - ref).abs(), torch.full_like(ref, float("inf")))
+    over = (err - (rnd(ref, dtype) if extra is None else extra)).clamp_min(0)
+    return float((over / mag.clamp_min(1e-300)).max()) if over.numel() else 0.0
+
+
+def gate(kernel, what, got, ref, mag, dtype, measured, margin, extra=None, tag=None):
+    """Print the c this output needs (EXCESS <kernel> [<tag>] <c> <what>), then assert c <= margin * measured[kernel]."""
+    c = needed_c(got, ref, mag, dtype, extra)
+    print(f"EXCESS {kernel} {tag + ' ' if tag else ''}{c:.3e} {what}")
+    assert c <= margin * measured[kernel], f"{kernel} {what}: needs c = {c:.3e}, gate {margin * measured[kernel]:.3e}"
+    return c
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Views of a production plan's buffers: a whole-batch _Plan (throughput lanes, forward(..., nsplit=1)) or a _MultiPlan of batch parts.
 def plan_part(pl, b: int):
     """(plan that computed image b, b's index inside it)."""

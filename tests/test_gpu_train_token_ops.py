@@ -30,11 +30,10 @@ pytestmark = pytest.mark.gpu
 
 from focoos_amd import _lib  # noqa: E402
 from focoos_amd._lib import FX_ACT, FocoosAmdError, check  # noqa: E402
-from tests.helpers import act64  # noqa: E402
+from tests import helpers  # noqa: E402
+from tests.helpers import U32, Buf, _bits, act64  # noqa: E402
 
 DEV = "cuda:0"
-GR = 2                      # guard rows before and after every buffer
-U32 = 2.0 ** -24            # unit roundoff of fp32
 MARGIN = 4.0
 # largest c = (|got - ref| - RND(ref)) / mag over all cases of the kernel and both element types, measured on an MI355X
 MEASURED = {
@@ -69,71 +68,12 @@ def adt():
     return _lib.act_dtype()
 
 
-def eps_floor():
-    return (2.0 ** -11, 2.0 ** -25) if adt() == torch.float16 else (2.0 ** -8, 2.0 ** -126)
-
-
 def rnd(ref):
-    e, fl = eps_floor()
-    return e * ref.abs() + fl
-
-
-def _bits(t):
-    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
-
-
-_SENT = {1: 0x5A, 2: 0x5A5A, 4: 0x5A5A5A5A}
-
-
-class Buf:
-    """[rows][ld] device tensor of which [rows][cols] is the logical region, between GR guard rows.  With `data` it is an input (padding
-    NaN); without, an output (sentinel everywhere; `prefill` then sets the logical region, for kernels that accumulate)."""
-
-    def __init__(self, rows, cols, ld, dtype, data=None, prefill=None):
-        assert ld >= cols
-        self.rows, self.cols, self.ld = rows, cols, ld
-        self.full = torch.empty(rows + 2 * GR, ld, dtype=dtype, device=DEV)
-        self.sent = _SENT[self.full.element_size()]
-        if data is not None:
-            self.full.fill_(float("nan"))
-            self.full[GR:GR + rows, :cols] = data.reshape(rows, cols).to(device=DEV, dtype=dtype)
-        else:
-            _bits(self.full).fill_(self.sent)
-            if prefill is not None:
-                self.full[GR:GR + rows, :cols] = prefill.reshape(rows, cols).to(device=DEV, dtype=dtype)
-
-    @property
-    def ptr(self):
-        return self.full[GR].data_ptr()
-
-    def get(self):
-        return self.full[GR:GR + self.rows, :self.cols].cpu()
-
-    def assert_guards(self, written=None):
-        """Everything outside the logical region - or, with `written` (bool [rows]), outside those rows of it - keeps the sentinel."""
-        b = _bits(self.full).cpu().clone()
-        region = b[GR:GR + self.rows, :self.cols]
-        if written is None:
-            region.fill_(self.sent)
-        else:
-            region[written] = self.sent
-        assert bool((b == self.sent).all()), "a guard or an unwritten element changed"
-
-
-def needed_c(got, ref, mag, extra=None):
-    """Smallest c with |got - ref| <= RND(ref) (or `extra`, for fp32 outputs) + c * mag everywhere; inf where got is not finite."""
-    got, ref, mag = got.double(), ref.double(), mag.double()
-    assert got.shape == ref.shape == mag.shape, (got.shape, ref.shape, mag.shape)
-    assert bool(torch.isfinite(ref).all())
-    err = torch.where(torch.isfinite(got), (got - ref).abs(), torch.full_like(ref, float("inf")))
-    over = (err - (rnd(ref) if extra is None else extra)).clamp_min(0)
-    return float((over / mag.clamp_min(1e-300)).max()) if over.numel() else 0.0
+    return helpers.rnd(ref, adt())
 
 
 def gate(kernel, what, got, ref, mag, extra=None):
-    c = needed_c(got, ref, mag, extra)
-    print(f"EXCESS {kernel} {_lib.compute_dtype()} {c:.3e} {what}")
-    assert c <= MARGIN * MEASURED[kernel], f"{kernel} {what}: needs c = {c:.3e}, gate {MARGIN * MEASURED[kernel]:.3e}"
+    helpers.gate(kernel, what, got, ref, mag, adt(), MEASURED, MARGIN, extra=extra, tag=_lib.compute_dtype())
 
 
 def rounded(t):
