@@ -332,6 +332,7 @@ extern "C" int fx_mha_masked_bwd_bf16(const void* q, int ldq, const void* k, int
   FX_CHECK_ARG(workspace_bytes >= fx_mha_bwd_workspace_bytes(B, Lq, Lk, heads) && ((uintptr_t)workspace % 4) == 0);
   FX_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && lddq % 8 == 0 && lddk % 8 == 0 && lddv % 8 == 0);
   FX_CHECK_ARG(ldq >= heads * 32 && ldk >= heads * 32 && ldv >= heads * 32 && lddo >= heads * 32);
+  FX_CHECK_ARG(lddq >= heads * 32 && lddk >= heads * 32 && lddv >= heads * 32);
   FX_CHECK_ARG(mask_bits == nullptr || ld_mask_words >= (Lk + 31) / 32);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   float* stats = reinterpret_cast<float*>(workspace);

@@ -452,6 +452,17 @@ static bool wgrad_dma_shape(int M, int N, int C, int KH, int KW) {
          2.0 * M * N * C * KH * KW >= 1e9 * min_gflop;
 }
 
+// Which of the wide class's layers the DMA kernel takes (ONE predicate for wgrad_launch and fx_conv2d_wgrad_variant): pointwise, or 3x3 /
+// stride 1 / pad 1 (Ho = H, Wo = W) on images of at least ceil(WD_BP / W) rows.  The 3x3 form carries a lane's (image row, column) from
+// step to step with ONE conditional subtraction of H: a step advances the row by WD_BP / W plus the column carry, so on a smaller image
+// (5 x 5: 6 + 1 rows against H = 5) the row would stay >= H, every tap would read as padding and the gradient would silently be too
+// small.  Those shapes - like stride 2 - run on the 128 x 128 kernel with the wide class's split plan.
+static bool wgrad_dma_route(int M, int Ho, int Wo, int N, int C, int KH, int KW, int stride, int pad) {
+  if (!wgrad_dma_shape(M, N, C, KH, KW)) return false;
+  if (KH == 1 && KW == 1 && stride == 1 && pad == 0) return true;
+  return KH == 3 && stride == 1 && pad == 1 && (WD_BP + Wo - 1) / Wo <= Ho;
+}
+
 extern "C" int fx_conv2d_wgrad_bias_nhwc_bf16(const void* x, int ldx, const void* dz, int lddz, float* dw, float* dbias, int B, int H, int W,
                                               int C, int Ho, int Wo, int N, int KH, int KW, int stride, int pad, fx_stream_t stream_);
 
@@ -538,7 +549,7 @@ static int wgrad_launch(const void* x, int ldx, const void* dz, int lddz, float*
   a.ld_dw = ld_dw > 0 ? ld_dw : a.Ktot;
   FX_CHECK_ARG(a.n_store <= N && a.k_store <= a.Ktot && a.ld_dw >= a.k_store);
   const bool pw = KH == 1 && KW == 1 && stride == 1 && pad == 0;
-  if (split_stride && !dbias && wgrad_dma_shape(a.M, N, C, KH, KW) && (pw || (KH == 3 && stride == 1 && pad == 1)) && ldx % 8 == 0 && a.n_store == N &&
+  if (split_stride && !dbias && wgrad_dma_route(a.M, Ho, Wo, N, C, KH, KW, stride, pad) && ldx % 8 == 0 && a.n_store == N &&
       a.k_store == a.Ktot && (int64_t)a.M + 4 * W + 8 < (1ll << 30)) {
     a.nKt = a.Ktot / 256;
     a.tiles = (N / 256) * a.nKt;
@@ -579,7 +590,7 @@ extern "C" int fx_linear_wgrad_bias_bf16(const void* x, int ldx, const void* dz,
 extern "C" int fx_conv2d_wgrad_variant(int B, int Ho, int Wo, int C, int N, int KH, int KW, int stride, int pad, char* out, int cap) {
   FX_CHECK_ARG(out && cap >= 32 && B > 0 && Ho > 0 && Wo > 0 && C > 0 && N > 0);
   const bool pw = KH == 1 && KW == 1 && stride == 1 && pad == 0;
-  const bool dma = wgrad_dma_shape(B * Ho * Wo, N, C, KH, KW) && (pw || (KH == 3 && stride == 1 && pad == 1));
+  const bool dma = wgrad_dma_route(B * Ho * Wo, Ho, Wo, N, C, KH, KW, stride, pad);
   snprintf(out, cap, "%s<%s>", dma ? "conv_wgrad_dma" : "conv_wgrad", pw ? "pw" : (dma ? "3x3" : "im2col"));
   return FX_OK;
 }

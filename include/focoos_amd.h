@@ -967,7 +967,8 @@ int fx_cast_f32_bf16(const float* x, void* y, int64_t n, fx_stream_t stream);
  * everywhere - the reference clears such mask rows, bisenetformer/modelling.py:423-426).  Replaces what autograd derives for
  * nn.MultiheadAttention's softmax(q k^T / sqrt(d)) v (focoos/nn/layers/transformer.py:83-106, 206-238, 583-601).
  * workspace: fx_mha_bwd_workspace_bytes() = 3 floats per (image, head, query): log-sum-exp, D = sum_j P_ij dP_ij, mask-in-effect.
- * `o` of the unmasked entry point is not read (kept for ABI stability). */
+ * `o` of the unmasked entry point is not read (kept for ABI stability).  All seven leading dimensions are multiples of 8 and at least
+ * heads * 32; anything else is FX_ERR_INVALID_ARGUMENT, nothing launched. */
 size_t fx_mha_bwd_workspace_bytes(int B, int Lq, int Lk, int heads);
 int fx_mha_bwd_bf16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int ldo, const void* dout, int lddo,
                     void* dq, int lddq, void* dk, int lddk, void* dv, int lddv, int B, int Lq, int Lk, int heads, void* workspace,

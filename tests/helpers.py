@@ -148,8 +148,9 @@ def gemm_ref64(x, w, bias=None, act=None, residual=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Guarded device buffers and the per-element gate of the small kernels' direct tests (tests/test_gpu_train_token_ops.py,
-# tests/test_gpu_infer_token_ops.py).  The element type is an argument: nothing here reads process state.
+# Guarded device buffers and the per-element gate of the kernels' direct tests (tests/test_gpu_train_token_ops.py,
+# tests/test_gpu_infer_token_ops.py, tests/test_gpu_train_matrix_ops.py).  The element type is an argument: nothing here reads process
+# state.  The sentinel guards STORES; an fp32 accumulation into it (1.5e16) leaves no trace - see acc_buf in test_gpu_train_matrix_ops.py.
 GR = 2                      # guard rows before and after every buffer
 U32 = 2.0 ** -24            # unit roundoff of fp32
 _SENT = {1: 0x5A, 2: 0x5A5A, 4: 0x5A5A5A5A}

@@ -3,8 +3,8 @@
 images (`synth_image(i)`) and targets (`bench.synth_train_targets`, step 0 of rank 0); configs[4]'s model and shape = bisenetformer-l-ade,
 8 images of 1024x1024, the registry's 12544 sample points.  The step goes through `TrainStep.forward_backward` = the production
 `TrainStep.step` minus all-reduce / optimizer: flat gradient views (DIRECT_GRAD), one-launch weight re-packing, production kernel routing
-(a layer's kernel is chosen by M = B*H*W, so the small-batch tests never exercise `conv_wgrad_dma`, the k-plane input-gradient kernels or
-the wide pointwise forms), weight gradients on the side stream, `FX_ENC_SELECT_ROWS=1`.
+(a layer's kernel is chosen by M = B*H*W, so the small-batch model tests never exercise `conv_wgrad_dma` - tests/test_gpu_train_matrix_ops.py
+calls it directly -, the k-plane input-gradient kernels or the wide pointwise forms), weight gradients on the side stream, `FX_ENC_SELECT_ROWS=1`.
 
 What is compared (as in tests/test_gpu_train_detr.py / test_gpu_train_bf.py, same gates): the CPU fp32 training oracle
 (oracle/train_oracle.py, pinned live against the real reference in train mode) free-running; its discrete choices - encoder top-k /
