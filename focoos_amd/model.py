@@ -282,13 +282,20 @@ class FocoosModel:
     def device(self):
         return self.model.device
 
-    def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate: bool = False, tracker=None) -> List[FocoosDetections]:
+    def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate: bool = False, tracker=None,
+                    mask_format: str = "png") -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
         reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``annotate``: every result
         also carries ``.image``, the uint8 input at its original size with the detections drawn on it on the device (annotate.py);
         non-uint8 inputs then raise ValueError.  ``tracker``: a ``tracking.DeviceTracker`` of ``len(inputs)`` streams, for callers who
         feed one batch per call - image b is the next frame of stream b, and every tracked detection gets its ``track_id`` (the
-        detections themselves are those of ``tracker=None``)."""
+        detections themselves are those of ``tracker=None``).  ``mask_format``: how the mask families hand out their masks - "png" (the
+        reference's base64 PNG in ``FocoosDet.mask``, the default), "rle" (``FocoosDet.rle``: the full-frame uncompressed COCO RLE, encoded on
+        the device, ``mask`` is None; mask_rle.py) or "none" (boxes, scores and labels only); anything else raises ValueError,
+        "rle" on a family without masks NotImplementedError.  ``annotate`` and ``tracker`` read the packed device results, so they compose."""
+        from .mask_rle import check_mask_format
+
+        check_mask_format(mask_format, self.model.family, "infer_batch")
         if annotate:
             from .annotate import annotate_results, check_inputs
 
@@ -314,7 +321,7 @@ class FocoosModel:
         if self.model.family == "fai_cls":
             out = self.processor.pack_detections(pl.logits.cpu(), self.model_info.classes, thr)   # the one D2H copy of the batch's logits
         elif self.model.family in ("fai_mf", "bisenetformer"):
-            out = self.processor.pack_detections(pl, self.model_info.classes)
+            out = self.processor.pack_detections(pl, self.model_info.classes, mask_format=mask_format)
         else:
             out = self.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, self.model_info.classes)
         if ids is not None:
@@ -329,7 +336,8 @@ class FocoosModel:
                                      annotate=round(t4 - t3, 3) if annotate else None)
         return out
 
-    def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate: bool = False, track=None):
+    def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate: bool = False, track=None,
+                     mask_format: str = "png"):
         """Throughput inference (round 6): iterate over ``batches`` (each a list of images of ONE common shape after preprocessing and one
         batch size) and yield each batch's ``List[FocoosDetections]`` in order, with up to ``depth`` batches in flight on the engine's
         pipeline (engine.pipeline(): batch i+1's backbone runs beside batch i's decoder tail; default depth 3).  Same results as
@@ -342,8 +350,14 @@ class FocoosModel:
         Each batch is one more launch after its lane finished (batches finish in order) and every tracked detection carries ``track_id``;
         the detections themselves are those of ``track=None``.  The first batch fixes the batch size, another size raises ValueError;
         a family without boxes raises NotImplementedError before anything touches the GPU; births dropped for want of a free slot warn
-        once per call."""
+        once per call.
+        ``mask_format``: as in ``infer_batch``; with "rle" each batch's masks are encoded on the device after its lane finished and only the
+        counts come back (one encoder serves every lane: batches finish in order on the current stream)."""
         from collections import deque
+
+        from .mask_rle import check_mask_format
+
+        check_mask_format(mask_format, self.model.family, "infer_stream")
 
         from .annotate import annotate_results, check_inputs
         from .tracking import TrackerConfig, attach_ids, for_batch, resolve, warn_drops
@@ -363,7 +377,7 @@ class FocoosModel:
             if track is not None:      # batches finish in order, so the frames reach the tracker in order
                 ids = track.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
             if mask_family:
-                out = self.processor.pack_detections(pl, self.model_info.classes)
+                out = self.processor.pack_detections(pl, self.model_info.classes, mask_format=mask_format)
             else:
                 out = self.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, self.model_info.classes)
             if ids is not None:
@@ -435,27 +449,30 @@ class FocoosModel:
 
     def __call__(self, inputs, **kwargs) -> FocoosDetections:
         lst = inputs if isinstance(inputs, list) else [inputs]
-        return self.infer_batch(lst, threshold=kwargs.get("threshold"))[0]
+        return self.infer_batch(lst, threshold=kwargs.get("threshold"), mask_format=kwargs.get("mask_format", "png"))[0]
 
-    def infer(self, image, threshold: Optional[float] = None, annotate: bool = False) -> FocoosDetections:
+    def infer(self, image, threshold: Optional[float] = None, annotate: bool = False, mask_format: str = "png") -> FocoosDetections:
         """focoos_model.py:370-416: one picture (path, PIL image, array, tensor) -> FocoosDetections.  ``annotate``: ``.image`` is the
         picture (np.uint8 [H, W, 3] RGB, original size) with the detections drawn on it on the device (annotate.py; the input itself
-        when nothing was detected) and ``.latency.annotate`` / ``.latency.imload`` are set."""
+        when nothing was detected) and ``.latency.annotate`` / ``.latency.imload`` are set.  ``mask_format``: as in ``infer_batch``."""
+        from .mask_rle import check_mask_format
+
+        check_mask_format(mask_format, self.model.family, "infer")
         t0 = perf_counter()
         if isinstance(image, (str, os.PathLike)):
             from PIL import Image
 
             image = np.array(Image.open(image).convert("RGB"))
         if not annotate:
-            return self(image, threshold=threshold)
+            return self(image, threshold=threshold, mask_format=mask_format)
         imload = perf_counter() - t0
-        res = self.infer_batch([image], threshold=threshold, annotate=True)[0]
+        res = self.infer_batch([image], threshold=threshold, annotate=True, mask_format=mask_format)[0]
         res.latency.imload = round(imload, 3)
         return res
 
     def infer_tiled(self, image, tile: Union[None, int, Tuple[int, int]] = None, overlap: float = 0.2, threshold: Optional[float] = None,
                     merge_threshold: float = 0.5, merge_metric: str = "iou", include_full: bool = True, batch_size: Optional[int] = None,
-                    max_detections: int = 300, annotate: bool = False) -> FocoosDetections:
+                    max_detections: int = 300, annotate: bool = False, mask_format: str = "png") -> FocoosDetections:
         """Tiled RT-DETR inference of ONE large picture (an engine-native mode like ``infer_stream``; the reference has none): ``image`` (what
         ``infer`` takes) is cut into overlapping windows of ``tile`` (int or (h, w), default ``model_info.im_size``; both the window cut from
         the frame and the size the model runs at) that share at least ``overlap`` in [0, 1) of a tile with their neighbours
@@ -467,8 +484,14 @@ class FocoosModel:
         pixels, best first.  Cropping, resizing and merging run on the device (fx_tile_gather_u8_f32, fx_merge_detections_nms; tiled.py):
         the frame goes up once, one packed result comes back.  Bad arguments raise ValueError; every family but fai_detr raises
         NotImplementedError before anything touches the GPU.  ``annotate``: ``.image`` is the frame with the merged detections drawn on
-        it (the resident frame is drawn on the device and copied back beside the packed result; annotate.py)."""
+        it (the resident frame is drawn on the device and copied back beside the packed result; annotate.py).  ``mask_format``: tiled
+        inference has no masks to hand out - "rle" raises NotImplementedError, another unknown value ValueError."""
+        from .mask_rle import check_mask_format
         from .tiled import infer_tiled as _infer_tiled
+
+        if check_mask_format(mask_format, None, "infer_tiled") == "rle":
+            raise NotImplementedError(f"infer_tiled: mask_format='rle' is not built: tiled inference merges boxes only (model family "
+                                      f"{self.model.family!r})")
 
         return _infer_tiled(self, image, tile, overlap, threshold, merge_threshold, merge_metric, include_full, batch_size, max_detections,
                             annotate)

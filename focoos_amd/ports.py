@@ -72,6 +72,7 @@ class FocoosDet:
     label: Optional[str] = None
     mask: Optional[str] = None
     keypoints: Optional[List[Tuple[int, int, float]]] = None
+    rle: Optional[dict] = None   # set by mask_format="rle" (mask_rle.py): the full-frame uncompressed COCO RLE {"size": [H, W], "counts": [...]}
     track_id: Optional[int] = None   # set by infer_stream(track=...) / infer_batch(tracker=...) (tracking.py); None = untracked
 
 

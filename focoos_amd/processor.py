@@ -316,6 +316,8 @@ class MaskFormerProcessor(DETRProcessor):
 
     _postprocessing_types = ("instance", "semantic")   # fai-mf-l-coco-ins / fai-mf-l-ade (predict_all_pixels): one post-process, two branches
     _export_output_names = ("masks", "logits")
+    rle_capacity: Optional[int] = None   # counts per image of the mask_format="rle" pool; None = mask_rle.default_capacity (Q (2 W + 2))
+    _rle_encoder = None                  # the MaskRleEncoder of the last "rle" call, reused while shape, device and capacity stay
 
     def __init__(self, config: dict, image_size=None):
         super().__init__(config, None)
@@ -405,7 +407,10 @@ class MaskFormerProcessor(DETRProcessor):
 
     def postprocess(self, output, inputs: ImageInput, class_names: Sequence[str] = (), top_k: Optional[int] = None,
                     threshold: Optional[float] = None, use_mask_score: Optional[bool] = None,
-                    predict_all_pixels: Optional[bool] = None) -> List[FocoosDetections]:
+                    predict_all_pixels: Optional[bool] = None, mask_format: str = "png") -> List[FocoosDetections]:
+        from .mask_rle import check_mask_format
+
+        check_mask_format(mask_format, what="postprocess")
         threshold = threshold or self.threshold
         use_mask_score = use_mask_score or self.use_mask_score
         predict_all_pixels = predict_all_pixels or self.predict_all_pixels
@@ -429,7 +434,7 @@ class MaskFormerProcessor(DETRProcessor):
                                          int(bool(use_mask_score)), ws.data_ptr(), ws.numel(), res.det_count.data_ptr(), res.det_query.data_ptr(),
                                          res.det_scores.data_ptr(), res.det_labels.data_ptr(), res.det_boxes.data_ptr(), res.det_area.data_ptr(),
                                          res.mask_words.data_ptr(), None, stream), "fx_seg_postprocess")
-            return self.pack_detections(res, class_names)
+            return self.pack_detections(res, class_names, mask_format=mask_format)
         nb = lib.fx_mf_postprocess_workspace_bytes(B, Q, H)
         ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
         # full-resolution probabilities: the kernel's bilinear tap degenerates to the identity (scale 1)
@@ -437,7 +442,7 @@ class MaskFormerProcessor(DETRProcessor):
                                     float(threshold), int(bool(use_mask_score)), ws.data_ptr(), ws.numel(), res.det_count.data_ptr(),
                                     res.det_query.data_ptr(), res.det_scores.data_ptr(), res.det_labels.data_ptr(), res.det_boxes.data_ptr(),
                                     res.det_area.data_ptr(), res.mask_words.data_ptr(), stream), "fx_mf_postprocess")
-        return self.pack_detections(res, class_names)
+        return self.pack_detections(res, class_names, mask_format=mask_format)
 
     def export_postprocess(self, output, inputs: ImageInput, class_names: Sequence[str] = (), threshold: Optional[float] = None,
                            **kwargs) -> List[FocoosDetections]:
@@ -461,9 +466,23 @@ class MaskFormerProcessor(DETRProcessor):
         w = words.cpu().numpy().view(np.uint8)
         return np.unpackbits(w, axis=-1, bitorder="little").reshape(words.shape[0], H, -1)[..., :W].astype(bool)
 
-    def pack_detections(self, res, class_names: Sequence[str] = (), encode_masks: bool = True) -> List[FocoosDetections]:
+    def pack_detections(self, res, class_names: Sequence[str] = (), encode_masks: bool = True,
+                        mask_format: str = "png") -> List[FocoosDetections]:
         """D2H of the packed device results (counts, scores, labels, boxes, bit-packed masks of the kept detections only),
-        then the host tail of processor.py:270-303: trim to the box, PNG + base64."""
+        then the host tail of processor.py:270-303: trim to the box, PNG + base64.  ``mask_format``: "png" is that path; "rle" encodes the
+        masks as uncompressed COCO RLE on the device (mask_rle.py, DESIGN 18: ``FocoosDet.rle`` is set, ``mask`` is None, no dense mask is
+        copied or unpacked unless a slot overflowed the pool of ``self.rle_capacity`` counts per image); "none" is ``encode_masks=False``."""
+        from .mask_rle import check_mask_format, encoder_for
+
+        if check_mask_format(mask_format, what="pack_detections") == "rle":
+            enc = self._rle_encoder = encoder_for(self._rle_encoder, res, self.rle_capacity)
+            enc.encode(res)      # on the current stream, before the copies below wait for it
+            rles = enc.fetch()
+            s, l, b = res.det_scores.cpu().tolist(), res.det_labels.cpu().tolist(), res.det_boxes.cpu().tolist()
+            return [FocoosDetections(detections=[
+                FocoosDet(bbox=b[i][j], conf=s[i][j], cls_id=l[i][j], label=class_names[l[i][j]] if class_names else None, rle=r)
+                for j, r in enumerate(ri)]) for i, ri in enumerate(rles)]
+        encode_masks = encode_masks and mask_format != "none"
         n = res.det_count.cpu().tolist()
         s, l, b = res.det_scores.cpu().tolist(), res.det_labels.cpu().tolist(), res.det_boxes.cpu().tolist()
         H, W = res.mask_words.shape[2], int(getattr(res, "mask_width", res.mask_words.shape[3] * 32))
@@ -472,7 +491,7 @@ class MaskFormerProcessor(DETRProcessor):
             if ni == 0:
                 out.append(FocoosDetections(detections=[]))
                 continue
-            masks = self.unpack_masks(res.mask_words[i, :ni], H, W)
+            masks = self.unpack_masks(res.mask_words[i, :ni], H, W) if encode_masks else None      # "none": no mask leaves the device
             out.append(FocoosDetections(detections=[
                 FocoosDet(bbox=b[i][j], conf=s[i][j], cls_id=l[i][j], label=class_names[l[i][j]] if class_names else None,
                           mask=binary_mask_to_base64(trim_mask(masks[j], b[i][j])) if encode_masks else None)

@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 18
+#define FX_ABI_VERSION 19
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -390,6 +390,34 @@ int fx_track_update(const float* det_scores, const int32_t* det_labels, const in
                     int track_buffer, int min_hits, float alpha, int32_t* track_ids, fx_stream_t stream);
 int fx_track_reset(int32_t* trk_id, int32_t* trk_label, int32_t* trk_tsu, int32_t* trk_hits, float* trk_box, float* trk_vel, int32_t* next_id,
                    int32_t* status, int B, int max_tracks, int b, fx_stream_t stream);
+
+/* ---- COCO run-length encoding of the kept masks on the device (ABI 19; csrc/mask_rle.hip):
+ * FocoosModel.infer(mask_format="rle").  Input: the packed results of fx_mf_postprocess / fx_seg_postprocess - mask_words i32
+ * [B][Q][H][ceil(W / 32)] (pixel x of a row = bit x % 32 of word x / 32, bits at x >= W zero), det_count i32 [B], det_boxes i32 [B][Q][4] =
+ * the inclusive (x0, y0, x1, y1) of the set pixels of slot j; slot j of image b is a detection iff j < clamp(det_count[b], 0, Q), and the
+ * words and box of any other slot are never read.
+ *
+ * Definition.  For the mask m[y][x] of a slot let s[i] = m[i % H][i / H], 0 <= i < H W (COCO's column-major order: a run continues from the
+ * bottom of column x into the top of column x + 1) and s[-1] = 0.  A transition is an i with s[i] != s[i - 1].  With the transitions
+ * t_1 < ... < t_T the counts are t_1, t_2 - t_1, ..., H W - t_T: T + 1 numbers, zeros-run first (0 when m[0][0] is set).  The empty mask
+ * gives [H W], the full mask [0, H W]; H = 2, W = 3, m = [[0,1,1],[1,1,0]] gives [1, 4, 1].
+ *
+ * Output, all int32:
+ *  - rle_len [B][Q]: the number of counts (T + 1) of every detection, stored or not; 0 for a slot that is no detection;
+ *  - rle_off [B][Q]: the exclusive prefix sum of rle_len over the slots of the image, in slot order;
+ *  - rle_counts [B][capacity]: the counts of slot j at [b][rle_off .. rle_off + rle_len) if and only if rle_off + rle_len <= capacity.  A slot
+ *    that does not fit writes nothing (the slots before it stay stored), no other element of rle_counts is ever written, nothing is
+ *    written at or beyond capacity.
+ * The box only bounds the work: columns x0 .. x1 + 1 and rows y0 .. y1 + 1 (clamped to the frame) are visited and everything outside the box
+ * counts as zero, so a tight box and the full frame [0, 0, W - 1, H - 1] give the same result for a mask that lies inside its box.
+ * Three launches (count per column, scan per slot, emit); plain stores, no atomics: the output is a pure function of the input.
+ * workspace: fx_mask_rle_workspace_bytes(B, Q, H, W) bytes (0 for a shape outside the limits), 4-byte aligned, contents irrelevant.
+ * Limits: 1 <= B, Q <= 65535, H, W >= 1, H W < 2^31 and Q (H W + 1) < 2^31 (positions, lengths and offsets are int32), capacity >= 1.  Null
+ * or misaligned pointers, a short workspace or anything else outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched.  The same in
+ * both libraries. */
+size_t fx_mask_rle_workspace_bytes(int B, int Q, int H, int W);
+int fx_mask_rle_encode(const int32_t* mask_words, const int32_t* det_count, const int32_t* det_boxes, int B, int Q, int H, int W, int capacity,
+                       int32_t* rle_len, int32_t* rle_off, int32_t* rle_counts, void* workspace, size_t workspace_bytes, fx_stream_t stream);
 
 /* F.max_pool2d(k=3,s=2,p=1) (resnet.py:254) on NHWC bf16. */
 int fx_maxpool3x3s2_nhwc_bf16(const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, fx_stream_t stream);
