@@ -131,6 +131,8 @@ SIGNATURES = {
     "fx_track_reset": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "fx_mask_rle_workspace_bytes": [_i, _i, _i, _i],
     "fx_mask_rle_encode": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
+    "fx_mask_polygon_workspace_bytes": [_i, _i, _i, _i, _i],
+    "fx_mask_polygon_encode": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "fx_maxpool3x3s2_nhwc_bf16": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "fx_stem_conv12_u8_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "fx_stem_conv_pool_supported": [_i, _i, _i, _i],
@@ -306,7 +308,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 19  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 20  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:
@@ -338,6 +340,7 @@ def load(name: str = None) -> C.CDLL:
     lib.fx_mf_eval_masks_workspace_bytes.restype = C.c_size_t
     lib.fx_merge_detections_workspace_bytes.restype = C.c_size_t
     lib.fx_mask_rle_workspace_bytes.restype = C.c_size_t
+    lib.fx_mask_polygon_workspace_bytes.restype = C.c_size_t
     lib.fx_error_string.argtypes = [C.c_int]
     lib.fx_error_string.restype = C.c_char_p
     if lib.fx_abi_version() != FX_ABI_VERSION:

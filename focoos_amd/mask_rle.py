@@ -4,7 +4,7 @@ The mask families leave their kept masks on the device as bit-packed words.  ``M
 (csrc/mask_rle.hip; the contract is in include/focoos_amd.h) and copies back the lengths, the offsets and the used part of each image's
 pool of counts: no dense mask crosses to the host and nothing is compressed on it.  A slot whose counts did not fit the pool is encoded on
 the host from its bit words (``encode_words_numpy``), with one warning per call, so the result is always complete.  The compressed RLE
-*string* of maskApi is out of scope (``check_mask_format``), like polygons and tiled inference."""
+*string* of maskApi is out of scope (``check_mask_format``), like tiled inference; polygons are mask_polygon.py."""
 from __future__ import annotations
 
 import warnings
@@ -12,21 +12,21 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-MASK_FORMATS = ("png", "rle", "none")
+MASK_FORMATS = ("png", "rle", "polygon", "none")
 MASK_FAMILIES = ("fai_mf", "bisenetformer")
 
 
 def check_mask_format(mask_format, family: Optional[str] = None, what: str = "infer") -> str:
-    """The ``mask_format`` keyword of the inference surface: "png" (the reference's base64 PNG, the default), "rle" (``FocoosDet.rle``) or
-    "none" (boxes, scores and labels only).  ValueError for anything else, the compressed "coco_string" by name; NotImplementedError, by
-    name, for "rle" on a family without masks.  Host only: nothing is loaded or launched."""
+    """The ``mask_format`` keyword of the inference surface: "png" (the reference's base64 PNG, the default), "rle" (``FocoosDet.rle``),
+    "polygon" (``FocoosDet.polygons``, mask_polygon.py) or "none" (boxes, scores and labels only).  ValueError for anything else, the
+    compressed "coco_string" by name; NotImplementedError, by name, for "rle" or "polygon" on a family without masks.  Host only: nothing is loaded or launched."""
     if mask_format == "coco_string":
         raise ValueError(f"{what}: mask_format='coco_string' (maskApi's compressed RLE string) is not built: its codec cannot be checked "
                          "against pycocotools here, which is why detection_eval does not decode it either; use 'rle' (uncompressed counts)")
     if not isinstance(mask_format, str) or mask_format not in MASK_FORMATS:
         raise ValueError(f"{what}: mask_format = {mask_format!r} must be one of {', '.join(repr(f) for f in MASK_FORMATS)}")
-    if mask_format == "rle" and family is not None and family not in MASK_FAMILIES:
-        raise NotImplementedError(f"{what}: mask_format='rle' needs masks; model family {family!r} has none "
+    if mask_format in ("rle", "polygon") and family is not None and family not in MASK_FAMILIES:
+        raise NotImplementedError(f"{what}: mask_format={mask_format!r} needs masks; model family {family!r} has none "
                                   f"(supported: {', '.join(MASK_FAMILIES)})")
     return mask_format
 
@@ -75,17 +75,23 @@ def rle_area(rle: dict) -> int:
 
 def to_coco_results(detections, image_id, category_ids: Optional[Sequence[int]] = None) -> List[dict]:
     """The entries of a COCO results file for one image: ``detections`` (a FocoosDetections or a list of FocoosDet) -> [{"image_id",
-    "category_id", "bbox" (x, y, w, h), "score", "segmentation" (the uncompressed RLE dict; only when the detection has one)}].
+    "category_id", "bbox" (x, y, w, h), "score", "segmentation" (the uncompressed RLE dict when the detection has one; else, when it has polygons, its outer rings as COCO's list of
+    flat [x0, y0, x1, y1, ...]: a COCO polygon cannot carry a hole, so the hole rings are left out and the holes read as filled)}].
     ``category_ids[cls_id]`` maps the model's class index to the dataset's category id (identity when None).  The box of a detection with
-    an RLE is the inclusive extent of its pixels, so its width is x1 - x0 + 1."""
+    an RLE or polygons is the inclusive extent of its pixels, so its width is x1 - x0 + 1."""
     out = []
     for d in getattr(detections, "detections", detections):
         x0, y0, x1, y1 = (d.bbox if d.bbox is not None else (0, 0, 0, 0))
-        inc = 1 if d.rle is not None else 0
+        polygons = getattr(d, "polygons", None)
+        inc = 1 if (d.rle is not None or polygons is not None) else 0
         e = {"image_id": image_id, "category_id": int(category_ids[d.cls_id]) if category_ids is not None else int(d.cls_id),
              "bbox": [x0, y0, x1 - x0 + inc, y1 - y0 + inc], "score": float(d.conf)}
         if d.rle is not None:
             e["segmentation"] = {"size": list(d.rle["size"]), "counts": list(d.rle["counts"])}
+        elif polygons is not None:
+            from .mask_polygon import outer_rings
+
+            e["segmentation"] = outer_rings(polygons)
         out.append(e)
     return out
 

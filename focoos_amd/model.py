@@ -291,8 +291,10 @@ class FocoosModel:
         feed one batch per call - image b is the next frame of stream b, and every tracked detection gets its ``track_id`` (the
         detections themselves are those of ``tracker=None``).  ``mask_format``: how the mask families hand out their masks - "png" (the
         reference's base64 PNG in ``FocoosDet.mask``, the default), "rle" (``FocoosDet.rle``: the full-frame uncompressed COCO RLE, encoded on
-        the device, ``mask`` is None; mask_rle.py) or "none" (boxes, scores and labels only); anything else raises ValueError,
-        "rle" on a family without masks NotImplementedError.  ``annotate`` and ``tracker`` read the packed device results, so they compose."""
+        the device, ``mask`` is None; mask_rle.py), "polygon" (``FocoosDet.polygons``: every ring of the mask's boundary, holes too,
+        traced on the device, ``mask`` and ``rle`` are None; mask_polygon.py) or "none" (boxes, scores and labels only); anything
+        else raises ValueError, "rle" or "polygon" on a family without masks NotImplementedError.  ``annotate`` and ``tracker`` read the
+        packed device results, so they compose."""
         from .mask_rle import check_mask_format
 
         check_mask_format(mask_format, self.model.family, "infer_batch")
@@ -352,7 +354,7 @@ class FocoosModel:
         a family without boxes raises NotImplementedError before anything touches the GPU; births dropped for want of a free slot warn
         once per call.
         ``mask_format``: as in ``infer_batch``; with "rle" each batch's masks are encoded on the device after its lane finished and only the
-        counts come back (one encoder serves every lane: batches finish in order on the current stream)."""
+        counts come back (one encoder serves every lane: batches finish in order on the current stream); "polygon" works the same way."""
         from collections import deque
 
         from .mask_rle import check_mask_format
@@ -485,12 +487,12 @@ class FocoosModel:
         the frame goes up once, one packed result comes back.  Bad arguments raise ValueError; every family but fai_detr raises
         NotImplementedError before anything touches the GPU.  ``annotate``: ``.image`` is the frame with the merged detections drawn on
         it (the resident frame is drawn on the device and copied back beside the packed result; annotate.py).  ``mask_format``: tiled
-        inference has no masks to hand out - "rle" raises NotImplementedError, another unknown value ValueError."""
+        inference has no masks to hand out - "rle" and "polygon" raise NotImplementedError, another unknown value ValueError."""
         from .mask_rle import check_mask_format
         from .tiled import infer_tiled as _infer_tiled
 
-        if check_mask_format(mask_format, None, "infer_tiled") == "rle":
-            raise NotImplementedError(f"infer_tiled: mask_format='rle' is not built: tiled inference merges boxes only (model family "
+        if check_mask_format(mask_format, None, "infer_tiled") in ("rle", "polygon"):
+            raise NotImplementedError(f"infer_tiled: mask_format={mask_format!r} is not built: tiled inference merges boxes only (model family "
                                       f"{self.model.family!r})")
 
         return _infer_tiled(self, image, tile, overlap, threshold, merge_threshold, merge_metric, include_full, batch_size, max_detections,

@@ -72,6 +72,8 @@ class FocoosDet:
     label: Optional[str] = None
     mask: Optional[str] = None
     keypoints: Optional[List[Tuple[int, int, float]]] = None
+    # set by mask_format="polygon" (mask_polygon.py): every ring of the mask's boundary as a flat [x0, y0, x1, y1, ...] in frame pixels, holes too
+    polygons: Optional[List[List[int]]] = None
     rle: Optional[dict] = None   # set by mask_format="rle" (mask_rle.py): the full-frame uncompressed COCO RLE {"size": [H, W], "counts": [...]}
     track_id: Optional[int] = None   # set by infer_stream(track=...) / infer_batch(tracker=...) (tracking.py); None = untracked
 

@@ -318,6 +318,9 @@ class MaskFormerProcessor(DETRProcessor):
     _export_output_names = ("masks", "logits")
     rle_capacity: Optional[int] = None   # counts per image of the mask_format="rle" pool; None = mask_rle.default_capacity (Q (2 W + 2))
     _rle_encoder = None                  # the MaskRleEncoder of the last "rle" call, reused while shape, device and capacity stay
+    polygon_capacity: Optional[int] = None   # words per image of the mask_format="polygon" pool; None = mask_polygon.default_capacity (Q (4 W + 1))
+    polygon_max_edges: Optional[int] = None  # boundary edges per image of its edge workspace; None = mask_polygon.default_max_edges (Q 2 (H + W))
+    _polygon_encoder = None                  # the MaskPolygonEncoder of the last "polygon" call, reused like _rle_encoder
 
     def __init__(self, config: dict, image_size=None):
         super().__init__(config, None)
@@ -471,7 +474,9 @@ class MaskFormerProcessor(DETRProcessor):
         """D2H of the packed device results (counts, scores, labels, boxes, bit-packed masks of the kept detections only),
         then the host tail of processor.py:270-303: trim to the box, PNG + base64.  ``mask_format``: "png" is that path; "rle" encodes the
         masks as uncompressed COCO RLE on the device (mask_rle.py, DESIGN 18: ``FocoosDet.rle`` is set, ``mask`` is None, no dense mask is
-        copied or unpacked unless a slot overflowed the pool of ``self.rle_capacity`` counts per image); "none" is ``encode_masks=False``."""
+        copied or unpacked unless a slot overflowed the pool of ``self.rle_capacity`` counts per image); "polygon" traces the masks' boundaries
+        on the device (mask_polygon.py, DESIGN 19: ``FocoosDet.polygons`` is set, ``mask`` and ``rle`` are None; ``self.polygon_capacity`` words per
+        image); "none" is ``encode_masks=False``."""
         from .mask_rle import check_mask_format, encoder_for
 
         if check_mask_format(mask_format, what="pack_detections") == "rle":
@@ -482,6 +487,16 @@ class MaskFormerProcessor(DETRProcessor):
             return [FocoosDetections(detections=[
                 FocoosDet(bbox=b[i][j], conf=s[i][j], cls_id=l[i][j], label=class_names[l[i][j]] if class_names else None, rle=r)
                 for j, r in enumerate(ri)]) for i, ri in enumerate(rles)]
+        if mask_format == "polygon":
+            from .mask_polygon import encoder_for as polygon_encoder_for
+
+            enc = self._polygon_encoder = polygon_encoder_for(self._polygon_encoder, res, self.polygon_capacity, self.polygon_max_edges)
+            enc.encode(res)      # on the current stream, before the copies below wait for it
+            polys = enc.fetch()
+            s, l, b = res.det_scores.cpu().tolist(), res.det_labels.cpu().tolist(), res.det_boxes.cpu().tolist()
+            return [FocoosDetections(detections=[
+                FocoosDet(bbox=b[i][j], conf=s[i][j], cls_id=l[i][j], label=class_names[l[i][j]] if class_names else None, polygons=r)
+                for j, r in enumerate(ri)]) for i, ri in enumerate(polys)]
         encode_masks = encode_masks and mask_format != "none"
         n = res.det_count.cpu().tolist()
         s, l, b = res.det_scores.cpu().tolist(), res.det_labels.cpu().tolist(), res.det_boxes.cpu().tolist()

@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 19
+#define FX_ABI_VERSION 20
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -418,6 +418,44 @@ int fx_track_reset(int32_t* trk_id, int32_t* trk_label, int32_t* trk_tsu, int32_
 size_t fx_mask_rle_workspace_bytes(int B, int Q, int H, int W);
 int fx_mask_rle_encode(const int32_t* mask_words, const int32_t* det_count, const int32_t* det_boxes, int B, int Q, int H, int W, int capacity,
                        int32_t* rle_len, int32_t* rle_off, int32_t* rle_counts, void* workspace, size_t workspace_bytes, fx_stream_t stream);
+
+/* ---- Boundary polygons of the kept masks on the device (ABI 20; csrc/mask_polygon.hip):
+ * FocoosModel.infer(mask_format="polygon").  Input: exactly that of fx_mask_rle_encode (mask_words, det_count, det_boxes; the words and box
+ * of a slot >= clamp(det_count[b], 0, Q) are never read).
+ *
+ * Definition.  Lattice points are integer (x, y), 0 <= x <= W, 0 <= y <= H; pixel (x, y) is the square [x, x + 1] x [y, y + 1], y grows
+ * downward, everything outside the frame is unset.  A boundary edge is a unit side between a set pixel and an unset one; it belongs to the
+ * set pixel and is directed so that the set pixel is on its right: side 0 = top, runs toward +x; 1 = right, +y; 2 = bottom, -x; 3 = left,
+ * -y.  Successor of side s of pixel p with heading d: let A = p + d (the pixel ahead) and L = the pixel to the left of A (across side s of
+ * A).  If A is unset: side (s + 1) % 4 of p (turn right); else if L is unset: side s of A (straight); else side (s + 3) % 4 of L (turn
+ * left).  Turning right first makes the foreground 4-connected: two set pixels that touch only diagonally are separate rings, a hole of two
+ * diagonal unset pixels is one ring through their shared point twice.  A ring is a cycle of the successor; its vertices are the tails of
+ * the edges whose predecessor has another side (none collinear; an even number, at least 4); it starts at the tail of its smallest top edge
+ * in (y, x) order, and the rings of a mask are ordered by that edge.  The shoelace sum over (x_i y_(i+1) - x_(i+1) y_i) is positive for an
+ * outer ring and negative for a hole; filling all rings by the even-odd rule at pixel centres gives the mask back, and half the sums add up
+ * to its popcount.  One pixel at (0, 0): [(0,0), (1,0), (1,1), (0,1)].
+ *
+ * Output, all int32.  A slot's stream is, for each ring in order, its vertex count v and then v vertices packed as x | y << 16.
+ *  - poly_len [B][Q]: the stream's true length, stored or not; 0 for an empty mask or a slot that is no detection; -1 for a slot whose
+ *    boundary edges did not fit the image's edge workspace: with E_j the boundary edges of slot j and base_j = the sum of E_i over the slots
+ *    i < j that fit, slot j fits iff base_j + E_j <= max_edges (a slot that does not fit takes nothing, so no other slot is shifted by it);
+ *  - poly_off [B][Q]: the exclusive prefix sum of max(poly_len, 0) over the slots of the image, in slot order;
+ *  - poly_pool [B][capacity]: the stream of slot j at [b][poly_off .. poly_off + poly_len) iff poly_len > 0 and poly_off + poly_len <=
+ *    capacity.  A slot that does not fit writes nothing, no other element is ever written, nothing is written at or beyond capacity.
+ * The box only bounds the work: rows y0 .. y1 and columns x0 .. x1 (clamped to the frame) are read and everything outside the box counts as
+ * unset, so a tight box and the full frame give the same result for a mask that lies inside its box.
+ * Three launches (scan of the edge counts, rank by pointer doubling, emit); every loop's trip count is fixed before it starts, no workgroup
+ * waits for another; plain stores, no atomics: the output is a pure function of the input.
+ * workspace: fx_mask_polygon_workspace_bytes(B, Q, H, W, max_edges) bytes = 4 (B Q H ceil(W / 32) + B Q + 7 B max_edges), 0 outside the
+ * limits; 4-byte aligned, contents irrelevant.
+ * Limits: 1 <= B, Q <= 65535, 1 <= H, W <= 32767 (a vertex packs into 16 + 16 bits), capacity >= 1, max_edges >= 1, and with L = 2 H W + H
+ * + W (every unit side of the lattice: the most boundary edges a mask has; a ring has at least 4 edges and no more vertices than edges, so
+ * a stream has at most L + L / 4 words) Q (L + L / 4) < 2^31: lengths and an image's offsets are int32.  Null or misaligned pointers, a
+ * short workspace or anything else outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched.  The same in both libraries. */
+size_t fx_mask_polygon_workspace_bytes(int B, int Q, int H, int W, int max_edges);
+int fx_mask_polygon_encode(const int32_t* mask_words, const int32_t* det_count, const int32_t* det_boxes, int B, int Q, int H, int W, int capacity,
+                           int max_edges, int32_t* poly_len, int32_t* poly_off, int32_t* poly_pool, void* workspace, size_t workspace_bytes,
+                           fx_stream_t stream);
 
 /* F.max_pool2d(k=3,s=2,p=1) (resnet.py:254) on NHWC bf16. */
 int fx_maxpool3x3s2_nhwc_bf16(const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, fx_stream_t stream);
