@@ -780,7 +780,8 @@ extern "C" int fx_mask_set_loss_cls_f32(const float* logits, int ldl, const floa
 // ------------------------------------------------------------------------------------------------
 // Gradients of the three losses of one prediction set (the backward of fx_mask_set_loss_f32 under upstream gradients g[0..2]):
 //   dlogits[b,q,c] = g0 * w_ce * w[y] / sum_rows w[y] * (softmax_c - [c == y])        (F.cross_entropy with class weights, mean)
-//   dmasks: see mask_point_loss_kernel<.., true>; planes of unmatched queries stay zero.
+//   dmasks: see mask_point_loss_bwd_lds_kernel / mask_point_loss_bwd_kernel above (they read the selection mask_point_loss_kernel left in
+//   the workspace); matched planes must be zero on entry, planes of unmatched queries are not touched.
 __global__ __launch_bounds__(256) void mask_label_ce_bwd_kernel(const float* __restrict__ logits, int ldl, const int32_t* __restrict__ tgt_labels,
                                                                 const int32_t* __restrict__ tgt_offsets, const int32_t* __restrict__ pred_idx,
                                                                 const int32_t* __restrict__ tgt_idx, int n_rows, int Q, int K, float eos_coef,

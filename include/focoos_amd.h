@@ -1078,18 +1078,23 @@ int fx_graph_time(void* graph_exec, fx_stream_t stream, int iters, float* ms_avg
 
 /* ---- training direction of the mask families (BASELINE config 5) ------------------------------------
  * Gradients of fx_mask_set_loss_f32 (SetCriterion.loss_labels / loss_masks under autograd, focoos/models/fai_mf/loss.py:411-431,
- * 463-523 == bisenetformer/loss.py): same arguments plus the forward's workspace (pair sums and CE weight sum are read from it),
- * grad3 f32 [3] ON THE DEVICE = upstream gradients of (loss_ce, loss_mask, loss_dice); writes dlogits f32 [B,Q,lddl] (all K+1
- * columns of every row) and ACCUMULATES into dmasks f32 [B,Q,h,w] (zero-initialised by the caller; only the planes of matched
- * queries are touched).  The point selection is recomputed (deterministic); sample coordinates carry no gradient.  pred_idx must not repeat within an image (a Hungarian matching never does): each matched
- * plane has one writer (the gradient is accumulated in LDS per plane band and stored, not added). */
+ * 463-523 == bisenetformer/loss.py): same arguments plus the workspace THAT FORWARD CALL WROTE: the pair sums, the CE weight sum, the
+ * candidate logits and the point selection are read from it, nothing is recomputed (another or a reused workspace gives another
+ * gradient).  grad3 f32 [3] ON THE DEVICE = upstream gradients of (loss_ce, loss_mask, loss_dice).  Sample coordinates carry no gradient.
+ *   dlogits f32 [B,Q,lddl]: the K+1 columns of every row are written; columns >= K+1 of a wider slab are not touched.
+ *   dmasks f32 [B,Q,h,w]: the planes of matched queries MUST BE ZERO on entry and hold the gradient on return; the planes of unmatched
+ *   queries are not touched.  What a non-zero matched plane becomes is unspecified: the default form accumulates a band of rows in LDS and
+ *   stores it, the other form (w > 16384, or FX_MPL_BWD_LDS=0) adds to the plane with atomics.
+ * pred_idx must not repeat within an image (a Hungarian matching never does): each matched plane has one writer.  The order of the fp32
+ * additions at a pixel that several points touch is not fixed: dmasks is reproducible to rounding, not to the bit. */
 int fx_mask_set_loss_bwd_f32(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H, int W,
                              const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx, const int32_t* tgt_idx,
                              const float* rand_over, int n_over, const float* rand_extra, int n_extra, int num_points, int B, int Q, int K,
                              float eos_coef, float num_masks, float w_ce, float w_mask, float w_dice, const void* workspace, size_t workspace_bytes,
                              const float* grad3, float* dlogits, int lddl, float* dmasks, fx_stream_t stream);
-/* Gradients of fx_mask_set_loss_cls_f32: as above; for the FOCAL / BCE / BCE_FOCAL modes dlogits is written as by
- * fx_mask_class_loss_bwd_f32 (all lddl columns of every row). */
+/* Gradients of fx_mask_set_loss_cls_f32: the same contract for the workspace and dmasks; FX_CLASS_LOSS_CE is the call above (K+1 columns
+ * of dlogits written), for the FOCAL / BCE / BCE_FOCAL modes dlogits is written as by fx_mask_class_loss_bwd_f32: ALL lddl columns of
+ * every row, 0 in the columns the loss does not read. */
 int fx_mask_set_loss_cls_bwd_f32(const float* logits, int ldl, const float* pred_masks, int h, int w, const void* tgt_masks, int tgt_is_u8, int H, int W,
                                  const int32_t* tgt_labels, const int32_t* tgt_offsets, int sum_T, const int32_t* pred_idx, const int32_t* tgt_idx,
                                  const float* rand_over, int n_over, const float* rand_extra, int n_extra, int num_points, int B, int Q, int K,
