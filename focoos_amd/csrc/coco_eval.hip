@@ -135,12 +135,6 @@ static __host__ __device__ inline size_t cm_need(int64_t nD, int64_t G) {
   return (size_t)(nD * G * 8 + 20 * G + 160 * ((G + 31) / 32));
 }
 
-__device__ __forceinline__ int cm_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <class Src>
 __global__ __launch_bounds__(64) void coco_match_kernel(CmArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_buf[];   // lds_bytes: sized by the host from max_gt
@@ -161,12 +155,12 @@ __global__ __launch_bounds__(64) void coco_match_kernel(CmArgs a) {
       const int k = Src::kept(a, sb + j), l = lab[j] == c;
       nk += k, nl += l, nc += (k && l);
     }
-    nk = cm_wave_sum(nk), nc = cm_wave_sum(nc), nl = cm_wave_sum(nl);
+    nk = fx_wave_sum(nk), nc = fx_wave_sum(nc), nl = fx_wave_sum(nl);
     const int64_t g0 = a.gt_off[b];
     const int64_t Gi = a.gt_off[b + 1] - g0;
     int G = 0;
     for (int64_t g = lane; g < Gi; g += 64) G += a.gt_cat[g0 + g] == c;
-    G = cm_wave_sum(G);
+    G = fx_wave_sum(G);
     if (nl == 0 && G == 0) continue;
     const bool live = nk > 0 && (nc > 0 || G > 0);   // an image without a kept detection is not evaluated at all
     const int nD = nc < CM_MAXDET ? nc : CM_MAXDET;

@@ -71,12 +71,6 @@ __global__ __launch_bounds__(SG_QMAX) void sg_prepare_kernel(SgArgs a) {
   }
 }
 
-__device__ __forceinline__ float sg_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);   // a + b == b + a: every lane ends with the same bits
-  return v;
-}
-
 __global__ __launch_bounds__(SG_THREADS) void sg_masks_kernel(SgArgs a) {
   __shared__ float s_ps[4][SG_QC];
   __shared__ int s_in[4][SG_QC][5];
@@ -118,7 +112,7 @@ __global__ __launch_bounds__(SG_THREADS) void sg_masks_kernel(SgArgs a) {
       const bool in = valid && m > a.thr;
       const unsigned long long bits = __ballot(in);
       if (lane == 0) wd[((int64_t)qs[i] * H + y) * ww + wc] = bits;
-      ps[i] += sg_wave_sum(in ? m : 0.0f);
+      ps[i] += fx_wave_sum(in ? m : 0.0f);
       if (bits) {
         cn[i] += __popcll(bits);
         const int lo = wc * 64 + (int)__ffsll((long long)bits) - 1, hi = wc * 64 + 63 - __clzll((long long)bits);
@@ -256,12 +250,6 @@ struct SiArgs {
   int Q;
 };
 
-__device__ __forceinline__ int si_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(64) void si_inter_kernel(SiArgs a) {
   const int g = blockIdx.x, qi = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
   const int64_t g0 = a.gt_off[b], Gi = a.gt_off[b + 1] - g0;
@@ -284,7 +272,7 @@ __global__ __launch_bounds__(64) void si_inter_kernel(SiArgs a) {
       sum += __popcll(D[o] & G[o]);
     }
   }
-  sum = si_wave_sum(sum);
+  sum = fx_wave_sum(sum);
   if (lane == 0) a.inter[(int64_t)a.Q * g0 + (int64_t)q * Gi + g] = sum;
 }
 
@@ -296,7 +284,7 @@ __global__ __launch_bounds__(64) void si_count_kernel(SiArgs a) {
   const unsigned long long* G = a.gt_words + a.gt_word_off[b] + (int64_t)g * H * ww;
   int sum = 0;
   for (int64_t e = lane; e < (int64_t)H * ww; e += 64) sum += __popcll(G[e]);
-  sum = si_wave_sum(sum);
+  sum = fx_wave_sum(sum);
   if (lane == 0) a.gcount[g0 + g] = sum;
 }
 

@@ -98,6 +98,25 @@ __device__ __forceinline__ uint4 pack_bf16x8(const float* f) {
 
 __device__ __forceinline__ float fx_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
+// Reductions over the 64 lanes of a wave: the xor butterfly from 32 down to 1.  a + b == b + a (max and min alike), so every lane ends
+// with the same bits.
+template <typename T>
+__device__ __forceinline__ T fx_wave_sum(T v) {   // float, double, int
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float fx_wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int fx_wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
 // activation codes: FX_ACT_*
 __device__ __forceinline__ float fx_act(float x, int act) {
   switch (act) {

@@ -36,12 +36,6 @@ extern "C" int fx_add_rows_bf16(const void* x, int ldx, const void* y, int ldy_,
 // ------------------------------------------------------------------------------------------------
 // LayerNorm over 256 channels, one wave per row (4 channels per lane), fp32 statistics
 // (two-pass mean / variance in registers, biased variance, eps inside the sqrt like nn.LayerNorm).
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void layernorm256_kernel(const bf16_t* __restrict__ x, int ldx, const bf16_t* __restrict__ res, int ldr,
                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             bf16_t* __restrict__ out, int ldo, int rows) {
@@ -58,9 +52,9 @@ __global__ __launch_bounds__(256) void layernorm256_kernel(const bf16_t* __restr
     v[2] += bf16lo_to_f32(rv.y);
     v[3] += bf16hi_to_f32(rv.y);
   }
-  float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / 256.0f);
+  float mean = fx_wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / 256.0f);
   float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
-  float var = wave_sum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.0f / 256.0f);
+  float var = fx_wave_sum(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3) * (1.0f / 256.0f);
   float rstd = rsqrtf(var + 1e-5f);
   float4 g = *reinterpret_cast<const float4*>(gamma + lane * 4), bt = *reinterpret_cast<const float4*>(beta + lane * 4);
   uint2 o;
@@ -83,9 +77,9 @@ __global__ __launch_bounds__(256) void layernorm128_kernel(const bf16_t* __restr
     v0 += bf16lo_to_f32(rv);
     v1 += bf16hi_to_f32(rv);
   }
-  const float mean = wave_sum(v0 + v1) * (1.0f / 128.0f);
+  const float mean = fx_wave_sum(v0 + v1) * (1.0f / 128.0f);
   const float d0 = v0 - mean, d1 = v1 - mean;
-  const float var = wave_sum(d0 * d0 + d1 * d1) * (1.0f / 128.0f);
+  const float var = fx_wave_sum(d0 * d0 + d1 * d1) * (1.0f / 128.0f);
   const float rstd = rsqrtf(var + 1e-5f);
   const float2 g = *reinterpret_cast<const float2*>(gamma + lane * 2), bt = *reinterpret_cast<const float2*>(beta + lane * 2);
   *reinterpret_cast<unsigned*>(out + (int64_t)row * ldo + lane * 2) = pack_bf16x2(d0 * rstd * g.x + bt.x, d1 * rstd * g.y + bt.y);

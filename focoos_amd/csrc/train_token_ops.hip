@@ -4,17 +4,6 @@
 // the cross-row parameter gradients; the decoder / AIFI tensors they touch are small (<= B*8400 rows of 256).
 #include "common.h"
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // ------------------------------------------------------------------------------------------------ activations
 __device__ __forceinline__ float act_grad(float z, int act) {
   switch (act) {
@@ -164,11 +153,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
     float sum = 0.0f;
 #pragma unroll
     for (int j = 0; j < CPL; ++j) sum += v[j];
-    const float mean = wsum(sum) * INV;
+    const float mean = fx_wave_sum(sum) * INV;
     float c[CPL], var = 0.0f;
 #pragma unroll
     for (int j = 0; j < CPL; ++j) c[j] = v[j] - mean, var += c[j] * c[j];
-    const float rstd = rsqrtf(wsum(var) * INV + 1e-5f);
+    const float rstd = rsqrtf(fx_wave_sum(var) * INV + 1e-5f);
     float xh[CPL], g[CPL], sg = 0.0f, sgx = 0.0f;
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
@@ -179,8 +168,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
       ag[j] += d[j] * xh[j];
       ab[j] += d[j];
     }
-    sg = wsum(sg) * INV;
-    sgx = wsum(sgx) * INV;
+    sg = fx_wave_sum(sg) * INV;
+    sgx = fx_wave_sum(sgx) * INV;
     if constexpr (CPL == 4) {
       uint2 o;
       o.x = pack_bf16x2(rstd * (g[0] - sg - xh[0] * sgx), rstd * (g[1] - sg - xh[1] * sgx));
@@ -346,7 +335,7 @@ __global__ __launch_bounds__(256) void vfl_loss_kernel(const bf16_t* __restrict_
     acc += w * bce;
     if (dlogits) dlogits[r * lddl + c] = f32_to_bf16(w * (p - t) * scale);
   }
-  acc = wsum(acc);
+  acc = fx_wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) unsafeAtomicAdd(loss_out, (red[0] + red[1] + red[2] + red[3]) * scale);
