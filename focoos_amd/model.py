@@ -283,7 +283,7 @@ class FocoosModel:
         return self.model.device
 
     def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate: bool = False, tracker=None,
-                    mask_format: str = "png") -> List[FocoosDetections]:
+                    mask_format: str = "png", zones=None) -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
         reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``annotate``: every result
         also carries ``.image``, the uint8 input at its original size with the detections drawn on it on the device (annotate.py);
@@ -294,10 +294,20 @@ class FocoosModel:
         the device, ``mask`` is None; mask_rle.py), "polygon" (``FocoosDet.polygons``: every ring of the mask's boundary, holes too,
         traced on the device, ``mask`` and ``rle`` are None; mask_polygon.py) or "none" (boxes, scores and labels only); anything
         else raises ValueError, "rle" or "polygon" on a family without masks NotImplementedError.  ``annotate`` and ``tracker`` read the
-        packed device results, so they compose."""
+        packed device results, so they compose.  ``zones``: a ``zones.DeviceZones`` of ``len(inputs)`` streams, the counterpart of
+        ``tracker`` for zone and line counting (zones.py): every result carries ``.zones``; a DeviceZones built on a tracker
+        runs that tracker (``tracker`` must be None or that one)."""
         from .mask_rle import check_mask_format
 
         check_mask_format(mask_format, self.model.family, "infer_batch")
+        if zones is not None:
+            from . import zones as Z
+
+            if not isinstance(zones, Z.DeviceZones):
+                Z.check_family(self.model.family, "infer_batch")
+                raise TypeError(f"infer_batch: zones must be a DeviceZones, not {type(zones).__name__}")
+            zones, tracker = Z.resolve(zones, tracker, self.model.family, "infer_batch")
+            Z.for_batch(zones, len(inputs), tracker, self.model.device, "infer_batch")
         if annotate:
             from .annotate import annotate_results, check_inputs
 
@@ -320,6 +330,8 @@ class FocoosModel:
         ids = None
         if tracker is not None:      # one launch on the packed device results; the ids come back beside the packed copy
             ids = tracker.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
+        if zones is not None:        # one more launch, right after the tracker's
+            zones.update(pl.det_labels, pl.det_boxes, pl.det_count, ids if zones.tracker is not None else None)
         if self.model.family == "fai_cls":
             out = self.processor.pack_detections(pl.logits.cpu(), self.model_info.classes, thr)   # the one D2H copy of the batch's logits
         elif self.model.family in ("fai_mf", "bisenetformer"):
@@ -329,6 +341,8 @@ class FocoosModel:
         if ids is not None:
             attach_ids(out, ids.cpu().tolist())
             warn_drops(tracker, "infer_batch")
+        if zones is not None:
+            Z.attach(out, zones.fetch())
         t3 = perf_counter()
         if annotate:
             annotate_results(self, inputs, images, pl, out)
@@ -339,7 +353,7 @@ class FocoosModel:
         return out
 
     def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate: bool = False, track=None,
-                     mask_format: str = "png"):
+                     mask_format: str = "png", zones=None, detections: bool = True):
         """Throughput inference (round 6): iterate over ``batches`` (each a list of images of ONE common shape after preprocessing and one
         batch size) and yield each batch's ``List[FocoosDetections]`` in order, with up to ``depth`` batches in flight on the engine's
         pipeline (engine.pipeline(): batch i+1's backbone runs beside batch i's decoder tail; default depth 3).  Same results as
@@ -354,17 +368,29 @@ class FocoosModel:
         a family without boxes raises NotImplementedError before anything touches the GPU; births dropped for want of a free slot warn
         once per call.
         ``mask_format``: as in ``infer_batch``; with "rle" each batch's masks are encoded on the device after its lane finished and only the
-        counts come back (one encoder serves every lane: batches finish in order on the current stream); "polygon" works the same way."""
+        counts come back (one encoder serves every lane: batches finish in order on the current stream); "polygon" works the same way.
+        ``zones``: zone and line counting on the device (zones.py) - a list of ``Zone`` / ``Line``, or a ``DeviceZones`` whose
+        state then outlives the call (built on a tracker, it runs that tracker).  One more launch per batch right after the tracker's;
+        every result carries ``.zones`` = ``{name: {"kind", "count", "detections", "entered", "exited", "crossed_in", "crossed_out"}}``:
+        this frame's occupancy and the indices into ``.detections`` of the detections inside, the running totals of the events, and the
+        indices of this frame's events.  Events need identity: a ``Line`` without ``track`` raises ValueError before anything touches the
+        GPU, zones without ``track`` count occupancy only.  The detections are those of ``zones=None``, which changes nothing.
+        ``detections=False`` (needs ``zones``; ValueError with ``annotate`` or another ``mask_format`` than the default): the analytics-only
+        mode - the detection objects are not built, every result is ``FocoosDetections(detections=[], zones=...)`` with the same zone
+        dicts."""
         from collections import deque
 
+        from . import zones as Z
         from .mask_rle import check_mask_format
 
+        Z.check_detections_flag(detections, zones, annotate, mask_format)
         check_mask_format(mask_format, self.model.family, "infer_stream")
 
         from .annotate import annotate_results, check_inputs
         from .tracking import TrackerConfig, attach_ids, for_batch, resolve, warn_drops
 
         track = resolve(track, self.model.family, self.model.device)
+        zones, track = Z.resolve(zones, track, self.model.family)
         thr = threshold or self.processor.threshold
         if self.model.family == "fai_cls":
             yield from self._infer_stream_cls(batches, thr, depth, annotate)
@@ -378,12 +404,18 @@ class FocoosModel:
             ids = None
             if track is not None:      # batches finish in order, so the frames reach the tracker in order
                 ids = track.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
-            if mask_family:
+            if zones is not None:      # one more launch, right after the tracker's, on the same packed results
+                zones.update(pl.det_labels, pl.det_boxes, pl.det_count, ids if zones.tracker is not None else None)
+            if not detections:         # analytics only: no detection objects, no ids on the host
+                out = [FocoosDetections(detections=[]) for _ in range(pipe.B)]
+            elif mask_family:
                 out = self.processor.pack_detections(pl, self.model_info.classes, mask_format=mask_format)
             else:
                 out = self.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, self.model_info.classes)
-            if ids is not None:
+            if ids is not None and detections:
                 attach_ids(out, ids.cpu().tolist())
+            if zones is not None:
+                Z.attach(out, zones.fetch())
             if annotate:      # the lane's results stay valid until the lane is submitted to again, which happens after this returns
                 annotate_results(self, *frames.pop(ticket), pl, out)
             return out
@@ -397,6 +429,8 @@ class FocoosModel:
             B, H, W, _ = x.shape
             if track is not None:
                 track = for_batch(track, B, x.device)      # created with the first batch, which fixes B
+            if zones is not None:
+                zones = Z.for_batch(zones, B, track, x.device)
             if pipe is None or (pipe.B, pipe.H, pipe.W) != (B, H, W):
                 while pending:
                     yield finish()

@@ -92,6 +92,9 @@ class FocoosDetections:
     detections: List[FocoosDet] = field(default_factory=list)
     latency: Optional[InferLatency] = None
     image: Optional[Any] = None
+    # set by infer_stream(zones=...) / infer_batch(zones=...) (zones.py): {region name: {"kind", "count", "detections", "entered", "exited",
+    # "crossed_in", "crossed_out"}}; None = no zones were asked for
+    zones: Optional[dict] = None
 
     def __len__(self):
         return len(self.detections)

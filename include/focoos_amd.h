@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 20
+#define FX_ABI_VERSION 21
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -456,6 +456,64 @@ size_t fx_mask_polygon_workspace_bytes(int B, int Q, int H, int W, int max_edges
 int fx_mask_polygon_encode(const int32_t* mask_words, const int32_t* det_count, const int32_t* det_boxes, int B, int Q, int H, int W, int capacity,
                            int max_edges, int32_t* poly_len, int32_t* poly_off, int32_t* poly_pool, void* workspace, size_t workspace_bytes,
                            fx_stream_t stream);
+
+/* ---- Zone and line counting on the device (ABI 21; csrc/zone_ops.hip): FocoosModel.infer_stream(zones=...).
+ * Input: the packed results (det_labels i32 [B][T], det_boxes i32 xyxy [B][T][4], 16-byte aligned, det_count i32 [B]; slot j of stream b is a
+ * detection iff j < clamp(det_count[b], 0, T)) and, optionally, the tracker's track_ids i32 [B][T] of this frame with its trk_id i32
+ * [B][max_tracks] after that update.  Batch index b is stream b.  Every decision is an integer one: the result is a pure function of the
+ * inputs and is compared for equality with the restatement (tests/zones_ref.py).
+ *
+ * Regions.  A region is a polygon zone (FX_ZONE_POLYGON, 3 .. FX_ZONE_MAX_VERTS vertices) or a line (FX_ZONE_LINE, 2 vertices: A, B), one
+ * fx_zone_region record: its vertices are verts[vert_first .. vert_first + vert_count) (i32 [V_total][2], (x, y) integer pixels in
+ * [-32768, 32768], 8-byte aligned), bit l % 32 of class_words[l / 32] admits label l (0 .. 255) and flags bit 0 (FX_ZONE_ANY_CLASS) admits every
+ * label; a label outside 0 .. 255 passes only with that bit.  The regions of stream b are the records reg_first[b] .. reg_first[b + 1] - 1
+ * (reg_first i32 [B + 1], reg_first[0] = 0, reg_first[B] = R_total, at most FX_ZONE_MAX_REGIONS per stream; a region shared by streams is
+ * replicated by the host); bit k of a per-detection mask is region reg_first[b] + k.  regions / reg_first / verts are device buffers;
+ * regions_host / reg_first_host / verts_host are host copies of the same bytes, which the library validates before it launches.
+ *
+ * Anchor.  A box coordinate is clamped to [0, 16384] when it is read.  The anchor P of a detection is taken in DOUBLED coordinates, so centres
+ * stay integers: P.x = {2 x0, x0 + x1, 2 x1}[anchor % 3], P.y = {2 y0, y0 + y1, 2 y1}[anchor / 3], anchor 0 .. 8 (7 = bottom centre).  Region
+ * vertices are doubled the same way; every product below is int64 (operands below 2^19).
+ * Zone test, even-odd, exact: a directed edge A -> B (B the next vertex, the last one closes onto the first) is counted when
+ * (A.y > P.y) != (B.y > P.y) and d = (B.x - A.x) (P.y - A.y) - (P.x - A.x) (B.y - A.y) has the sign of B.y - A.y (d > 0 when B.y > A.y, d < 0
+ * otherwise); inside = an odd count.  An axis-aligned rectangle is half-open: left and top edges inside, right and bottom edges outside.
+ * Line test: s = sign((B.x - A.x) (P.y - A.y) - (B.y - A.y) (P.x - A.x)), within = 0 <= dot(P - A, B - A) <= dot(B - A, B - A).
+ * A detection takes part in a region when its label passes.  Observation of a participant: zone, every frame, +1 inside / -1 outside;
+ * line, s, but only when s != 0 and within (otherwise this frame is no observation).
+ *
+ * State, device buffers owned by the caller, all zero at first: st_id / st_side i32 [R_total][max_tracks], in_total / out_total i32
+ * [R_total].  A detection with track_ids[b][j] = id >= 0 owns the LOWEST slot t of its stream with trk_id[b][t] == id (none: it is treated as
+ * untracked).  Its previous side in region r is st_side[r][t] when st_id[r][t] == id and 0 (unknown) otherwise, which is how a slot taken
+ * by a new id forgets its predecessor.  An observation `side` with previous side -side is an event: +1 "in", -1 "out"; a first observation
+ * only records.  Then st_id[r][t] = id, st_side[r][t] = side.  in_total[r] / out_total[r] grow by the frame's events (one writer each).
+ * Ids are expected to be unique within a stream (the tracker's are); duplicates leave an unspecified one of their sides stored and stay
+ * memory-safe.  track_ids null (trk_id is then not read): occupancy only, no events, no state or total is written.
+ *
+ * Outputs of one update, every element written: now i32 [R_total] = the participants inside each zone this frame, tracked or not (0 for a
+ * line); det_inside / det_in / det_out u32 [B][T]: bit k set = inside zone k / "in" event / "out" event of region k; 0 from det_count[b] on.
+ * One launch, one workgroup per stream, plain stores, no atomics.
+ * Limits: 1 <= B <= FX_TRACK_MAX_STREAMS, 1 <= T, max_tracks <= FX_TRACK_MAX_SLOTS, R_total >= 1, V_total >= 2; kind 0 .. 1, anchor 0 .. 8, flags
+ * 0 .. 1, 0 <= vert_first, vert_first + vert_count <= V_total, a line's A != B.  Null (where required) or misaligned pointers (det_boxes 16,
+ * verts 8, everything else 4 bytes) or anything else outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched, nothing written.
+ *
+ * fx_zone_reset: the regions of stream b (0 <= b < B), or of every stream when b = -1, get st_id = st_side = 0 and, with clear_counters != 0,
+ * in_total = out_total = 0.  The same in both libraries. */
+#define FX_ZONE_MAX_REGIONS 32 /* per stream: one bit each in det_inside / det_in / det_out */
+#define FX_ZONE_MAX_VERTS 64
+enum { FX_ZONE_POLYGON = 0, FX_ZONE_LINE = 1 };
+enum { FX_ZONE_ANY_CLASS = 1 };
+typedef struct fx_zone_region {
+  int32_t kind, anchor, flags, vert_first, vert_count;
+  uint32_t class_words[8];
+  int32_t reserved[3];
+} fx_zone_region; /* 64 bytes */
+int fx_zone_update(const int32_t* det_labels, const int32_t* det_boxes, const int32_t* det_count, int B, int T, const int32_t* track_ids,
+                   const int32_t* trk_id, int max_tracks, const fx_zone_region* regions, const int32_t* reg_first, const int32_t* verts,
+                   const fx_zone_region* regions_host, const int32_t* reg_first_host, const int32_t* verts_host, int R_total, int V_total,
+                   int32_t* st_id, int32_t* st_side, int32_t* in_total, int32_t* out_total, int32_t* now, uint32_t* det_inside,
+                   uint32_t* det_in, uint32_t* det_out, fx_stream_t stream);
+int fx_zone_reset(int32_t* st_id, int32_t* st_side, int32_t* in_total, int32_t* out_total, const int32_t* reg_first_host, int B, int max_tracks,
+                  int b, int clear_counters, fx_stream_t stream);
 
 /* F.max_pool2d(k=3,s=2,p=1) (resnet.py:254) on NHWC bf16. */
 int fx_maxpool3x3s2_nhwc_bf16(const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, fx_stream_t stream);
