@@ -9,7 +9,7 @@
 // so both kernels are compared for equality with the numpy restatement of tests/annotate_ref.py.  The contract is in include/focoos_amd.h.
 //
 // fp32 / integer only: the FX_FP16 switch of the second library does not touch this file.
-#include "common.h"
+#include "det_common.h"
 
 #pragma clang fp contract(off)
 
@@ -22,8 +22,6 @@
 #define AN_KIND_BOX 1u
 #define AN_KIND_MASK 2u
 #define AN_KIND_LABEL 4u
-
-__device__ __forceinline__ int an_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // FOCOOS_PALETTE (#015fe6 #3faebd #63dba6 #a151ff #df923a) as R | G << 8 | B << 16; selects, not a table: a runtime-indexed array would live in scratch
 __device__ __forceinline__ uint32_t an_palette(int label) {
@@ -43,14 +41,14 @@ __global__ __launch_bounds__(256) void annotate_records_kernel(const float* __re
   if (flat >= (int64_t)B * T) return;
   const int b = (int)(flat / T), j = (int)(flat - (int64_t)b * T);
   uint32_t* out = reinterpret_cast<uint32_t*>(rec + flat);
-  if (j >= an_clamp(count[b], 0, T)) {
+  if (j >= fx_det_count(count, b, T)) {
 #pragma unroll
     for (int i = 0; i < (int)(sizeof(fx_annotate_record) / 4); ++i) out[i] = 0u;
     return;
   }
   const int label = labels[flat];
   const bool named = label >= 0 && label < K;
-  const int nl = named ? an_clamp(name_len[label], 0, FX_ANN_LNAME) : 0;
+  const int nl = named ? fx_clampi(name_len[label], 0, FX_ANN_LNAME) : 0;
   const uint8_t* name = name_glyphs + (int64_t)(named ? label : 0) * FX_ANN_LNAME;
   const float p = __fadd_rn(__fmul_rn(scores[flat], 100.0f), 0.5f);
   const int pct = p >= 100.0f ? 100 : (p >= 0.0f ? (int)p : 0);   // NaN fails both comparisons: 0
@@ -59,8 +57,8 @@ __global__ __launch_bounds__(256) void annotate_records_kernel(const float* __re
   const int pad = 2 * s, w = nchar * gw * s + 2 * pad, h = gh * s + 2 * pad;
   const int bx0 = boxes[flat * 4], by0 = boxes[flat * 4 + 1];
   const int wmax = W - w > 0 ? W - w : 0, hmax = H - h > 0 ? H - h : 0;
-  out[0] = (uint32_t)an_clamp(bx0, 0, wmax);
-  out[1] = (uint32_t)(by0 - h >= 0 ? by0 - h : an_clamp(by0, 0, hmax));
+  out[0] = (uint32_t)fx_clampi(bx0, 0, wmax);
+  out[1] = (uint32_t)(by0 - h >= 0 ? by0 - h : fx_clampi(by0, 0, hmax));
   out[2] = (uint32_t)w;
   out[3] = (uint32_t)h;
   out[4] = an_palette(label);
@@ -138,7 +136,7 @@ __global__ __launch_bounds__(AN_BX * AN_BY) void annotate_kernel(const uint8_t* 
   const int img = b0 + (int)blockIdx.z;
   const int tx0 = blockIdx.x * (AN_BX * 4), ty0 = blockIdx.y * AN_BY;
   const int tx1 = (tx0 + AN_BX * 4 < W ? tx0 + AN_BX * 4 : W) - 1, ty1 = (ty0 + AN_BY < H ? ty0 + AN_BY : H) - 1;   // inclusive
-  const int cnt = an_clamp(det_count[img], 0, T);
+  const int cnt = fx_det_count(det_count, img, T);
   const int thick = 2 * s;
   const int64_t slot0 = (int64_t)img * T;
 

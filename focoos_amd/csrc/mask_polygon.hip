@@ -15,17 +15,15 @@
 //     emit   poly_off = sum of the earlier slots' lengths; a slot that fits writes every word of its range exactly once
 //
 // Every loop has a trip count fixed before it starts (a wrong successor gives a wrong ring, never a walk without end), no workgroup waits
-// for another, nothing is read back between the launches.  Plain vector stores, no atomics; integer only: the FX_FP16 switch of the second
-// library does not touch this file.
-#include "common.h"
+// for another, nothing is read back between the launches.  The detection count, the box clamped to the frame, the block-wide exclusive scan
+// (groups, leaders) and the block-wide sum (poly_off) are det_common.h's, shared with mask_rle.hip.  Plain vector stores, no atomics;
+// integer only: the FX_FP16 switch of the second library does not touch this file.
+#include "det_common.h"
 
 #define POLY_THREADS 256
-#define POLY_WAVES (POLY_THREADS / 64)
 #define POLY_RANK_THREADS 1024
 #define POLY_EDGE_ARRAYS 7
 #define POLY_NONE 0x7fffffff
-
-__device__ __forceinline__ int poly_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // What of the frame a slot's box lets the kernels read: rows ya .. ye, words wa .. we, the first and last word masked to the box's columns.
 // Everything else is unset, like everything outside the frame.
@@ -36,13 +34,12 @@ struct PolyCtx {
 };
 
 __device__ __forceinline__ PolyCtx poly_ctx(const uint32_t* plane, const int32_t* __restrict__ box, int H, int W) {
-  const int x0 = poly_clampi(box[0], 0, W - 1), y0 = poly_clampi(box[1], 0, H - 1);
-  const int x1 = poly_clampi(box[2], 0, W - 1), y1 = poly_clampi(box[3], 0, H - 1);
+  const FxFrameBox f = fx_frame_box(box, H, W);
   PolyCtx c;
   c.plane = plane, c.W32 = (W + 31) >> 5;
-  c.ya = y0, c.ye = y1, c.wa = x0 >> 5, c.we = x1 >> 5;
-  c.mfirst = 0xffffffffu << (x0 & 31), c.mlast = 0xffffffffu >> (31 - (x1 & 31));
-  if (x1 < x0 || y1 < y0) c.ye = c.ya - 1, c.we = c.wa - 1;   // no group at all
+  c.ya = f.y0, c.ye = f.y1, c.wa = f.x0 >> 5, c.we = f.x1 >> 5;
+  c.mfirst = 0xffffffffu << (f.x0 & 31), c.mlast = 0xffffffffu >> (31 - (f.x1 & 31));
+  if (f.x1 < f.x0 || f.y1 < f.y0) c.ye = c.ya - 1, c.we = c.wa - 1;   // no group at all
   return c;
 }
 
@@ -114,10 +111,9 @@ __device__ __forceinline__ int poly_edge_base(const int32_t* __restrict__ slot_e
 __global__ __launch_bounds__(POLY_THREADS) void mask_polygon_scan_kernel(const uint32_t* __restrict__ words, const int32_t* __restrict__ det_count,
                                                                           const int32_t* __restrict__ det_boxes, int Q, int H, int W,
                                                                           int32_t* __restrict__ group_off, int32_t* __restrict__ slot_edges) {
-  __shared__ int s_sum[POLY_WAVES];
-  const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int64_t slot = (int64_t)b * Q + j;
-  if (j >= poly_clampi(det_count[b], 0, Q)) {
+  if (j >= fx_det_count(det_count, b, Q)) {
     if (tid == 0) slot_edges[slot] = 0;
     return;
   }
@@ -130,25 +126,10 @@ __global__ __launch_bounds__(POLY_THREADS) void mask_polygon_scan_kernel(const u
     const int g = base + tid;
     const bool in = g < G;
     const int y = c.ya + g / bw, wi = c.wa + g % bw;
-    int sum = in ? poly_count(poly_edges(c, y, wi)) : 0;   // inclusive scan inside the wavefront
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int s2 = __shfl_up(sum, o, 64);
-      if (lane >= o) sum += s2;
-    }
-    if (lane == 63) s_sum[wave] = sum;
-    __syncthreads();
-    int wsum = 0, tsum = 0;
-#pragma unroll
-    for (int w = 0; w < POLY_WAVES; ++w) {
-      if (w < wave) wsum += s_sum[w];
-      tsum += s_sum[w];
-    }
-    int esum = __shfl_up(sum, 1, 64);   // exclusive = inclusive of the lane before
-    if (lane == 0) esum = 0;
-    if (in) off[(int64_t)y * W32 + wi] = run + wsum + esum;
-    run += tsum;
-    __syncthreads();   // s_sum is rewritten by the next chunk
+    int total;
+    const int ex = fx_block_exscan<POLY_THREADS>(in ? poly_count(poly_edges(c, y, wi)) : 0, total);
+    if (in) off[(int64_t)y * W32 + wi] = run + ex;
+    run += total;
   }
   if (tid == 0) slot_edges[slot] = run;
 }
@@ -182,10 +163,9 @@ __global__ __launch_bounds__(POLY_RANK_THREADS) void mask_polygon_rank_kernel(co
                                                                                int max_edges, const int32_t* __restrict__ group_off,
                                                                                const int32_t* __restrict__ slot_edges, int32_t* edges,
                                                                                int32_t* __restrict__ poly_len) {
-  __shared__ int s_sum[POLY_RANK_THREADS / 64];
-  const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int64_t slot = (int64_t)b * Q + j;
-  if (j >= poly_clampi(det_count[b], 0, Q)) {
+  if (j >= fx_det_count(det_count, b, Q)) {
     if (tid == 0) poly_len[slot] = 0;
     return;
   }
@@ -284,25 +264,10 @@ __global__ __launch_bounds__(POLY_RANK_THREADS) void mask_polygon_rank_kernel(co
   for (int base = 0; base < E; base += POLY_RANK_THREADS) {   // block-uniform
     const int e = base + tid;
     const bool leader = e < E && a.lead[e] == e;
-    int sum = leader ? 1 + vs[e] : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int s2 = __shfl_up(sum, o, 64);
-      if (lane >= o) sum += s2;
-    }
-    if (lane == 63) s_sum[wave] = sum;
-    __syncthreads();
-    int wsum = 0, tsum = 0;
-#pragma unroll
-    for (int w = 0; w < POLY_RANK_THREADS / 64; ++w) {
-      if (w < wave) wsum += s_sum[w];
-      tsum += s_sum[w];
-    }
-    int esum = __shfl_up(sum, 1, 64);
-    if (lane == 0) esum = 0;
-    if (leader) ns[e] = run + wsum + esum;
-    run += tsum;
-    __syncthreads();
+    int total;
+    const int ex = fx_block_exscan<POLY_RANK_THREADS>(leader ? 1 + vs[e] : 0, total);
+    if (leader) ns[e] = run + ex;
+    run += total;
   }
   if (tid == 0) poly_len[slot] = run;
 }
@@ -311,23 +276,16 @@ __global__ __launch_bounds__(POLY_THREADS) void mask_polygon_emit_kernel(const i
                                                                           const int32_t* __restrict__ slot_edges, int32_t* edges,
                                                                           const int32_t* __restrict__ poly_len, int32_t* __restrict__ poly_off,
                                                                           int32_t* __restrict__ poly_pool) {
-  __shared__ int s_part[POLY_WAVES];
-  const int j = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
   const int64_t slot = (int64_t)b * Q + j;
   // poly_off = sum of the lengths of the slots before j, a slot without a stream (0 or -1) counting 0 (below 2^31: an argument check)
   int part = 0;
   for (int i = tid; i < j; i += POLY_THREADS) part += max(poly_len[(int64_t)b * Q + i], 0);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-  if (lane == 0) s_part[wave] = part;
-  __syncthreads();
-  int off = 0;
-#pragma unroll
-  for (int w = 0; w < POLY_WAVES; ++w) off += s_part[w];
+  const int off = fx_block_sum<POLY_THREADS>(part);
   const int len = poly_len[slot];
   if (blockIdx.x == 0 && tid == 0) poly_off[slot] = off;
   if (len <= 0 || (int64_t)off + len > (int64_t)capacity) return;   // no stream, or it does not fit: nothing of it is written
-  if (j >= poly_clampi(det_count[b], 0, Q)) return;
+  if (j >= fx_det_count(det_count, b, Q)) return;
   const int E = slot_edges[slot];
   bool fits;
   const int ebase = poly_edge_base(slot_edges + (int64_t)b * Q, j, max_edges, &fits);

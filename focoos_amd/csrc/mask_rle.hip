@@ -12,14 +12,13 @@
 //
 // A lane gets the 64 rows of its column as one 64-bit register by a ballot transpose of the tile's rows (lane r loads the two words of row
 // r, 64 ballots hand lane c bit c of every row): no LDS, two coalesced dword loads per lane and 64 rows, and the transitions of 64 rows are
-// popcount(w ^ (w << 1 | carry)).  The contract is in include/focoos_amd.h.  Plain vector stores, no atomics; integer only: the FX_FP16
-// switch of the second library does not touch this file.
-#include "common.h"
+// popcount(w ^ (w << 1 | carry)).  The contract is in include/focoos_amd.h.  The detection count, the box clamped to the frame, the
+// block-wide exclusive scan and the block-wide sum are det_common.h's, shared with mask_polygon.hip.  Plain vector stores, no atomics;
+// integer only: the FX_FP16 switch of the second library does not touch this file.
+#include "det_common.h"
 
 #define RLE_THREADS 256
 #define RLE_WAVES (RLE_THREADS / 64)
-
-__device__ __forceinline__ int rle_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // What of the frame a slot's box lets the kernels visit: columns xa .. xe (the column after the box included: a run that reaches the bottom
 // row of the box's last column ends at the top of the next one) and rows ra .. re (the row after the box included).  Everything outside
@@ -30,11 +29,10 @@ struct RleSpan {
 };
 
 __device__ __forceinline__ RleSpan rle_span(const int32_t* __restrict__ box, int H, int W) {
-  const int x0 = rle_clampi(box[0], 0, W - 1), y0 = rle_clampi(box[1], 0, H - 1);
-  const int x1 = rle_clampi(box[2], 0, W - 1), y1 = rle_clampi(box[3], 0, H - 1);
+  const FxFrameBox f = fx_frame_box(box, H, W);
   RleSpan s;
-  s.xa = x0, s.xe = min(x1 + 1, W - 1);
-  s.ra = y0, s.re = min(y1 + 1, H - 1);
+  s.xa = f.x0, s.xe = min(f.x1 + 1, W - 1);
+  s.ra = f.y0, s.re = min(f.y1 + 1, H - 1);
   return s;
 }
 
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(RLE_THREADS) void mask_rle_count_kernel(const uint3
                                                                       const int32_t* __restrict__ det_boxes, int Q, int H, int W,
                                                                       int32_t* __restrict__ colcnt, int32_t* __restrict__ collast) {
   const int j = blockIdx.y, b = blockIdx.z;
-  if (j >= rle_clampi(det_count[b], 0, Q)) return;
+  if (j >= fx_det_count(det_count, b, Q)) return;
   const int64_t slot = (int64_t)b * Q + j;
   const RleSpan sp = rle_span(det_boxes + slot * 4, H, W);
   const int xb = (blockIdx.x * RLE_WAVES + (threadIdx.x >> 6)) * 64;
@@ -121,43 +119,25 @@ __global__ __launch_bounds__(RLE_THREADS) void mask_rle_scan_kernel(const int32_
                                                                      int Q, int H, int W, int32_t* __restrict__ colcnt,
                                                                      int32_t* __restrict__ collast, int32_t* __restrict__ slotlast,
                                                                      int32_t* __restrict__ rle_len) {
-  __shared__ int s_sum[RLE_WAVES], s_max[RLE_WAVES];
-  const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int64_t slot = (int64_t)b * Q + j;
-  if (j >= rle_clampi(det_count[b], 0, Q)) {
+  if (j >= fx_det_count(det_count, b, Q)) {
     if (tid == 0) rle_len[slot] = 0, slotlast[slot] = 0;
     return;
   }
   const RleSpan sp = rle_span(det_boxes + slot * 4, H, W);
   int32_t* cc = colcnt + slot * W;
   int32_t* cl = collast + slot * W;
-  int run_sum = 0, run_max = 0;   // over the chunks before this one
+  FxSumMax run = {0, 0};   // over the chunks before this one
   for (int base = sp.xa; base <= sp.xe; base += RLE_THREADS) {   // block-uniform
     const int x = base + tid;
     const bool in = x <= sp.xe;
-    const int v = in ? cc[x] : 0, m = in ? cl[x] : 0;
-    int sum = v, mx = m;   // inclusive scans inside the wavefront
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int s2 = __shfl_up(sum, o, 64), m2 = __shfl_up(mx, o, 64);
-      if (lane >= o) sum += s2, mx = max(mx, m2);
-    }
-    if (lane == 63) s_sum[wave] = sum, s_max[wave] = mx;
-    __syncthreads();
-    int wsum = 0, wmax = 0, tsum = 0, tmax = 0;
-#pragma unroll
-    for (int w = 0; w < RLE_WAVES; ++w) {
-      if (w < wave) wsum += s_sum[w], wmax = max(wmax, s_max[w]);
-      tsum += s_sum[w], tmax = max(tmax, s_max[w]);
-    }
-    // exclusive = inclusive of the lane before
-    int esum = __shfl_up(sum, 1, 64), emax = __shfl_up(mx, 1, 64);
-    if (lane == 0) esum = 0, emax = 0;
-    if (in) cc[x] = run_sum + wsum + esum, cl[x] = max(run_max, max(wmax, emax));
-    run_sum += tsum, run_max = max(run_max, tmax);
-    __syncthreads();   // s_sum / s_max are rewritten by the next chunk
+    FxSumMax total;
+    const FxSumMax ex = fx_block_exscan<RLE_THREADS>(in ? FxSumMax{cc[x], cl[x]} : FxSumMax{0, 0}, total);
+    if (in) cc[x] = run.sum + ex.sum, cl[x] = max(run.mx, ex.mx);
+    run = fx_scan_join(run, total);
   }
-  if (tid == 0) rle_len[slot] = run_sum + 1, slotlast[slot] = run_max;
+  if (tid == 0) rle_len[slot] = run.sum + 1, slotlast[slot] = run.mx;
 }
 
 __global__ __launch_bounds__(RLE_THREADS) void mask_rle_emit_kernel(const uint32_t* __restrict__ words, const int32_t* __restrict__ det_count,
@@ -165,19 +145,12 @@ __global__ __launch_bounds__(RLE_THREADS) void mask_rle_emit_kernel(const uint32
                                                                      const int32_t* __restrict__ rle_len, int32_t* __restrict__ colstart,
                                                                      int32_t* __restrict__ colprev, const int32_t* __restrict__ slotlast,
                                                                      int32_t* __restrict__ rle_off, int32_t* __restrict__ rle_counts) {
-  __shared__ int s_part[RLE_WAVES];
-  const int j = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, wave = tid >> 6;
   const int64_t slot = (int64_t)b * Q + j;
   // rle_off = sum of rle_len over the slots before j (below 2^31: an argument check); zero lengths from det_count on
   int part = 0;
   for (int i = tid; i < j; i += RLE_THREADS) part += rle_len[(int64_t)b * Q + i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-  if (lane == 0) s_part[wave] = part;
-  __syncthreads();
-  int off = 0;
-#pragma unroll
-  for (int w = 0; w < RLE_WAVES; ++w) off += s_part[w];
+  const int off = fx_block_sum<RLE_THREADS>(part);
   const int len = rle_len[slot];
   const bool stored = len > 0 && (int64_t)off + len <= (int64_t)capacity;
   int32_t* out = rle_counts + (int64_t)b * capacity + off;

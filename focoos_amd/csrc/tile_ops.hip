@@ -11,7 +11,7 @@
 //                            pure function of the inputs and is compared for equality with the numpy restatement (tests/tiled_ref.py).
 //
 // fp32 / fp64 / integer only: the FX_FP16 switch of the second library does not touch this file.
-#include "common.h"
+#include "det_common.h"
 
 #pragma clang fp contract(off)
 
@@ -125,8 +125,6 @@ __device__ __forceinline__ uint64_t mg_key(float score, int flat) {
   return ((uint64_t)b << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)flat);
 }
 
-__device__ __forceinline__ int mg_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // One thread per slot of [N][T].  A valid slot (slot < count[view]) counts the valid slots that precede it in the total order (every lane
 // reads the same address in the loop, so the compared keys arrive as broadcast loads) and, when that rank is below the cap, writes itself
 // into the sorted arrays: its box moved by its window's origin and clamped to the frame.  Ranks are a permutation of 0..M-1, so every
@@ -138,12 +136,12 @@ __global__ __launch_bounds__(256) void merge_rank_kernel(const float* __restrict
   const int64_t flat64 = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (flat64 >= (int64_t)N * T) return;
   const int flat = (int)flat64, n = flat / T, j = flat - n * T;
-  const bool valid = j < mg_clamp(count[n], 0, T);
+  const bool valid = j < fx_det_count(count, n, T);
   if (!valid && flat != 0) return;
   const uint64_t key = valid ? mg_key(scores[flat], flat) : 0;
   int rank = 0, total = 0;
   for (int v = 0; v < N; ++v) {
-    const int c = mg_clamp(count[v], 0, T);
+    const int c = fx_det_count(count, v, T);
     const float* sv = scores + (int64_t)v * T;
     for (int s = 0; s < c; ++s) rank += mg_key(sv[s], v * T + s) > key ? 1 : 0;
     total += c;
@@ -153,16 +151,11 @@ __global__ __launch_bounds__(256) void merge_rank_kernel(const float* __restrict
   const int ox = windows[4 * n], oy = windows[4 * n + 1];
   const int32_t* b = boxes + (int64_t)flat * 4;
   int4 o;
-  o.x = mg_clamp(b[0] + ox, 0, frame_w), o.y = mg_clamp(b[1] + oy, 0, frame_h);
-  o.z = mg_clamp(b[2] + ox, 0, frame_w), o.w = mg_clamp(b[3] + oy, 0, frame_h);
+  o.x = fx_clampi(b[0] + ox, 0, frame_w), o.y = fx_clampi(b[1] + oy, 0, frame_h);
+  o.z = fx_clampi(b[2] + ox, 0, frame_w), o.w = fx_clampi(b[3] + oy, 0, frame_h);
   reinterpret_cast<float*>(ws + MG_OFF_SCORE)[rank] = scores[flat];
   reinterpret_cast<int32_t*>(ws + MG_OFF_LABEL)[rank] = labels[flat];
   reinterpret_cast<int4*>(ws + MG_OFF_BOX)[rank] = o;
-}
-
-__device__ __forceinline__ int64_t mg_area(const int4& b) {
-  const int64_t w = b.z > b.x ? b.z - b.x : 0, h = b.w > b.y ? b.w - b.y : 0;
-  return w * h;
 }
 
 // Phase 1: workgroup (bj, bi) = one wavefront = the 64 x 64 block (rows 64 bi.., columns 64 bj..) of the upper triangle.  Lane l owns column
@@ -184,17 +177,15 @@ __global__ __launch_bounds__(64) void merge_mask_kernel(unsigned char* __restric
   const bool cv = col < M;
   const int4 cb = cv ? box[col] : make_int4(0, 0, 0, 0);
   const int cl = cv ? lab[col] : -2;
-  const int64_t ca = mg_area(cb);
+  const int64_t ca = fx_box_area(cb);
   const double dthr = (double)thr;
   uint64_t mine = 0;
   for (int i = 0; i < 64; ++i) {
     const int4 rb = s_box[i];
-    const int64_t ra = mg_area(rb);
+    const int64_t ra = fx_box_area(rb);
     bool hit = false;
     if (cv && 64 * bi + i < col && s_lab[i] == cl && ra > 0 && ca > 0) {   // rows >= M hold label -1 and area 0
-      const int ix0 = rb.x > cb.x ? rb.x : cb.x, iy0 = rb.y > cb.y ? rb.y : cb.y;
-      const int ix1 = rb.z < cb.z ? rb.z : cb.z, iy1 = rb.w < cb.w ? rb.w : cb.w;
-      const int64_t inter = (ix1 > ix0 && iy1 > iy0) ? (int64_t)(ix1 - ix0) * (int64_t)(iy1 - iy0) : 0;
+      const int64_t inter = fx_box_inter(rb, cb);
       const int64_t den = ios ? (ra < ca ? ra : ca) : ra + ca - inter;
       hit = (double)inter > dthr * (double)den;
     }

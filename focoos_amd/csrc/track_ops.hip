@@ -10,7 +10,7 @@
 //
 // The contract of both is in include/focoos_amd.h.  Plain vector stores, no atomics.  fp32 / fp64 / integer only: the FX_FP16 switch of
 // the second library does not touch this file.
-#include "common.h"
+#include "det_common.h"
 
 #pragma clang fp contract(off)
 
@@ -25,27 +25,18 @@
 #define TK_LOW 2
 #define TK_BIRTH 4
 
-__device__ __forceinline__ int tk_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // clamp(rint(x), 0, 16384) with rint rounding half to even; NaN gives 0
 __device__ __forceinline__ int tk_coord(float x) {
   const float r = rintf(x);
   return !(r >= 0.0f) ? 0 : (r > (float)TK_COORD ? TK_COORD : (int)r);
 }
 
-__device__ __forceinline__ int64_t tk_area(const int4& b) {
-  const int64_t w = b.z > b.x ? b.z - b.x : 0, h = b.w > b.y ? b.w - b.y : 0;
-  return w * h;
-}
-
-// The eligibility of one (track, detection) pair, the merge kernel's form: both areas non-zero and (double)inter > thr * (double)union.
-// Labels are compared by the caller.  inter / uni come back for the order.
+// The eligibility of one (track, detection) pair, the merge kernel's form on the same box arithmetic (det_common.h): both areas non-zero
+// and (double)inter > thr * (double)union.  Labels are compared by the caller.  inter / uni come back for the order.
 __device__ __forceinline__ bool tk_pair(const int4& a, const int4& d, double thr, int64_t& inter, int64_t& uni) {
-  const int ix0 = a.x > d.x ? a.x : d.x, iy0 = a.y > d.y ? a.y : d.y;
-  const int ix1 = a.z < d.z ? a.z : d.z, iy1 = a.w < d.w ? a.w : d.w;
-  if (ix1 <= ix0 || iy1 <= iy0) return false;   // inter = 0 never exceeds thr * union (thr > 0): covers the zero areas as well
-  inter = (int64_t)(ix1 - ix0) * (int64_t)(iy1 - iy0);
-  uni = tk_area(a) + tk_area(d) - inter;
+  inter = fx_box_inter(a, d);
+  if (inter == 0) return false;   // inter = 0 never exceeds thr * union (thr > 0): covers the zero areas as well
+  uni = fx_box_area(a) + fx_box_area(d) - inter;
   return (double)inter > thr * (double)uni;
 }
 
@@ -78,7 +69,7 @@ __global__ __launch_bounds__(TK_THREADS) void track_update_kernel(
   __shared__ int s_n[2];
 
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int cnt = tk_clampi(det_count[b], 0, T);
+  const int cnt = fx_det_count(det_count, b, T);
   int32_t* g_id = trk_id + (int64_t)b * M;
   int32_t* g_label = trk_label + (int64_t)b * M;
   int32_t* g_tsu = trk_tsu + (int64_t)b * M;
@@ -106,9 +97,9 @@ __global__ __launch_bounds__(TK_THREADS) void track_update_kernel(
     const int64_t f = (int64_t)b * T + j;
     const float sc = det_scores[f];
     const int4 r = reinterpret_cast<const int4*>(det_boxes)[f];
-    const int4 d = make_int4(tk_clampi(r.x, 0, TK_COORD), tk_clampi(r.y, 0, TK_COORD), tk_clampi(r.z, 0, TK_COORD), tk_clampi(r.w, 0, TK_COORD));
+    const int4 d = make_int4(fx_clampi(r.x, 0, TK_COORD), fx_clampi(r.y, 0, TK_COORD), fx_clampi(r.z, 0, TK_COORD), fx_clampi(r.w, 0, TK_COORD));
     unsigned char fl = sc >= high ? TK_HIGH : (sc >= low ? TK_LOW : 0);   // a NaN score takes no part
-    if (fl == TK_HIGH && sc >= new_thresh && tk_area(d) > 0) fl |= TK_BIRTH;
+    if (fl == TK_HIGH && sc >= new_thresh && fx_box_area(d) > 0) fl |= TK_BIRTH;
     s_dbox[j] = d, s_dlab[j] = det_labels[f], s_dfl[j] = fl, s_dm[j] = TK_NONE;
   }
   __syncthreads();

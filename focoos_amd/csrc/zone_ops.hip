@@ -11,7 +11,7 @@
 // The contract of both is in include/focoos_amd.h.  Plain vector stores, no atomics: a region belongs to one stream, so one workgroup is
 // the only writer of its state rows and one thread the only writer of its counters.  Integer only: the FX_FP16 switch of the second
 // library does not touch this file.
-#include "common.h"
+#include "det_common.h"
 
 #pragma clang fp contract(off)
 
@@ -25,8 +25,6 @@
 
 static_assert(sizeof(fx_zone_region) == 64, "fx_zone_region is 64 bytes");
 static_assert(ZN_REGIONS == 32, "one bit per region in a 32-bit mask, one lane of a half wavefront per region counter");
-
-__device__ __forceinline__ int zn_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // One workgroup = one stream.  Thread i owns detections i, i + 256, ... (at most 4), one at a time: its box, label, id and slot stay in
 // registers while the regions of the stream (records and doubled vertices in LDS, read at wave-uniform addresses) go by.  Every loop
@@ -43,10 +41,10 @@ __global__ __launch_bounds__(ZN_THREADS) void zone_update_kernel(
   __shared__ int s_cnt[ZN_WAVES][3][ZN_REGIONS];
 
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int cnt = zn_clampi(det_count[b], 0, T);
+  const int cnt = fx_det_count(det_count, b, T);
   // the device tables are the bytes the library validated on the host; the clamps keep a caller whose copies differ inside the buffers
-  const int r0 = zn_clampi(reg_first[b], 0, R_total);
-  const int nr = zn_clampi(reg_first[b + 1] - r0, 0, R_total - r0 < ZN_REGIONS ? R_total - r0 : ZN_REGIONS);
+  const int r0 = fx_clampi(reg_first[b], 0, R_total);
+  const int nr = fx_clampi(reg_first[b + 1] - r0, 0, R_total - r0 < ZN_REGIONS ? R_total - r0 : ZN_REGIONS);
   const bool tracked = track_ids != nullptr;
 
   if (tracked)
@@ -56,10 +54,10 @@ __global__ __launch_bounds__(ZN_THREADS) void zone_update_kernel(
   __syncthreads();
   for (int i = tid; i < nr * ZN_VERTS; i += ZN_THREADS) {
     const int k = i / ZN_VERTS, v = i % ZN_VERTS;      // powers of two: shifts
-    const int vc = zn_clampi(s_reg[k].vert_count, 0, V_total < ZN_VERTS ? V_total : ZN_VERTS);
+    const int vc = fx_clampi(s_reg[k].vert_count, 0, V_total < ZN_VERTS ? V_total : ZN_VERTS);
     if (v < vc) {
-      const int2 p = reinterpret_cast<const int2*>(verts)[zn_clampi(s_reg[k].vert_first, 0, V_total - vc) + v];
-      s_vert[i] = make_int2(2 * zn_clampi(p.x, -ZN_VCOORD, ZN_VCOORD), 2 * zn_clampi(p.y, -ZN_VCOORD, ZN_VCOORD));
+      const int2 p = reinterpret_cast<const int2*>(verts)[fx_clampi(s_reg[k].vert_first, 0, V_total - vc) + v];
+      s_vert[i] = make_int2(2 * fx_clampi(p.x, -ZN_VCOORD, ZN_VCOORD), 2 * fx_clampi(p.y, -ZN_VCOORD, ZN_VCOORD));
     }
   }
   __syncthreads();
@@ -72,7 +70,7 @@ __global__ __launch_bounds__(ZN_THREADS) void zone_update_kernel(
     int x0 = 0, y0 = 0, x1 = 0, y1 = 0, lab = 0, id = -1, slot = -1;
     if (valid) {
       const int4 r = reinterpret_cast<const int4*>(det_boxes)[f];
-      x0 = zn_clampi(r.x, 0, ZN_COORD), y0 = zn_clampi(r.y, 0, ZN_COORD), x1 = zn_clampi(r.z, 0, ZN_COORD), y1 = zn_clampi(r.w, 0, ZN_COORD);
+      x0 = fx_clampi(r.x, 0, ZN_COORD), y0 = fx_clampi(r.y, 0, ZN_COORD), x1 = fx_clampi(r.z, 0, ZN_COORD), y1 = fx_clampi(r.w, 0, ZN_COORD);
       lab = det_labels[f];
       if (tracked) id = track_ids[f];
     }
@@ -89,7 +87,7 @@ __global__ __launch_bounds__(ZN_THREADS) void zone_update_kernel(
     for (int k = 0; k < nr; ++k) {
       const fx_zone_region& rg = s_reg[k];
       const int2* vt = s_vert + k * ZN_VERTS;
-      const int vc = zn_clampi(rg.vert_count, 0, V_total < ZN_VERTS ? V_total : ZN_VERTS);
+      const int vc = fx_clampi(rg.vert_count, 0, V_total < ZN_VERTS ? V_total : ZN_VERTS);
       const bool pass = valid && ((rg.flags & FX_ZONE_ANY_CLASS) || ((unsigned)lab < 256u && ((rg.class_words[lab >> 5] >> (lab & 31)) & 1u)));
       const int ix = rg.anchor % 3, iy = rg.anchor / 3;   // constant divisors
       const int px = ix == 0 ? 2 * x0 : (ix == 1 ? x0 + x1 : 2 * x1), py = iy == 0 ? 2 * y0 : (iy == 1 ? y0 + y1 : 2 * y1);

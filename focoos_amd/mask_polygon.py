@@ -8,13 +8,15 @@ warning per call, so the result is always complete.
 
 A ring is a flat list ``[x0, y0, x1, y1, ...]`` of lattice points in frame pixels (pixel (x, y) is the square [x, x + 1] x [y, y + 1]); the
 rings of a mask come in the canonical order of the definition, holes included: a hole has a negative shoelace sum (``is_hole``).  Vertex
-simplification and cv2's pixel-centre contours are out of scope."""
+simplification and cv2's pixel-centre contours are out of scope.  What this encoder shares with mask_rle.py's (buffers, checks, copy
+back, fallback, ``encoder_for``) is mask_pool.py."""
 from __future__ import annotations
 
-import warnings
-from typing import List, Optional, Sequence
+from typing import List, Optional
 
 import numpy as np
+
+from .mask_pool import PooledMaskEncoder, unpack_words  # noqa: F401  (unpack_words is imported from here as well)
 
 # side s of a pixel: 0 top, 1 right, 2 bottom, 3 left.  Heading of its edge (the set pixel on the right, y downward), the step across the
 # side (to the left of the heading) and the tail of the edge relative to the pixel
@@ -70,14 +72,6 @@ def trace_mask_numpy(mask) -> List[List[int]]:
                 break
         rings.append(ring)
     return rings
-
-
-def unpack_words(words, W: int) -> np.ndarray:
-    """int32 [H, ceil(W / 32)] bit-packed rows (pixel x = bit x % 32 of word x / 32) -> bool [H, W]."""
-    w = np.ascontiguousarray(np.asarray(words)).astype("<i4", copy=False)
-    if w.ndim != 2 or w.shape[1] != (int(W) + 31) // 32:
-        raise ValueError(f"words must be [H, {(int(W) + 31) // 32}] for W = {W}, got {w.shape}")
-    return np.unpackbits(w.view(np.uint8), axis=-1, bitorder="little")[:, :int(W)].astype(bool)
 
 
 def trace_words_numpy(words, W: int) -> List[List[int]]:
@@ -152,113 +146,32 @@ def default_max_edges(Q: int, H: int, W: int) -> int:
     return int(Q) * 2 * (int(H) + int(W))
 
 
-class MaskPolygonEncoder:
-    """Output buffers and workspace of fx_mask_polygon_encode for results of one shape (B images, Q slots, H x W pixels) on ``device``.
-    ``encode(res)`` launches on the current stream; ``fetch()`` copies the lengths, the offsets and the used prefix of each image's pool
-    on that stream and returns, per image, the rings of its detections.  One encoder serves every lane of ``infer_stream``: launch and
-    copy of a batch run in order on one stream before the next batch is encoded."""
+class MaskPolygonEncoder(PooledMaskEncoder):
+    """The pooled encoder (mask_pool.py) of fx_mask_polygon_encode: a slot's stream is ``decode_stream``'s, ``fetch()`` returns per image
+    the list, in slot order, of its detections' rings (each ring a flat [x0, y0, x1, y1, ...]; [] for an empty mask)."""
+
+    CALL, SIZES = "fx_mask_polygon", ("capacity", "max_edges")
+    LIMITS = "H, W <= 32767, Q (L + L / 4) < 2^31 with L = 2 H W + H + W"
 
     def __init__(self, B: int, Q: int, H: int, W: int, device, capacity: Optional[int] = None, max_edges: Optional[int] = None):
-        import torch
+        super().__init__(B, Q, H, W, device, capacity, max_edges)
+        self.poly_len, self.poly_off, self.poly_pool = self.meta[0], self.meta[1], self.pool
 
-        from ._lib import load
+    @staticmethod
+    def sizes(Q, H, W, capacity=None, max_edges=None):
+        return (default_capacity(Q, W) if capacity is None else int(capacity),
+                default_max_edges(Q, H, W) if max_edges is None else int(max_edges))
 
-        self.lib = load("bf16")   # inference surface: the bf16 product library (the kernel is the same in both)
-        self.device = torch.device(device)
-        self.B, self.Q, self.H, self.W = int(B), int(Q), int(H), int(W)
-        self.capacity = default_capacity(Q, W) if capacity is None else int(capacity)
-        self.max_edges = default_max_edges(Q, H, W) if max_edges is None else int(max_edges)
-        if self.capacity < 1 or self.max_edges < 1:
-            raise ValueError(f"MaskPolygonEncoder: capacity = {capacity!r} and max_edges = {max_edges!r} must be >= 1")
-        nb = int(self.lib.fx_mask_polygon_workspace_bytes(self.B, self.Q, self.H, self.W, self.max_edges))
-        if nb == 0:
-            raise ValueError(f"MaskPolygonEncoder: B = {B}, Q = {Q}, H = {H}, W = {W} is outside the kernel's limits (H, W <= 32767, "
-                             "Q (L + L / 4) < 2^31 with L = 2 H W + H + W)")
-        i32 = dict(dtype=torch.int32, device=self.device)
-        self.meta = torch.zeros(2, self.B, self.Q, **i32)      # poly_len, poly_off: one copy back
-        self.poly_len, self.poly_off = self.meta[0], self.meta[1]
-        self.poly_pool = torch.zeros(self.B, self.capacity, **i32)
-        self.workspace = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        self._host = None          # pinned [B, capacity], made with the first fetch
-        self._res = None
-        self.last_d2h_bytes = 0    # of the last fetch, fallback words included
-        self.last_fallback = 0     # slots the last fetch traced on the host
-        self.total_fallback = 0    # ... and every fetch of this encoder, out of total_masks
-        self.total_masks = 0
-
-    def key(self):
-        return (self.B, self.Q, self.H, self.W, self.device, self.capacity, self.max_edges)
-
-    def encode(self, res) -> None:
-        """``res``: an engine plan or the processor's device results (``mask_words`` [B, Q, H, ceil(W / 32)], ``det_count``, ``det_boxes``)."""
-        import torch
-
-        from ._lib import check
-
-        words = res.mask_words
-        shape = (self.B, self.Q, self.H, (self.W + 31) // 32)
-        if tuple(words.shape) != shape or words.dtype != torch.int32 or not words.is_contiguous() or words.device != self.device:
-            raise ValueError(f"MaskPolygonEncoder.encode: mask_words must be a contiguous int32 tensor {shape} on {self.device}, got "
-                             f"{words.dtype} {tuple(words.shape)} on {words.device}")
-        for name, t, shp in (("det_count", res.det_count, (self.B,)), ("det_boxes", res.det_boxes, (self.B, self.Q, 4))):
-            if tuple(t.shape) != shp or t.dtype != torch.int32 or not t.is_contiguous() or t.device != self.device:
-                raise ValueError(f"MaskPolygonEncoder.encode: {name} must be a contiguous int32 tensor {shp} on {self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        check(self.lib.fx_mask_polygon_encode(words.data_ptr(), res.det_count.data_ptr(), res.det_boxes.data_ptr(), self.B, self.Q, self.H, self.W,
-                                              self.capacity, self.max_edges, self.poly_len.data_ptr(), self.poly_off.data_ptr(),
-                                              self.poly_pool.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), stream),
-              "fx_mask_polygon_encode")
-        self._res = res
-
-    def fetch(self) -> List[List[List[List[int]]]]:
-        """Per image the list, in slot order, of its detections' rings (each ring a flat [x0, y0, x1, y1, ...]; [] for an empty mask)."""
-        import torch
-
-        if self._res is None:
-            raise RuntimeError("MaskPolygonEncoder.fetch: nothing was encoded")
-        meta = self.meta.cpu().numpy().astype(np.int64)      # synchronises the stream
-        ln, off = meta[0], meta[1]
+    def _det_counts(self, ln):
         count = np.clip(self._res.det_count.cpu().numpy().astype(np.int64), 0, self.Q)      # an empty mask has length 0 too: the count decides
-        stored = (ln > 0) & (off + ln <= self.capacity)
-        used = np.where(stored, off + ln, 0).max(axis=1)
-        if self._host is None:
-            self._host = torch.empty(self.B, self.capacity, dtype=torch.int32, pin_memory=True)
-        for b in range(self.B):
-            if used[b]:
-                self._host[b, :used[b]].copy_(self.poly_pool[b, :used[b]], non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        pool = self._host.numpy()
-        self.last_d2h_bytes = int(meta.size * 4 + count.size * 4 + used.sum() * 4)
-        out, fell, masks = [], 0, 0
-        for b in range(self.B):
-            n = int(count[b])
-            masks += n
-            lost = np.flatnonzero(~stored[b, :n] & (ln[b, :n] != 0))      # -1, or did not fit the pool
-            words = {}
-            if len(lost):      # the same rings from the slots' bit words, on the host (one copy per image)
-                w = self._res.mask_words[b, :n][torch.from_numpy(lost).to(self.device)].cpu().numpy()
-                self.last_d2h_bytes += w.nbytes
-                words = dict(zip(lost.tolist(), w))
-                fell += len(lost)
-            out.append([decode_stream(pool[b, off[b, j]:off[b, j] + ln[b, j]]) if stored[b, j]
-                        else (trace_words_numpy(words[j], self.W) if j in words else []) for j in range(n)])
-        self.last_fallback = fell
-        self.total_fallback += fell
-        self.total_masks += masks
-        if fell:
-            warnings.warn(f"mask_format='polygon': {fell} of {masks} masks did not fit the pool of {self.capacity} words or the workspace of "
-                          f"{self.max_edges} edges per image and were traced on the host (raise the capacity)", RuntimeWarning, stacklevel=3)
-        return out
+        return count, count.size * 4
 
+    def _decode(self, stream):
+        return decode_stream(stream)
 
-def encoder_for(current: Optional[MaskPolygonEncoder], res, capacity: Optional[int] = None,
-                max_edges: Optional[int] = None) -> MaskPolygonEncoder:
-    """``current`` when it fits ``res`` (shape, device, capacity, max_edges), a new encoder otherwise."""
-    B, Q, H, _ = res.mask_words.shape
-    W = int(getattr(res, "mask_width", res.mask_words.shape[3] * 32))
-    dev = res.mask_words.device
-    cap = default_capacity(Q, W) if capacity is None else int(capacity)
-    me = default_max_edges(Q, H, W) if max_edges is None else int(max_edges)
-    if current is not None and current.key() == (B, Q, H, W, dev, cap, me):
-        return current
-    return MaskPolygonEncoder(B, Q, H, W, dev, cap, me)
+    def _encode_words(self, words):
+        return trace_words_numpy(words, self.W)
+
+    def _warning(self, fell, masks):
+        return (f"mask_format='polygon': {fell} of {masks} masks did not fit the pool of {self.capacity} words or the workspace of "
+                f"{self.max_edges} edges per image and were traced on the host (raise the capacity)")

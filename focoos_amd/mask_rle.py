@@ -4,13 +4,15 @@ The mask families leave their kept masks on the device as bit-packed words.  ``M
 (csrc/mask_rle.hip; the contract is in include/focoos_amd.h) and copies back the lengths, the offsets and the used part of each image's
 pool of counts: no dense mask crosses to the host and nothing is compressed on it.  A slot whose counts did not fit the pool is encoded on
 the host from its bit words (``encode_words_numpy``), with one warning per call, so the result is always complete.  The compressed RLE
-*string* of maskApi is out of scope (``check_mask_format``), like tiled inference; polygons are mask_polygon.py."""
+*string* of maskApi is out of scope (``check_mask_format``), like tiled inference; polygons are mask_polygon.py, and what the two
+encoders share (buffers, checks, copy back, fallback, ``encoder_for``) is mask_pool.py."""
 from __future__ import annotations
 
-import warnings
 from typing import List, Optional, Sequence
 
 import numpy as np
+
+from .mask_pool import PooledMaskEncoder, unpack_words
 
 MASK_FORMATS = ("png", "rle", "polygon", "none")
 MASK_FAMILIES = ("fai_mf", "bisenetformer")
@@ -44,11 +46,7 @@ def encode_mask_numpy(mask) -> dict:
 
 def encode_words_numpy(words, W: int) -> dict:
     """int32 [H, ceil(W / 32)] bit-packed rows (pixel x = bit x % 32 of word x / 32) -> the RLE dict of the mask."""
-    w = np.ascontiguousarray(np.asarray(words)).astype("<i4", copy=False)
-    if w.ndim != 2 or w.shape[1] != (int(W) + 31) // 32:
-        raise ValueError(f"encode_words_numpy: words must be [H, {(int(W) + 31) // 32}] for W = {W}, got {w.shape}")
-    bits = np.unpackbits(w.view(np.uint8), axis=-1, bitorder="little")[:, :int(W)]
-    return encode_mask_numpy(bits)
+    return encode_mask_numpy(unpack_words(words, W))
 
 
 def _runs(rle: dict):
@@ -102,106 +100,29 @@ def default_capacity(Q: int, W: int) -> int:
     return int(Q) * (2 * int(W) + 2)
 
 
-class MaskRleEncoder:
-    """Output buffers and workspace of fx_mask_rle_encode for results of one shape (B images, Q slots, H x W pixels) on ``device``.
-    ``encode(res)`` launches on the current stream; ``fetch()`` copies the lengths, the offsets and the used prefix of each image's pool
-    on that stream and returns, per image, the RLE dicts of its detections.  One encoder serves every lane of ``infer_stream``: launch
-    and copy of a batch run in order on one stream before the next batch is encoded."""
+class MaskRleEncoder(PooledMaskEncoder):
+    """The pooled encoder (mask_pool.py) of fx_mask_rle_encode: a slot's stream is its counts, ``fetch()`` returns per image the RLE dicts
+    {"size": [H, W], "counts": [...]} of its detections, in slot order."""
+
+    CALL, LIMITS = "fx_mask_rle", "Q (H W + 1) < 2^31"
 
     def __init__(self, B: int, Q: int, H: int, W: int, device, capacity: Optional[int] = None):
-        import torch
+        super().__init__(B, Q, H, W, device, capacity)
+        self.rle_len, self.rle_off, self.rle_counts = self.meta[0], self.meta[1], self.pool
 
-        from ._lib import load
+    @staticmethod
+    def sizes(Q, H, W, capacity=None):
+        return (default_capacity(Q, W) if capacity is None else int(capacity),)
 
-        self.lib = load("bf16")   # inference surface: the bf16 product library (the kernel is the same in both)
-        self.device = torch.device(device)
-        self.B, self.Q, self.H, self.W = int(B), int(Q), int(H), int(W)
-        self.capacity = default_capacity(Q, W) if capacity is None else int(capacity)
-        if self.capacity < 1:
-            raise ValueError(f"MaskRleEncoder: capacity = {capacity!r} must be >= 1")
-        nb = int(self.lib.fx_mask_rle_workspace_bytes(self.B, self.Q, self.H, self.W))
-        if nb == 0:
-            raise ValueError(f"MaskRleEncoder: B = {B}, Q = {Q}, H = {H}, W = {W} is outside the kernel's limits (Q (H W + 1) < 2^31)")
-        i32 = dict(dtype=torch.int32, device=self.device)
-        self.meta = torch.zeros(2, self.B, self.Q, **i32)      # rle_len, rle_off: one copy back
-        self.rle_len, self.rle_off = self.meta[0], self.meta[1]
-        self.rle_counts = torch.zeros(self.B, self.capacity, **i32)
-        self.workspace = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        self._host = None          # pinned [B, capacity], made with the first fetch
-        self._res = None
-        self.last_d2h_bytes = 0    # of the last fetch, fallback words included
-        self.last_fallback = 0     # slots the last fetch encoded on the host
-        self.total_fallback = 0    # ... and every fetch of this encoder, out of total_masks
-        self.total_masks = 0
+    def _det_counts(self, ln):
+        return (ln > 0).sum(axis=1), 0      # every mask has at least one count, and nothing more is copied
 
-    def key(self):
-        return (self.B, self.Q, self.H, self.W, self.device, self.capacity)
+    def _decode(self, counts):
+        return {"size": [self.H, self.W], "counts": counts.tolist()}
 
-    def encode(self, res) -> None:
-        """``res``: an engine plan or the processor's device results (``mask_words`` [B, Q, H, ceil(W / 32)], ``det_count``, ``det_boxes``)."""
-        import torch
+    def _encode_words(self, words):
+        return encode_words_numpy(words, self.W)
 
-        from ._lib import check
-
-        words = res.mask_words
-        shape = (self.B, self.Q, self.H, (self.W + 31) // 32)
-        if tuple(words.shape) != shape or words.dtype != torch.int32 or not words.is_contiguous() or words.device != self.device:
-            raise ValueError(f"MaskRleEncoder.encode: mask_words must be a contiguous int32 tensor {shape} on {self.device}, got "
-                             f"{words.dtype} {tuple(words.shape)} on {words.device}")
-        for name, t, shp in (("det_count", res.det_count, (self.B,)), ("det_boxes", res.det_boxes, (self.B, self.Q, 4))):
-            if tuple(t.shape) != shp or t.dtype != torch.int32 or not t.is_contiguous() or t.device != self.device:
-                raise ValueError(f"MaskRleEncoder.encode: {name} must be a contiguous int32 tensor {shp} on {self.device}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        check(self.lib.fx_mask_rle_encode(words.data_ptr(), res.det_count.data_ptr(), res.det_boxes.data_ptr(), self.B, self.Q, self.H, self.W,
-                                          self.capacity, self.rle_len.data_ptr(), self.rle_off.data_ptr(), self.rle_counts.data_ptr(),
-                                          self.workspace.data_ptr(), self.workspace.numel(), stream), "fx_mask_rle_encode")
-        self._res = res
-
-    def fetch(self) -> List[List[dict]]:
-        """Per image the list of {"size": [H, W], "counts": [...]} of its detections, in slot order."""
-        import torch
-
-        if self._res is None:
-            raise RuntimeError("MaskRleEncoder.fetch: nothing was encoded")
-        meta = self.meta.cpu().numpy().astype(np.int64)      # synchronises the stream
-        ln, off = meta[0], meta[1]
-        stored = (ln > 0) & (off + ln <= self.capacity)
-        used = np.where(stored, off + ln, 0).max(axis=1)
-        if self._host is None:
-            self._host = torch.empty(self.B, self.capacity, dtype=torch.int32, pin_memory=True)
-        for b in range(self.B):
-            if used[b]:
-                self._host[b, :used[b]].copy_(self.rle_counts[b, :used[b]], non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        pool = self._host.numpy()
-        self.last_d2h_bytes = int(meta.size * 4 + used.sum() * 4)
-        size, out, fell = [self.H, self.W], [], 0
-        for b in range(self.B):
-            n = int((ln[b] > 0).sum())      # detections are the leading slots
-            lost = np.flatnonzero(~stored[b, :n])
-            words = {}
-            if len(lost):      # did not fit the pool: the same counts from the slots' bit words, on the host (one copy per image)
-                w = self._res.mask_words[b, :n][torch.from_numpy(lost).to(self.device)].cpu().numpy()
-                self.last_d2h_bytes += w.nbytes
-                words = dict(zip(lost.tolist(), w))
-                fell += len(lost)
-            out.append([{"size": list(size), "counts": pool[b, off[b, j]:off[b, j] + ln[b, j]].tolist()} if stored[b, j]
-                        else encode_words_numpy(words[j], self.W) for j in range(n)])
-        self.last_fallback = fell
-        self.total_fallback += fell
-        self.total_masks += int((ln > 0).sum())
-        if fell:
-            warnings.warn(f"mask_format='rle': {fell} of {int((ln > 0).sum())} masks did not fit the pool of {self.capacity} counts per image and "
-                          f"were encoded on the host (raise the capacity)", RuntimeWarning, stacklevel=3)
-        return out
-
-
-def encoder_for(current: Optional[MaskRleEncoder], res, capacity: Optional[int] = None) -> MaskRleEncoder:
-    """``current`` when it fits ``res`` (shape, device, capacity), a new encoder otherwise."""
-    B, Q, H, _ = res.mask_words.shape
-    W = int(getattr(res, "mask_width", res.mask_words.shape[3] * 32))
-    dev = res.mask_words.device
-    cap = default_capacity(Q, W) if capacity is None else int(capacity)
-    if current is not None and current.key() == (B, Q, H, W, dev, cap):
-        return current
-    return MaskRleEncoder(B, Q, H, W, dev, cap)
+    def _warning(self, fell, masks):
+        return (f"mask_format='rle': {fell} of {masks} masks did not fit the pool of {self.capacity} counts per image and "
+                f"were encoded on the host (raise the capacity)")

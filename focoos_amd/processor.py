@@ -466,8 +466,9 @@ class MaskFormerProcessor(DETRProcessor):
     @staticmethod
     def unpack_masks(words: torch.Tensor, H: int, W: int) -> np.ndarray:
         """int32 [n, H, ceil(W/32)] bit-packed -> bool [n, H, W]."""
-        w = words.cpu().numpy().view(np.uint8)
-        return np.unpackbits(w, axis=-1, bitorder="little").reshape(words.shape[0], H, -1)[..., :W].astype(bool)
+        from .mask_pool import unpack_words
+
+        return unpack_words(words.cpu().numpy()[..., :(W + 31) // 32], W).reshape(words.shape[0], H, W)      # rows may be padded with words
 
     def pack_detections(self, res, class_names: Sequence[str] = (), encode_masks: bool = True,
                         mask_format: str = "png") -> List[FocoosDetections]:
@@ -477,26 +478,24 @@ class MaskFormerProcessor(DETRProcessor):
         copied or unpacked unless a slot overflowed the pool of ``self.rle_capacity`` counts per image); "polygon" traces the masks' boundaries
         on the device (mask_polygon.py, DESIGN 19: ``FocoosDet.polygons`` is set, ``mask`` and ``rle`` are None; ``self.polygon_capacity`` words per
         image); "none" is ``encode_masks=False``."""
-        from .mask_rle import check_mask_format, encoder_for
+        from .mask_rle import check_mask_format
 
-        if check_mask_format(mask_format, what="pack_detections") == "rle":
-            enc = self._rle_encoder = encoder_for(self._rle_encoder, res, self.rle_capacity)
+        if check_mask_format(mask_format, what="pack_detections") in ("rle", "polygon"):
+            from .mask_polygon import MaskPolygonEncoder
+            from .mask_pool import encoder_for
+            from .mask_rle import MaskRleEncoder
+
+            if mask_format == "rle":
+                enc = self._rle_encoder = encoder_for(MaskRleEncoder, self._rle_encoder, res, self.rle_capacity)
+            else:
+                enc = self._polygon_encoder = encoder_for(MaskPolygonEncoder, self._polygon_encoder, res, self.polygon_capacity,
+                                                          self.polygon_max_edges)
             enc.encode(res)      # on the current stream, before the copies below wait for it
-            rles = enc.fetch()
+            items, field = enc.fetch(), "rle" if mask_format == "rle" else "polygons"      # the FocoosDet field an item goes to
             s, l, b = res.det_scores.cpu().tolist(), res.det_labels.cpu().tolist(), res.det_boxes.cpu().tolist()
             return [FocoosDetections(detections=[
-                FocoosDet(bbox=b[i][j], conf=s[i][j], cls_id=l[i][j], label=class_names[l[i][j]] if class_names else None, rle=r)
-                for j, r in enumerate(ri)]) for i, ri in enumerate(rles)]
-        if mask_format == "polygon":
-            from .mask_polygon import encoder_for as polygon_encoder_for
-
-            enc = self._polygon_encoder = polygon_encoder_for(self._polygon_encoder, res, self.polygon_capacity, self.polygon_max_edges)
-            enc.encode(res)      # on the current stream, before the copies below wait for it
-            polys = enc.fetch()
-            s, l, b = res.det_scores.cpu().tolist(), res.det_labels.cpu().tolist(), res.det_boxes.cpu().tolist()
-            return [FocoosDetections(detections=[
-                FocoosDet(bbox=b[i][j], conf=s[i][j], cls_id=l[i][j], label=class_names[l[i][j]] if class_names else None, polygons=r)
-                for j, r in enumerate(ri)]) for i, ri in enumerate(polys)]
+                FocoosDet(bbox=b[i][j], conf=s[i][j], cls_id=l[i][j], label=class_names[l[i][j]] if class_names else None, **{field: r})
+                for j, r in enumerate(ri)]) for i, ri in enumerate(items)]
         encode_masks = encode_masks and mask_format != "none"
         n = res.det_count.cpu().tolist()
         s, l, b = res.det_scores.cpu().tolist(), res.det_labels.cpu().tolist(), res.det_boxes.cpu().tolist()

@@ -23,10 +23,13 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 INVALID = -1   # FX_ERR_INVALID_ARGUMENT
 SENTINEL = -777
-SHAPES = [(5, 7), (33, 65), (64, 64), (70, 100)]
+SHAPES = [(5, 7), (33, 65), (64, 64), (70, 100), (6, 300)]
 B, Q, COUNT = 2, 3, [3, 1]
-SLOTS = ((0, 0), (0, 1), (0, 2), (1, 0))
 GARBAGE_BOX = [-5, 7, 10 ** 9, -3]
+
+
+def _slots(count):
+    return [(b, j) for b in range(B) for j in range(count[b])]      # the detections in (image, slot) order
 
 
 def _stream():
@@ -79,18 +82,20 @@ def cases(H, W):
     return _CASES[(H, W)]
 
 
-def run(H, W, slots, capacity, max_edges, sentinel=SENTINEL):
-    """One fx_mask_polygon_encode call on B = 2, Q = 3, det_count = [3, 1]: ``slots`` = four (mask, box) for (0, 0), (0, 1), (0, 2), (1, 0);
-    slots 1 and 2 of image 1 hold garbage words and boxes.  Returns (words, poly_len, poly_off, pool) as numpy arrays."""
+def run(H, W, slots, capacity, max_edges, sentinel=SENTINEL, Q=Q, count=COUNT):
+    """One fx_mask_polygon_encode call on B = 2, Q = 3, det_count = [3, 1] unless given: ``slots`` = the (mask, box) of the detections, by
+    default four for (0, 0), (0, 1), (0, 2), (1, 0); the other slots (1 and 2 of image 1) hold garbage words and boxes.  Returns (words,
+    poly_len, poly_off, pool) as numpy arrays."""
     lib = _lib.load()
     rs = np.random.RandomState(H + W)
     W32 = (W + 31) // 32
     words = rs.randint(-2 ** 31, 2 ** 31 - 1, (B, Q, H, W32), dtype=np.int64).astype(np.int32)
     boxes = np.tile(np.array(GARBAGE_BOX, np.int32), (B, Q, 1))
-    for (b, j), (m, box) in zip(SLOTS, slots):
+    assert len(slots) == sum(count)
+    for (b, j), (m, box) in zip(_slots(count), slots):
         words[b, j], boxes[b, j] = R.pack_words(m), box
     d_words, d_boxes = torch.from_numpy(words).to(DEV), torch.from_numpy(boxes).to(DEV)
-    d_count = torch.tensor(COUNT, dtype=torch.int32, device=DEV)
+    d_count = torch.tensor(count, dtype=torch.int32, device=DEV)
     ln = torch.full((B, Q), SENTINEL, dtype=torch.int32, device=DEV)
     off = torch.full((B, Q), SENTINEL, dtype=torch.int32, device=DEV)
     pool = torch.full((B, capacity), sentinel, dtype=torch.int32, device=DEV)
@@ -104,18 +109,20 @@ def run(H, W, slots, capacity, max_edges, sentinel=SENTINEL):
     return words, ln.cpu().numpy(), off.cpu().numpy(), pool.cpu().numpy()
 
 
-def check(H, W, chosen, capacity, max_edges, unstored, unfit=()):
-    """Runs the call on four cases and checks everything the contract states; ``unstored`` = the exact set of (b, j) among the detections
-    that must not be stored, ``unfit`` = those of them whose poly_len must be -1."""
-    refs, edges = [c[3] for c in chosen], [c[4] for c in chosen]
-    words, ln, off, pool = run(H, W, [(c[1], c[2]) for c in chosen], capacity, max_edges)
-    lengths = [[len(refs[0]), len(refs[1]), len(refs[2])], [len(refs[3]), 99, 99]]
-    want_ln, want_off, want_st = R.capacity_rule(lengths, [edges[:3], [edges[3], 9, 9]], COUNT, capacity, max_edges)
+def check(H, W, chosen, capacity, max_edges, unstored, unfit=(), Q=Q, count=COUNT):
+    """Runs the call on the cases (four by default) and checks everything the contract states; ``unstored`` = the exact set of (b, j) among
+    the detections that must not be stored, ``unfit`` = those of them whose poly_len must be -1."""
+    refs = [c[3] for c in chosen]
+    words, ln, off, pool = run(H, W, [(c[1], c[2]) for c in chosen], capacity, max_edges, Q=Q, count=count)
+    lengths, edges = np.full((B, Q), 99), np.full((B, Q), 9)      # of the garbage slots: ignored by the rule
+    for (b, j), c in zip(_slots(count), chosen):
+        lengths[b, j], edges[b, j] = len(c[3]), c[4]
+    want_ln, want_off, want_st = R.capacity_rule(lengths.tolist(), edges.tolist(), count, capacity, max_edges)
     assert np.array_equal(ln, want_ln) and np.array_equal(off, want_off)      # true lengths, stored or not; 0 for the garbage slots
-    assert {(b, j) for b in range(B) for j in range(COUNT[b]) if not want_st[b, j] and lengths[b][j]} == set(unstored)
+    assert {(b, j) for (b, j) in _slots(count) if not want_st[b, j] and lengths[b, j]} == set(unstored)
     assert {(b, j) for b in range(B) for j in range(Q) if ln[b, j] < 0} == set(unfit)
     untouched = np.ones_like(pool, bool)
-    for (b, j), ref in zip(SLOTS, refs):
+    for (b, j), ref in zip(_slots(count), refs):
         if not want_st[b, j]:
             continue
         got = pool[b, off[b, j]:off[b, j] + ln[b, j]]
@@ -168,6 +175,17 @@ def test_a_slot_over_max_edges_is_minus_one_and_shifts_nothing():
     # one edge more: slot 1 fits, and now slot 2 finds no room behind it
     check(H, W, order, cap, me + 1, unstored={(0, 2)}, unfit={(0, 2)})
     check(H, W, order, cap, me + 1 + stripe[4], unstored=())      # room for all three
+
+
+def test_slot_offsets_over_260_slots():
+    """poly_off of slot j sums j lengths: from slot 257 on the 256 threads of the emit kernel take a second length each, and all four
+    wavefronts contribute.  The masks are the shape's cases, cyclically.  The edge workspace has room for 260 slots at the frame's limit of
+    L = 2 H W + H + W = 82 edges, and the pool of 260 x 89 words is four times what these masks take together (the largest, the
+    checkerboard, takes 90): everything is stored, which ``unstored=()`` asserts."""
+    H, W, Qn = 5, 7, 260
+    count = [Qn, 1]
+    cs = cases(H, W)
+    check(H, W, [cs[i % len(cs)] for i in range(sum(count))], Qn * 89, Qn * 82, unstored=(), Q=Qn, count=count)
 
 
 def test_two_calls_give_byte_equal_pools():

@@ -22,9 +22,13 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 INVALID = -1   # FX_ERR_INVALID_ARGUMENT
 SENTINEL = -777
-SHAPES = [(5, 7), (33, 65), (64, 64), (70, 100)]
+SHAPES = [(5, 7), (33, 65), (64, 64), (70, 100), (6, 300)]      # 300 columns: the scan kernel carries its sum and its max across a chunk of 256
 B, Q, COUNT = 2, 3, [3, 1]
 GARBAGE_BOX = [-5, 7, 10 ** 9, -3]
+
+
+def _slots(count):
+    return [(b, j) for b in range(B) for j in range(count[b])]      # the detections in (image, slot) order
 
 
 def _stream():
@@ -74,18 +78,20 @@ def cases(H, W):
     return _CASES[(H, W)]
 
 
-def run(H, W, slots, capacity, sentinel=SENTINEL):
-    """One fx_mask_rle_encode call on B = 2, Q = 3, det_count = [3, 1]: ``slots`` = four (mask, box) for (0, 0), (0, 1), (0, 2), (1, 0); slots 1
-    and 2 of image 1 hold garbage words and boxes.  Returns (words, rle_len, rle_off, pool) as numpy arrays."""
+def run(H, W, slots, capacity, sentinel=SENTINEL, Q=Q, count=COUNT):
+    """One fx_mask_rle_encode call on B = 2, Q = 3, det_count = [3, 1] unless given: ``slots`` = the (mask, box) of the detections, by default
+    four for (0, 0), (0, 1), (0, 2), (1, 0); the other slots (1 and 2 of image 1) hold garbage words and boxes.  Returns (words, rle_len,
+    rle_off, pool) as numpy arrays."""
     lib = _lib.load()
     rs = np.random.RandomState(H + W)
     W32 = (W + 31) // 32
     words = rs.randint(-2 ** 31, 2 ** 31 - 1, (B, Q, H, W32), dtype=np.int64).astype(np.int32)
     boxes = np.tile(np.array(GARBAGE_BOX, np.int32), (B, Q, 1))
-    for (b, j), (m, box) in zip(((0, 0), (0, 1), (0, 2), (1, 0)), slots):
+    assert len(slots) == sum(count)
+    for (b, j), (m, box) in zip(_slots(count), slots):
         words[b, j], boxes[b, j] = R.pack_words(m), box
     d_words, d_boxes = torch.from_numpy(words).to(DEV), torch.from_numpy(boxes).to(DEV)
-    d_count = torch.tensor(COUNT, dtype=torch.int32, device=DEV)
+    d_count = torch.tensor(count, dtype=torch.int32, device=DEV)
     ln = torch.full((B, Q), SENTINEL, dtype=torch.int32, device=DEV)
     off = torch.full((B, Q), SENTINEL, dtype=torch.int32, device=DEV)
     pool = torch.full((B, capacity), sentinel, dtype=torch.int32, device=DEV)
@@ -99,15 +105,17 @@ def run(H, W, slots, capacity, sentinel=SENTINEL):
     return words, ln.cpu().numpy(), off.cpu().numpy(), pool.cpu().numpy()
 
 
-def check(H, W, slots, refs, capacity, unstored):
+def check(H, W, slots, refs, capacity, unstored, Q=Q, count=COUNT):
     """Runs the call and checks everything the contract states; ``unstored`` = the exact set of (b, j) that must not be stored."""
-    words, ln, off, pool = run(H, W, slots, capacity)
-    lengths = [[len(refs[0]), len(refs[1]), len(refs[2])], [len(refs[3]), 99, 99]]
-    want_ln, want_off, want_st = R.capacity_rule(lengths, COUNT, capacity)
+    words, ln, off, pool = run(H, W, slots, capacity, Q=Q, count=count)
+    lengths = np.full((B, Q), 99)      # of the garbage slots: ignored by the rule
+    for (b, j), ref in zip(_slots(count), refs):
+        lengths[b, j] = len(ref)
+    want_ln, want_off, want_st = R.capacity_rule(lengths.tolist(), count, capacity)
     assert np.array_equal(ln, want_ln) and np.array_equal(off, want_off)      # true lengths, stored or not; 0 for the garbage slots
-    assert {(b, j) for b in range(B) for j in range(COUNT[b]) if not want_st[b, j]} == set(unstored)
+    assert {(b, j) for (b, j) in _slots(count) if not want_st[b, j]} == set(unstored)
     untouched = np.ones_like(pool, bool)
-    for (b, j), ref in zip(((0, 0), (0, 1), (0, 2), (1, 0)), refs):
+    for (b, j), ref in zip(_slots(count), refs):
         if not want_st[b, j]:
             continue
         got = pool[b, off[b, j]:off[b, j] + ln[b, j]]
@@ -143,6 +151,16 @@ def test_capacity_rule_and_sentinel():
     check(H, W, [(c[1], c[2]) for c in order], [c[3] for c in order], cap, unstored={(0, 2)})
     # one count more and everything is stored
     check(H, W, [(c[1], c[2]) for c in order], [c[3] for c in order], cap + 1, unstored=())
+
+
+def test_slot_offsets_over_260_slots():
+    """rle_off of slot j sums j lengths: from slot 257 on the 256 threads of the emit kernel take a second length each, and all four wavefronts
+    contribute.  The masks are the shape's cases, cyclically; the pool holds the most 260 masks of this frame can have."""
+    H, W, Qn = 5, 7, 260
+    count = [Qn, 1]
+    cs = cases(H, W)
+    chosen = [cs[i % len(cs)] for i in range(sum(count))]
+    check(H, W, [(c[1], c[2]) for c in chosen], [c[3] for c in chosen], Qn * (H * W + 1), unstored=(), Q=Qn, count=count)
 
 
 def test_two_calls_give_byte_equal_pools():
