@@ -65,6 +65,18 @@ def bf16_rne(ref: torch.Tensor) -> torch.Tensor:
     return torch.round(r / u) * u        # r / u is exact (u a power of two); torch.round rounds half to even
 
 
+def elem_rne(ref: torch.Tensor, dtype) -> torch.Tensor:
+    """bf16_rne for either 16-bit element type: fp64 -> the nearest value of `dtype` (torch.bfloat16 or torch.float16), ties to even, in
+    ONE rounding, returned as fp64.  fp16 has 11 significand bits and subnormals spaced 2^-24 below 2^-14; no input here overflows."""
+    if dtype == torch.bfloat16:
+        return bf16_rne(ref)
+    assert dtype == torch.float16
+    r = ref.double()
+    e = torch.frexp(r.abs().clamp_min(2.0 ** -14)).exponent
+    u = pow2(e - 11)
+    return torch.round(r / u) * u
+
+
 def ulp_stats(got: torch.Tensor, ref: torch.Tensor, mag: torch.Tensor, fp32_out: bool = False) -> dict:
     """Worst error in output ulps (over outputs with |ref| >= mag / 256), the smallest c with |got-ref| <= ulp + c*mag everywhere, and the
     RNE agreement rate (bf16 only)."""
@@ -149,8 +161,9 @@ def gemm_ref64(x, w, bias=None, act=None, residual=None):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Guarded device buffers and the per-element gate of the kernels' direct tests (tests/test_gpu_train_token_ops.py,
-# tests/test_gpu_infer_token_ops.py, tests/test_gpu_train_matrix_ops.py).  The element type is an argument: nothing here reads process
-# state.  The sentinel guards STORES; an fp32 accumulation into it (1.5e16) leaves no trace - see acc_buf in test_gpu_train_matrix_ops.py.
+# tests/test_gpu_infer_token_ops.py, tests/test_gpu_train_matrix_ops.py, tests/test_gpu_seg_head_ops.py).  The element type is an
+# argument: nothing here reads process state.  The sentinel guards STORES; an fp32 accumulation into it (1.5e16) leaves no trace - see
+# acc_buf in test_gpu_train_matrix_ops.py.
 GR = 2                      # guard rows before and after every buffer
 U32 = 2.0 ** -24            # unit roundoff of fp32
 _SENT = {1: 0x5A, 2: 0x5A5A, 4: 0x5A5A5A5A}
