@@ -91,6 +91,14 @@ class FxRcStage(C.Structure):
     ]
 
 
+class FxFrameDesc(C.Structure):
+    """include/focoos_amd.h fx_frame_desc (64 bytes)"""
+    _fields_ = [
+        ("plane", C.c_void_p * 3), ("pitch", C.c_int32 * 3), ("height", C.c_int32), ("width", C.c_int32), ("format", C.c_int32),
+        ("matrix", C.c_int32), ("reserved", C.c_int32 * 3),
+    ]
+
+
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 
 # name -> argtypes (every function returns int unless noted); mirrors include/focoos_amd.h
@@ -123,6 +131,7 @@ SIGNATURES = {
     "fx_augment_labels": [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp],
     "fx_resize_bilinear_u8": [_vp, _i, _i, _vp, _i, _i, _vp],
     "fx_tile_gather_u8_f32": [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "fx_frames_ingest": [_vp, _vp, _i, _vp, _i, _i, _i, _vp],
     "fx_merge_detections_workspace_bytes": [_i, _i],
     "fx_merge_detections_nms": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "fx_annotate_labels_from_detections": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
@@ -310,7 +319,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 21  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 22  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:

@@ -2,16 +2,15 @@
 //
 //   fx_tile_gather_u8_f32    N windows of one uint8 HWC frame -> N bilinearly resized float32 views of one size, in one launch.  The value of a
 //                            view is, bit for bit, what fx_resize_bilinear_u8 (pixel_ops.hip) writes for a contiguous copy of its window:
-//                            the tap / weight arithmetic below is that kernel's in the same operation order.  pixel_ops.hip is compiled
-//                            with the compiler's default contraction, which fuses three of its multiply-adds; they are spelled out here
-//                            as fmaf so that the equality does not hang on the optimiser making the same choice twice
-//                            (tests/test_gpu_tiled.py compares the two kernels bit for bit).
+//                            the tap / weight arithmetic is that kernel's in the same operation order (resize_common.h, shared with
+//                            frame_ops.hip; tests/test_gpu_tiled.py compares the two kernels bit for bit).
 //   fx_merge_detections_nms  the per-view packed detections -> frame coordinates -> class-aware greedy NMS -> one packed list.  Integer
 //                            areas, one IEEE operation per side of the decision (contraction is off in this unit), so the result is a
 //                            pure function of the inputs and is compared for equality with the numpy restatement (tests/tiled_ref.py).
 //
 // fp32 / fp64 / integer only: the FX_FP16 switch of the second library does not touch this file.
 #include "det_common.h"
+#include "resize_common.h"
 
 #pragma clang fp contract(off)
 
@@ -21,18 +20,6 @@
 #define TG_BY 4    // rows per workgroup
 
 // ---- gather ------------------------------------------------------------------------------------------------------------------------------
-// Bilinear source index exactly as ATen's upsample_bilinear2d (align_corners=False) and pixel_ops.hip's bilinear_src:
-//   src = scale * (dst + 0.5) - 0.5 (one fused multiply-add there, so one here), clamped at 0; scale = in / out.
-__device__ __forceinline__ void tg_bilinear_src(int dst, float scale, int in_size, int& i0, int& i1, float& l0, float& l1) {
-  float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
-  src = src < 0.0f ? 0.0f : src;
-  i0 = (int)src;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.0f - l1;
-}
-
 // One thread = 4 consecutive output pixels of one row (12 floats, 48 bytes): three 16-byte stores when every row starts 16-byte aligned
 // (VEC: Wo % 4 == 0 and an aligned base), twelve scalar stores otherwise.  Grid (row segments of 256 pixels, groups of 4 rows, views); the
 // window record is read once per workgroup.  Taps are clamped to the WINDOW (in_size = its extent), then shifted by its origin.
@@ -50,7 +37,7 @@ __global__ __launch_bounds__(TG_BX * TG_BY) void tile_gather_kernel(const uint8_
   const float sh = (float)wh / (float)Ho, sw = (float)ww / (float)Wo;
   int h0, h1;
   float lh0, lh1;
-  tg_bilinear_src(ho, sh, wh, h0, h1, lh0, lh1);
+  fx_resize_src(ho, sh, wh, h0, h1, lh0, lh1);
   const uint8_t* r0 = frame + ((int64_t)(y0 + h0) * W + x0) * 3;
   const uint8_t* r1 = frame + ((int64_t)(y0 + h1) * W + x0) * 3;
   float v[12];
@@ -59,15 +46,12 @@ __global__ __launch_bounds__(TG_BX * TG_BY) void tile_gather_kernel(const uint8_
     const int wo = wo0 + k < Wo ? wo0 + k : Wo - 1;   // a ragged last thread recomputes the last pixel, stores are guarded below
     int w0, w1;
     float lw0, lw1;
-    tg_bilinear_src(wo, sw, ww, w0, w1, lw0, lw1);
+    fx_resize_src(wo, sw, ww, w0, w1, lw0, lw1);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       float p00 = r0[w0 * 3 + c], p01 = r0[w1 * 3 + c];
       float p10 = r1[w0 * 3 + c], p11 = r1[w1 * 3 + c];
-      // lh0 * (lw0 * p00 + lw1 * p01) + lh1 * (lw0 * p10 + lw1 * p11) as resize_u8_kernel evaluates it: the first product of each sum
-      // rounded, the second fused into the addition
-      const float top = fmaf(lw1, p01, lw0 * p00), bottom = fmaf(lw1, p11, lw0 * p10);
-      v[k * 3 + c] = fmaf(lh0, top, lh1 * bottom);
+      v[k * 3 + c] = fx_resize_filter(lh0, lh1, lw0, lw1, p00, p01, p10, p11);
     }
   }
   float* out = y + (((int64_t)n * Ho + ho) * Wo + wo0) * 3;

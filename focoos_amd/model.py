@@ -285,7 +285,9 @@ class FocoosModel:
     def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate: bool = False, tracker=None,
                     mask_format: str = "png", zones=None) -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
-        reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``annotate``: every result
+        reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``inputs`` may also be a
+        ``frames.FrameBatch`` of NV12 / I420 / BGR / RGB video frames, host or device: the results are those of the same frames passed as
+        RGB arrays (frames.py).  ``annotate``: every result
         also carries ``.image``, the uint8 input at its original size with the detections drawn on it on the device (annotate.py);
         non-uint8 inputs then raise ValueError.  ``tracker``: a ``tracking.DeviceTracker`` of ``len(inputs)`` streams, for callers who
         feed one batch per call - image b is the next frame of stream b, and every tracked detection gets its ``track_id`` (the
@@ -297,9 +299,11 @@ class FocoosModel:
         packed device results, so they compose.  ``zones``: a ``zones.DeviceZones`` of ``len(inputs)`` streams, the counterpart of
         ``tracker`` for zone and line counting (zones.py): every result carries ``.zones``; a DeviceZones built on a tracker
         runs that tracker (``tracker`` must be None or that one)."""
+        from .frames import as_frame_batch, drawable
         from .mask_rle import check_mask_format
 
         check_mask_format(mask_format, self.model.family, "infer_batch")
+        inputs = as_frame_batch(inputs) or inputs      # a FrameBatch (or one Frame) goes where a list of images goes (frames.py, DESIGN 21)
         if zones is not None:
             from . import zones as Z
 
@@ -345,7 +349,7 @@ class FocoosModel:
             Z.attach(out, zones.fetch())
         t3 = perf_counter()
         if annotate:
-            annotate_results(self, inputs, images, pl, out)
+            annotate_results(self, drawable(inputs, images, self.model.device), images, pl, out)
         t4 = perf_counter()
         for o in out:
             o.latency = InferLatency(preprocess=round(t1 - t0, 3), inference=round(t2 - t1, 3), postprocess=round(t3 - t2, 3),
@@ -381,6 +385,7 @@ class FocoosModel:
         from collections import deque
 
         from . import zones as Z
+        from .frames import as_frame_batch, drawable
         from .mask_rle import check_mask_format
 
         Z.check_detections_flag(detections, zones, annotate, mask_format)
@@ -421,6 +426,7 @@ class FocoosModel:
             return out
 
         for inputs in batches:
+            inputs = as_frame_batch(inputs) or inputs
             if annotate:
                 check_inputs(inputs, "infer_stream")
             images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
@@ -441,7 +447,7 @@ class FocoosModel:
                 yield finish()
             pending.append(pipe.submit(x, sizes, thr))
             if annotate:
-                frames[pending[-1]] = (inputs, x)      # the submitted batch stays referenced until it is drawn
+                frames[pending[-1]] = (drawable(inputs, x, x.device), x)      # the submitted batch stays referenced until it is drawn
         while pending:
             yield finish()
         if track is not None and not isinstance(track, TrackerConfig):
@@ -456,6 +462,7 @@ class FocoosModel:
         pipe, key, pending = None, None, deque()
 
         from .annotate import annotate_results, check_inputs
+        from .frames import as_frame_batch, drawable
 
         def finish():
             ticket, host, drawn = pending.popleft()
@@ -466,6 +473,7 @@ class FocoosModel:
             return out
 
         for inputs in batches:
+            inputs = as_frame_batch(inputs) or inputs
             if annotate:
                 check_inputs(inputs, "infer_stream")
             images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
@@ -479,18 +487,22 @@ class FocoosModel:
             if len(pending) >= pipe.depth:      # the lane about to be reused still holds an unread result
                 yield finish()
             host = {"logits": torch.empty(B, self.model.num_classes, dtype=torch.float32, pin_memory=True)}
-            pending.append((pipe.submit(x, None, thr, host), host, (inputs, x) if annotate else None))
+            pending.append((pipe.submit(x, None, thr, host), host, (drawable(inputs, x, x.device), x) if annotate else None))
         while pending:
             yield finish()
 
     def __call__(self, inputs, **kwargs) -> FocoosDetections:
-        lst = inputs if isinstance(inputs, list) else [inputs]
+        from .frames import as_frame_batch
+
+        lst = as_frame_batch(inputs) or (inputs if isinstance(inputs, list) else [inputs])
         return self.infer_batch(lst, threshold=kwargs.get("threshold"), mask_format=kwargs.get("mask_format", "png"))[0]
 
     def infer(self, image, threshold: Optional[float] = None, annotate: bool = False, mask_format: str = "png") -> FocoosDetections:
         """focoos_model.py:370-416: one picture (path, PIL image, array, tensor) -> FocoosDetections.  ``annotate``: ``.image`` is the
         picture (np.uint8 [H, W, 3] RGB, original size) with the detections drawn on it on the device (annotate.py; the input itself
-        when nothing was detected) and ``.latency.annotate`` / ``.latency.imload`` are set.  ``mask_format``: as in ``infer_batch``."""
+        when nothing was detected) and ``.latency.annotate`` / ``.latency.imload`` are set.  ``mask_format``: as in ``infer_batch``.
+        ``image`` may also be a ``frames.Frame`` (NV12, I420, BGR or RGB video frame, host or device)."""
+        from .frames import Frame, FrameBatch
         from .mask_rle import check_mask_format
 
         check_mask_format(mask_format, self.model.family, "infer")
@@ -502,7 +514,8 @@ class FocoosModel:
         if not annotate:
             return self(image, threshold=threshold, mask_format=mask_format)
         imload = perf_counter() - t0
-        res = self.infer_batch([image], threshold=threshold, annotate=True, mask_format=mask_format)[0]
+        res = self.infer_batch(image if isinstance(image, (Frame, FrameBatch)) else [image], threshold=threshold, annotate=True,
+                               mask_format=mask_format)[0]
         res.latency.imload = round(imload, 3)
         return res
 
@@ -522,7 +535,10 @@ class FocoosModel:
         NotImplementedError before anything touches the GPU.  ``annotate``: ``.image`` is the frame with the merged detections drawn on
         it (the resident frame is drawn on the device and copied back beside the packed result; annotate.py).  ``mask_format``: tiled
         inference has no masks to hand out - "rle" and "polygon" raise NotImplementedError, another unknown value ValueError."""
+        from .frames import refuse_frames
         from .mask_rle import check_mask_format
+
+        refuse_frames(image, "infer_tiled")      # before anything loads the library
         from .tiled import infer_tiled as _infer_tiled
 
         if check_mask_format(mask_format, None, "infer_tiled") in ("rle", "polygon"):

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check
+from .frames import as_frame_batch
 from .ports import ClassificationModelOutput, DatasetEntry, DETRModelOutput, DynamicAxes, FocoosDet, FocoosDetections, MaskFormerModelOutput  # noqa: F401
 
 try:  # PIL is optional
@@ -59,6 +60,9 @@ class DETRProcessor:
                 return (h, w)
             raise ValueError(f"Unsupported input type: {type(img)}")
 
+        frames = as_frame_batch(inputs)
+        if frames is not None:
+            return frames.sizes
         if isinstance(inputs, list):
             return [one(i) for i in inputs]
         return [one(inputs)]
@@ -72,7 +76,13 @@ class DETRProcessor:
     def preprocess(self, inputs: ImageInput, device: torch.device, dtype: torch.dtype = torch.float32):
         """Returns (images, targets).  ``images`` is NHWC on ``device``: uint8 [B,H,W,3] when every input
         already has the target size (fused fast path), float32 [B,H,W,3] (0..255 scale, bilinearly resized)
-        otherwise.  The engine's ``FAIDetr.forward`` accepts both, as well as the reference's NCHW float."""
+        otherwise.  The engine's ``FAIDetr.forward`` accepts both, as well as the reference's NCHW float.  A ``frames.FrameBatch`` (or one
+        ``Frame``) gives, bit for bit, what the list of its frames converted to RGB arrays gives, in one launch (frames.py)."""
+        frames = as_frame_batch(inputs)
+        if frames is not None:
+            if self.training:
+                raise ValueError("During training, inputs should be a list of DetectionDatasetDict")
+            return frames.to_engine_input(self._target_size(), device), []
         lst = inputs if isinstance(inputs, list) else [inputs]
         if len(lst) > 0 and isinstance(lst[0], DatasetEntry):
             return self._preprocess_entries(lst, device)
@@ -374,7 +384,7 @@ class MaskFormerProcessor(DETRProcessor):
     def preprocess(self, inputs: ImageInput, device: torch.device, dtype: torch.dtype = torch.float32):
         """fai_mf/processor.py:60-97 (inference branch): images are batched at their own size; mixed sizes cannot be stacked
         (base_processor.py:294 torch.stack) and are rejected here as well."""
-        lst = inputs if isinstance(inputs, list) else [inputs]
+        lst = as_frame_batch(inputs) or (inputs if isinstance(inputs, list) else [inputs])
         if len(lst) > 0 and isinstance(lst[0], DatasetEntry):
             return self._preprocess_mask_entries(lst, device)
         sizes = set(self.get_image_sizes(lst))

@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 21
+#define FX_ABI_VERSION 22
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -514,6 +514,42 @@ int fx_zone_update(const int32_t* det_labels, const int32_t* det_boxes, const in
                    uint32_t* det_in, uint32_t* det_out, fx_stream_t stream);
 int fx_zone_reset(int32_t* st_id, int32_t* st_side, int32_t* in_total, int32_t* out_total, const int32_t* reg_first_host, int B, int max_tracks,
                   int b, int clear_counters, fx_stream_t stream);
+
+/* ---- Video frame ingest (ABI 22; csrc/frame_ops.hip): a batch of decoder / camera frames -> the engine's input, one
+ * launch.  A frame is 1-3 uint8 planes with a row pitch in bytes each:
+ *   FX_FRAME_RGB24 / BGR24  plane[0] = [H][W][3] packed (pitch >= 3 W)
+ *   FX_FRAME_NV12           plane[0] = Y [H][W] (pitch >= W), plane[1] = interleaved UV [(H+1)/2][(W+1)/2][2] (pitch >= 2 ((W+1)/2))
+ *   FX_FRAME_I420           plane[0] = Y, plane[1] = U, plane[2] = V, chroma planes [(H+1)/2][(W+1)/2] (pitch >= (W+1)/2)
+ * Chroma is replicated: pixel (y, x) uses the chroma sample (y >> 1, x >> 1).  With C = Y - 16 (limited range) or Y (full range),
+ * D = U - 128, E = V - 128, all int32, arithmetic shift, clip to 0..255:
+ *   R = clip((cy C + crv E + 128) >> 8), G = clip((cy C - cgu D - cgv E + 128) >> 8), B = clip((cy C + cbu D + 128) >> 8)
+ *   (cy, crv, cgu, cgv, cbu) = 601 limited (298, 409, 100, 208, 516), 601 full (256, 359, 88, 183, 454),
+ *                              709 limited (298, 459, 55, 136, 541), 709 full (256, 403, 48, 120, 475).
+ * BGR24 swaps the outer channels, RGB24 is a copy; `matrix` is not read for the packed formats but must be a known value.
+ *
+ * fx_frames_ingest: descs = fx_frame_desc [B], a DEVICE array (8-byte aligned) whose plane pointers are device pointers; descs_host = the
+ * same values in host memory.  out_f32 = 1: y = float32 [B][Ho][Wo][3] on the 0..255 scale; element (b, ...) is, bit for bit, what
+ * fx_resize_bilinear_u8 writes for a contiguous copy of frame b's converted RGB bytes resized to (Ho, Wo) (the conversion is applied per tap,
+ * before the filter; a frame of exactly (Ho, Wo) holds its bytes as floats); 16-byte stores when Wo % 4 == 0 and y is 16-byte aligned.
+ * out_f32 = 0: every frame must be exactly (Ho, Wo) and y = uint8 [B][Ho][Wo][3] holds the converted bytes; a thread moves 16 pixels with
+ * 16-byte loads and stores when W % 16 == 0, y is 16-byte aligned and every plane base and pitch of the batch is a multiple of 16 (8 for the
+ * I420 chroma planes), bytewise otherwise.  The host copy is validated before anything is launched: the planes of the format non-null,
+ * pitches as above, 1 <= H, W, Ho, Wo <= 16384, known format and matrix, the size rule of out_f32 = 0, 1 <= B <= 65535, out_f32 in {0, 1}, y
+ * aligned to its element.  The library cannot see the planes' allocations: their extents are the caller's to check.  Anything outside the
+ * contract: FX_ERR_INVALID_ARGUMENT, nothing launched, nothing written.  The same in both libraries. */
+enum { FX_FRAME_RGB24 = 0, FX_FRAME_BGR24 = 1, FX_FRAME_NV12 = 2, FX_FRAME_I420 = 3 };
+enum { FX_FRAME_BT601_LIMITED = 0, FX_FRAME_BT601_FULL = 1, FX_FRAME_BT709_LIMITED = 2, FX_FRAME_BT709_FULL = 3 };
+#define FX_FRAME_MAX_DIM 16384
+#define FX_FRAME_MAX_BATCH 65535
+typedef struct fx_frame_desc {
+  const uint8_t* plane[3];
+  int32_t pitch[3];
+  int32_t height, width;
+  int32_t format; /* FX_FRAME_RGB24, BGR24, NV12, I420 */
+  int32_t matrix; /* FX_FRAME_BT601_LIMITED ... FX_FRAME_BT709_FULL */
+  int32_t reserved[3];
+} fx_frame_desc; /* 64 bytes */
+int fx_frames_ingest(const fx_frame_desc* descs, const fx_frame_desc* descs_host, int B, void* y, int out_f32, int Ho, int Wo, fx_stream_t stream);
 
 /* F.max_pool2d(k=3,s=2,p=1) (resnet.py:254) on NHWC bf16. */
 int fx_maxpool3x3s2_nhwc_bf16(const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, fx_stream_t stream);
