@@ -5,10 +5,17 @@ bit-packed masks never leave the GPU: ``fx_annotate_labels_from_detections`` tur
 and ``fx_annotate_u8`` draws outlines, half-opacity masks and the labels in one pass over the uint8 frames (csrc/annotate.hip; the contract
 is in include/focoos_amd.h).  What is mirrored from the reference is the layer order (outlines, masks, labels), the palette and the class
 colouring, the half-opacity masks with the smaller instance on top and the label text; pixel equality with supervision / cv2 is NOT claimed
-(a bitmap font in a fixed cell, square label corners).  Keypoints are out of scope."""
+(a bitmap font in a fixed cell, square label corners).  Keypoints are out of scope.
+
+``annotate=Overlay(ids, zones, traces)`` in ``infer_stream`` / ``infer_batch`` adds the analytics half of the picture from
+what is already on the device when a lane finishes: "#17 " in front of a tracked label (``fx_annotate_labels_tracked``), the regions of a
+``DeviceZones`` tinted and outlined and its lines stroked, a tail of the last N anchors behind every track (``DeviceTraces``, ``fx_trace_update``;
+all three in one geometry pass, ``fx_annotate_overlay_u8``) and "door: 3" / "gate: 12/9" at every region (``fx_annotate_zone_records``, drawn by
+``fx_annotate_u8``).  csrc/overlay.hip; tests/overlay_ref.py restates the contracts.  ``annotate=True`` draws exactly what it always drew."""
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -18,6 +25,9 @@ LMAX = 32       # FX_ANN_LMAX
 GLYPHS = 95     # FX_ANN_GLYPHS: ASCII 32..126
 MAX_SLOTS = 1024
 FLAG_BOXES, FLAG_MASKS, FLAG_LABELS = 1, 2, 4
+RNAME = 16      # FX_OVL_RNAME: glyphs of a region name
+MAX_TRACE = 64  # FX_TRACE_MAX_LEN: points kept per track
+OVL_FILL, OVL_STROKE, OVL_TRACES = 1, 2, 4
 FOCOOS_PALETTE = ("#015fe6", "#3faebd", "#63dba6", "#a151ff", "#df923a")
 # ctypes-free mirror of fx_annotate_record (56 bytes)
 REC_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"), ("colour", "<u4"), ("nchar", "<i4"), ("glyph", "u1", (LMAX,))])
@@ -102,6 +112,142 @@ def classification_records(lines: Sequence[Sequence[Tuple[str, float]]], T: int,
             r["colour"], r["nchar"] = palette_colour(i), len(g)
             r["glyph"][:len(g)] = g
     return rec
+
+
+class DeviceTraces:
+    """The ring of the last ``length`` anchors (bottom centre of the box, doubled pixels) of every slot of ``tracker``, on the device: what
+    ``Overlay(traces=...)`` draws as the tail behind a tracked object.  ``update`` is one launch right after the
+    tracker's; the state belongs to this object and outlives the ``infer_stream`` calls it is passed to through ``Overlay(traces=this)``.
+    After ``DeviceTracker.reset(b)`` the ids of stream b start over: ``reset(b)`` must follow it."""
+
+    STATE = ("id", "label", "len", "head", "xy")
+
+    def __init__(self, tracker, length: int, device=None):
+        from .tracking import DeviceTracker
+
+        if not isinstance(tracker, DeviceTracker):
+            raise TypeError(f"DeviceTraces: tracker must be a DeviceTracker, not {type(tracker).__name__}")
+        if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or not 1 <= length <= MAX_TRACE:
+            raise ValueError(f"DeviceTraces: length = {length!r} must be an integer in 1..{MAX_TRACE}")
+        self.tracker, self.length = tracker, int(length)
+        self.device = torch.device(device if device is not None else tracker.device)
+        if tracker.id.device != torch.empty(0, device=self.device).device:
+            raise ValueError(f"DeviceTraces: device {self.device} but the tracker lives on {tracker.id.device}")
+        self.lib = tracker.lib
+        self.streams, self.max_tracks = tracker.streams, tracker.config.max_tracks
+        i32 = dict(dtype=torch.int32, device=self.device)
+        B, M = self.streams, self.max_tracks
+        self.id, self.label = torch.zeros(B, M, **i32), torch.zeros(B, M, **i32)
+        self.len, self.head = torch.zeros(B, M, **i32), torch.zeros(B, M, **i32)
+        self.xy = torch.zeros(B, M, self.length, 2, **i32)
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _state_ptrs(self):
+        return self.id.data_ptr(), self.label.data_ptr(), self.len.data_ptr(), self.head.data_ptr()
+
+    def update(self, det_labels: torch.Tensor, det_boxes: torch.Tensor, det_count: torch.Tensor, track_ids: torch.Tensor) -> None:
+        """One frame of every stream: the packed device results and the ids the tracker gave them in THIS frame (i32 [B, T])."""
+        from ._lib import check
+
+        B, T = self.streams, int(det_labels.shape[-1])
+        for name, t, shape in (("det_labels", det_labels, (B, T)), ("det_boxes", det_boxes, (B, T, 4)), ("det_count", det_count, (B,)),
+                               ("track_ids", track_ids, (B, T))):
+            if tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != self.id.device or not t.is_contiguous():
+                raise ValueError(f"DeviceTraces.update: {name} must be a contiguous torch.int32 tensor {shape} on {self.id.device}, got "
+                                 f"{t.dtype} {tuple(t.shape)} on {t.device}")
+        check(self.lib.fx_trace_update(det_labels.data_ptr(), det_boxes.data_ptr(), det_count.data_ptr(), B, T, track_ids.data_ptr(),
+                                       self.tracker.id.data_ptr(), self.max_tracks, self.length, *self._state_ptrs(), self.xy.data_ptr(),
+                                       self._stream()), "fx_trace_update")
+
+    def reset(self, stream: Optional[int] = None) -> None:
+        """Forget the traces of ``stream`` (all streams when None)."""
+        from ._lib import check
+
+        if stream is not None and (isinstance(stream, bool) or not isinstance(stream, (int, np.integer)) or not 0 <= stream < self.streams):
+            raise ValueError(f"DeviceTraces.reset: stream = {stream!r} must be in 0..{self.streams - 1} or None")
+        check(self.lib.fx_trace_reset(*self._state_ptrs(), self.streams, self.max_tracks, -1 if stream is None else int(stream), self._stream()),
+              "fx_trace_reset")
+
+    def state(self) -> Dict[str, np.ndarray]:
+        """Host copies of the state arrays: id / label / len / head [streams, max_tracks], xy [streams, max_tracks, length, 2]."""
+        src = dict(id=self.id, label=self.label, len=self.len, head=self.head, xy=self.xy)
+        return {k: src[k].cpu().numpy().copy() for k in self.STATE}
+
+
+@dataclass(frozen=True)
+class Overlay:
+    """What ``annotate=`` draws beyond ``True`` (boxes, masks, "name: NN%") in ``infer_stream`` / ``infer_batch``: ``ids`` - "#17 " in front
+    of the label of a tracked detection; ``zones`` - the regions tinted and outlined, the lines stroked, "door: 3" / "gate: 12/9" at each
+    region's first vertex; ``traces`` - the last N (0..64, 0 = off) anchors of every track joined into a tail, or a ``DeviceTraces`` whose
+    state then outlives the call.  Validated at construction: ValueError names the field."""
+    ids: bool = True
+    zones: bool = True
+    traces: Union[int, DeviceTraces] = 0
+
+    def __post_init__(self):
+        for f in ("ids", "zones"):
+            if not isinstance(getattr(self, f), (bool, np.bool_)):
+                raise ValueError(f"Overlay.{f} = {getattr(self, f)!r}: must be True or False")
+        t = self.traces
+        if not isinstance(t, DeviceTraces) and (isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= t <= MAX_TRACE):
+            raise ValueError(f"Overlay.traces = {t!r}: must be an integer in 0..{MAX_TRACE} (points kept per track, 0 = off) or a DeviceTraces")
+
+    @property
+    def traced(self) -> bool:
+        return isinstance(self.traces, DeviceTraces) or self.traces > 0
+
+
+def check_overlay(annotate, tracked: bool, zoned: bool, family: str, what: str = "infer_stream") -> Optional[Overlay]:
+    """The Overlay of ``annotate=`` (None for True / False), refused on the host, by field, when the call has nothing to draw it from."""
+    if not isinstance(annotate, Overlay):
+        return None
+    if family == "fai_cls":
+        raise NotImplementedError(f"{what}: annotate=Overlay(...) draws ids, zones and traces of boxes; model family 'fai_cls' has none")
+    if annotate.ids and not tracked:
+        raise ValueError(f"{what}: Overlay.ids = True needs a tracker (pass track= / tracker=, or Overlay(ids=False))")
+    if annotate.traced and not tracked:
+        raise ValueError(f"{what}: Overlay.traces = {annotate.traces!r} needs a tracker (pass track= / tracker=)")
+    if annotate.zones and not zoned:
+        raise ValueError(f"{what}: Overlay.zones = True needs zones= (or Overlay(zones=False))")
+    if what == "infer_batch" and annotate.traced and not isinstance(annotate.traces, DeviceTraces):
+        raise ValueError(f"infer_batch: Overlay.traces = {annotate.traces!r} would start a new trace with every call: pass a DeviceTraces")
+    return annotate
+
+
+def refuse_overlay(annotate, what: str) -> None:
+    """``infer`` and ``infer_tiled`` see one picture: no stream, no identity, nothing an Overlay could draw."""
+    if isinstance(annotate, Overlay):
+        raise ValueError(f"{what}: annotate=Overlay(...) needs a stream identity: use infer_stream or infer_batch ({what} takes annotate=True)")
+
+
+def traces_for_batch(overlay: Overlay, tracker, what: str = "infer_stream") -> Optional[DeviceTraces]:
+    """The DeviceTraces of a call: created for ``tracker`` with the first batch from ``Overlay(traces=N)``, or the caller's own."""
+    t = overlay.traces
+    if isinstance(t, DeviceTraces):
+        if t.tracker is not tracker:
+            raise ValueError(f"{what}: Overlay.traces was built for another tracker: pass that tracker as track= / tracker=")
+        return t
+    return DeviceTraces(tracker, int(t)) if t > 0 else None
+
+
+@dataclass
+class OverlayPass:
+    """What one batch's drawing reads beyond the packed results: the Overlay, the ids of this frame and the device state objects."""
+    overlay: Overlay
+    ids: Optional[torch.Tensor] = None
+    zones: Optional[object] = None       # zones.DeviceZones, when Overlay.zones
+    traces: Optional[DeviceTraces] = None
+
+
+def region_name_table(names: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
+    """Region names as the zone-records kernel reads them: glyph indices uint8 [R, RNAME] (truncated) and lengths int32 [R]."""
+    tab, ln = np.zeros((max(len(names), 1), RNAME), dtype=np.uint8), np.zeros(max(len(names), 1), dtype=np.int32)
+    for k, name in enumerate(names):
+        g = encode_text(str(name))[:RNAME]
+        tab[k, :len(g)], ln[k] = g, len(g)
+    return tab, ln
 
 
 def check_inputs(inputs, what: str = "infer_batch") -> None:
@@ -189,6 +335,93 @@ class DeviceAnnotator:
               "fx_annotate_u8")
         return dst
 
+    def records_tracked(self, results, ids: torch.Tensor, b0: int, B: int, H: int, W: int, s: int) -> torch.Tensor:
+        """fx_annotate_labels_tracked: ``records()`` with "#id " in front of the text of every slot whose ``ids`` (i32 [rows, T]) is >= 0."""
+        from ._lib import check
+
+        T = int(results.det_scores.shape[1])
+        rec = torch.zeros(int(results.det_count.shape[0]), T, REC_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+        check(self.lib.fx_annotate_labels_tracked(
+            results.det_scores.data_ptr() + 4 * b0 * T, results.det_labels.data_ptr() + 4 * b0 * T, results.det_boxes.data_ptr() + 16 * b0 * T,
+            results.det_count.data_ptr() + 4 * b0, ids.data_ptr() + 4 * b0 * T, B, T, self.names.data_ptr(), self.name_len.data_ptr(),
+            len(self.classes), H, W, s, self.gw, self.gh, rec.data_ptr() + REC_DTYPE.itemsize * b0 * T, self._stream()),
+            "fx_annotate_labels_tracked")
+        return rec
+
+    def _zone_tables(self, zones) -> dict:
+        """The region names, region counts and the record buffer of a DeviceZones, uploaded once and kept on it."""
+        tab = getattr(zones, "_overlay_tables", None)
+        if tab is None:
+            from .zones import MAX_REGIONS
+
+            names, ln = region_name_table([r.name for regs in zones.per_stream for r in regs])
+            S = zones.streams
+            tab = zones._overlay_tables = dict(
+                names=torch.from_numpy(names).to(self.device), name_len=torch.from_numpy(ln).to(self.device),
+                count=torch.from_numpy(np.diff(zones.reg_first).astype(np.int32)).to(self.device),
+                zeros=torch.zeros(S, MAX_REGIONS, 4, dtype=torch.int32, device=self.device),
+                rec=torch.zeros(S, MAX_REGIONS, REC_DTYPE.itemsize, dtype=torch.uint8, device=self.device))
+        return tab
+
+    def zone_records(self, zones, H: int, W: int, s: int) -> torch.Tensor:
+        """fx_annotate_zone_records for every stream of ``zones`` at frame size (H, W): uint8 [streams, 32, 56], the counts read from the
+        buffer of the last ``zones.update`` on the device."""
+        from ._lib import check
+
+        tab, R = self._zone_tables(zones), zones.R
+        io = zones._io
+        check(self.lib.fx_annotate_zone_records(
+            zones._d_records.data_ptr(), zones._d_reg_first.data_ptr(), zones._d_verts.data_ptr(), zones.records.ctypes.data,
+            zones.reg_first.ctypes.data, zones.verts.ctypes.data, R, int(zones.verts.shape[0]), tab["names"].data_ptr(), tab["name_len"].data_ptr(),
+            io[:R].data_ptr(), io[R:2 * R].data_ptr(), io[2 * R:3 * R].data_ptr(), zones.streams, H, W, s, self.gw, self.gh, tab["rec"].data_ptr(),
+            self._stream()), "fx_annotate_zone_records")
+        return tab["rec"]
+
+    def geometry(self, frames: torch.Tensor, b0: int, zones, traces: Optional[DeviceTraces], flags: int,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fx_annotate_overlay_u8: zone fills, zone outlines / line strokes and traces of streams b0 .. b0+B-1 on ``frames``, in place or
+        into ``out``.  ``zones`` (a DeviceZones) is read with OVL_FILL | OVL_STROKE, ``traces`` with OVL_TRACES."""
+        from ._lib import check
+
+        self._check_frames(frames)
+        dst = frames if out is None else out
+        B, H, W, _ = frames.shape
+        z = [None] * 6 + [0, 0]
+        t = [None] * 6 + [1, 1]
+        streams = zones.streams if zones is not None else (traces.streams if traces is not None else b0 + B)
+        if flags & (OVL_FILL | OVL_STROKE):
+            z = [zones._d_records.data_ptr(), zones._d_reg_first.data_ptr(), zones._d_verts.data_ptr(), zones.records.ctypes.data,
+                 zones.reg_first.ctypes.data, zones.verts.ctypes.data, zones.R, int(zones.verts.shape[0])]
+        if flags & OVL_TRACES:
+            t = [traces.tracker.id.data_ptr(), *traces._state_ptrs(), traces.xy.data_ptr(), traces.max_tracks, traces.length]
+        check(self.lib.fx_annotate_overlay_u8(frames.data_ptr(), dst.data_ptr(), B, H, W, int(b0), streams, *z, *t, scale_for(H, W), flags,
+                                              self._stream()), "fx_annotate_overlay_u8")
+        return dst
+
+    def annotate_overlay(self, frames: torch.Tensor, results, b0: int, ov: OverlayPass) -> torch.Tensor:
+        """``annotate()`` with the layers of an Overlay, in place, bottom to top: zone fills, zone outlines and line strokes, traces
+        (one geometry pass), the three layers of ``annotate()`` with the id in the label, the region count labels."""
+        self._check_frames(frames)
+        B, H, W, _ = frames.shape
+        s = scale_for(H, W)
+        geo = (OVL_FILL | OVL_STROKE if ov.zones is not None else 0) | (OVL_TRACES if ov.traces is not None else 0)
+        if geo:
+            self.geometry(frames, b0, ov.zones, ov.traces, geo)
+        labels = bool(self.flags & FLAG_LABELS)
+        rec = None
+        if labels:
+            rec = self.records_tracked(results, ov.ids, b0, B, H, W, s) if ov.overlay.ids else self.records(results, b0, B, H, W, s)
+        self.draw(frames, results, rec, b0)
+        if labels and ov.zones is not None:
+            from ._lib import check
+
+            tab = self._zone_tables(ov.zones)
+            zrec = self.zone_records(ov.zones, H, W, s)
+            check(self.lib.fx_annotate_u8(frames.data_ptr(), frames.data_ptr(), B, H, W, int(b0), int(zrec.shape[1]), tab["count"].data_ptr(),
+                                          tab["zeros"].data_ptr(), tab["zeros"].data_ptr(), None, None, 0, 0, zrec.data_ptr(),
+                                          self.atlas.data_ptr(), self.gw, self.gh, s, FLAG_LABELS, self._stream()), "fx_annotate_u8")
+        return frames
+
     def annotate_classification(self, frames: torch.Tensor, detections: Sequence, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The classification overlay: ``detections[b]`` (FocoosDetections) gives frame b's lines; the records are built on the host (the
         classifier leaves nothing packed on the device) and drawn by fx_annotate_u8 with only the labels flag."""
@@ -229,11 +462,12 @@ def to_host(frames: torch.Tensor) -> np.ndarray:
     return host.numpy().copy()
 
 
-def annotate_results(fm, inputs, images: torch.Tensor, results, out: list) -> None:
+def annotate_results(fm, inputs, images: torch.Tensor, results, out: list, overlay: Optional[OverlayPass] = None) -> None:
     """Set ``out[i].image`` (np.uint8 [H, W, 3] at the ORIGINAL size of input i) for one batch: ``images`` is what preprocess returned,
     ``results`` the plan holding the packed device results (ignored for classification, drawn from ``out``'s detections).  When
     preprocess took the uint8 same-size fast path the batch itself is drawn on; otherwise every original goes up once (the boxes are in
-    original pixels already) and each run of equal-size images is one kernel call with its ``b0``.  One pinned copy back per call."""
+    original pixels already) and each run of equal-size images is one kernel call with its ``b0``.  One pinned copy back per call.
+    ``overlay``: the layers of an ``Overlay`` as well (``annotate_overlay``); None draws exactly what ``annotate=True`` always drew."""
     ann = annotator_of(fm)
     lst = inputs if isinstance(inputs, list) else [inputs]
     cls = fm.model.family == "fai_cls"
@@ -252,7 +486,10 @@ def annotate_results(fm, inputs, images: torch.Tensor, results, out: list) -> No
             i = j
     for b0, fr in runs:
         n = fr.shape[0]
-        drawn = ann.annotate_classification(fr, out[b0:b0 + n]) if cls else ann.annotate(fr, results, b0)
+        if cls:
+            drawn = ann.annotate_classification(fr, out[b0:b0 + n])
+        else:
+            drawn = ann.annotate(fr, results, b0) if overlay is None else ann.annotate_overlay(fr, results, b0, overlay)
         host = to_host(drawn)
         for k in range(n):
             out[b0 + k].image = host[k]

@@ -9,26 +9,15 @@
 // so both kernels are compared for equality with the numpy restatement of tests/annotate_ref.py.  The contract is in include/focoos_amd.h.
 //
 // fp32 / integer only: the FX_FP16 switch of the second library does not touch this file.
-#include "det_common.h"
+#include "annotate_common.h"
 
 #pragma clang fp contract(off)
 
-#define AN_BX 64   // threads along a row: 64 x 4 pixels = 256 pixels per row segment, one wavefront per row
-#define AN_BY 4    // rows per workgroup
 #define AN_MAX_T 1024
-#define AN_MAX_SCALE 8
-#define AN_MAX_CELL 32
 #define AN_LDS_PER_SLOT 44   // clipped box (16) + label rectangle (16) + colour (4) + area (4) + slot | kind << 16 (4)
 #define AN_KIND_BOX 1u
 #define AN_KIND_MASK 2u
 #define AN_KIND_LABEL 4u
-
-// FOCOOS_PALETTE (#015fe6 #3faebd #63dba6 #a151ff #df923a) as R | G << 8 | B << 16; selects, not a table: a runtime-indexed array would live in scratch
-__device__ __forceinline__ uint32_t an_palette(int label) {
-  int m = label % 5;
-  if (m < 0) m += 5;
-  return m == 0 ? 0xe65f01u : m == 1 ? 0xbdae3fu : m == 2 ? 0xa6db63u : m == 3 ? 0xff51a1u : 0x3a92dfu;
-}
 
 // ---- label records ---------------------------------------------------------------------------------------------------------------------
 // One thread per slot of [B][T].  The glyph bytes are produced four at a time and stored as dwords (the record is 4-byte aligned, glyph[]
@@ -200,20 +189,7 @@ __global__ __launch_bounds__(AN_BX * AN_BY) void annotate_kernel(const uint8_t* 
   const int64_t off = (((int64_t)blockIdx.z * H + y) * W + x) * 3;
   const int np = W - x < 4 ? W - x : 4;
   uint32_t px[4];
-  if constexpr (VEC) {
-    const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src + off);
-    const uint32_t d0 = s32[0], d1 = s32[1], d2 = s32[2];
-    px[0] = d0 & 0xffffffu;
-    px[1] = (d0 >> 24) | ((d1 & 0xffffu) << 8);
-    px[2] = (d1 >> 16) | ((d2 & 0xffu) << 16);
-    px[3] = d2 >> 8;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint8_t* q = src + off + (k < np ? k : 0) * 3;
-      px[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
-    }
-  }
+  an_load4<VEC>(src, off, np, px);
 
   unsigned ohit = 0, mhit = 0, lhit = 0;
   uint32_t ocol[4] = {0, 0, 0, 0}, mcol[4] = {0, 0, 0, 0};
@@ -301,22 +277,7 @@ __global__ __launch_bounds__(AN_BX * AN_BY) void annotate_kernel(const uint8_t* 
     px[k] = p;
   }
 
-  if constexpr (VEC) {
-    uint32_t* d32 = reinterpret_cast<uint32_t*>(dst + off);
-    d32[0] = px[0] | (px[1] << 24);
-    d32[1] = (px[1] >> 8) | (px[2] << 16);
-    d32[2] = (px[2] >> 16) | (px[3] << 8);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (k < np) {
-        uint8_t* q = dst + off + k * 3;
-        q[0] = (uint8_t)px[k];
-        q[1] = (uint8_t)(px[k] >> 8);
-        q[2] = (uint8_t)(px[k] >> 16);
-      }
-    }
-  }
+  an_store4<VEC>(dst, off, np, px);
 }
 
 extern "C" int fx_annotate_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int b0, int T, const int32_t* det_count,

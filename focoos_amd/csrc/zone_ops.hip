@@ -11,19 +11,14 @@
 // The contract of both is in include/focoos_amd.h.  Plain vector stores, no atomics: a region belongs to one stream, so one workgroup is
 // the only writer of its state rows and one thread the only writer of its counters.  Integer only: the FX_FP16 switch of the second
 // library does not touch this file.
-#include "det_common.h"
+#include "zone_common.h"
 
 #pragma clang fp contract(off)
 
 #define ZN_THREADS 256
 #define ZN_WAVES (ZN_THREADS / 64)
-#define ZN_REGIONS FX_ZONE_MAX_REGIONS
-#define ZN_VERTS FX_ZONE_MAX_VERTS
-#define ZN_COORD 16384     // box coordinates live in [0, ZN_COORD], as in the tracker
-#define ZN_VCOORD 32768    // region vertices live in [-ZN_VCOORD, ZN_VCOORD]; doubled: |difference| < 2^18, products < 2^36
 #define ZN_REC_WORDS ((int)(sizeof(fx_zone_region) / 4))
 
-static_assert(sizeof(fx_zone_region) == 64, "fx_zone_region is 64 bytes");
 static_assert(ZN_REGIONS == 32, "one bit per region in a 32-bit mask, one lane of a half wavefront per region counter");
 
 // One workgroup = one stream.  Thread i owns detections i, i + 256, ... (at most 4), one at a time: its box, label, id and slot stay in
@@ -145,35 +140,6 @@ __global__ __launch_bounds__(ZN_THREADS) void zone_reset_kernel(int32_t* __restr
   const int r = r_first + (int)blockIdx.x;
   for (int t = threadIdx.x; t < M; t += ZN_THREADS) st_id[(int64_t)r * M + t] = 0, st_side[(int64_t)r * M + t] = 0;
   if (threadIdx.x == 0 && clear_counters) in_total[r] = 0, out_total[r] = 0;
-}
-
-static bool zn_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-// reg_first[0] = 0, monotone, at most ZN_REGIONS regions per stream
-static bool zn_offsets_ok(const int32_t* reg_first, int B) {
-  if (!reg_first || B < 1 || B > FX_TRACK_MAX_STREAMS || reg_first[0] != 0) return false;
-  for (int b = 0; b < B; ++b) {
-    const int64_t n = (int64_t)reg_first[b + 1] - reg_first[b];
-    if (n < 0 || n > ZN_REGIONS) return false;
-  }
-  return true;
-}
-
-static bool zn_tables_ok(const fx_zone_region* regions, const int32_t* reg_first, const int32_t* verts, int B, int R_total, int V_total) {
-  if (!regions || !verts || R_total < 1 || V_total < 2) return false;
-  if (!zn_offsets_ok(reg_first, B) || reg_first[B] != R_total) return false;
-  for (int r = 0; r < R_total; ++r) {
-    const fx_zone_region& g = regions[r];
-    if (g.kind != FX_ZONE_POLYGON && g.kind != FX_ZONE_LINE) return false;
-    if (g.anchor < 0 || g.anchor > 8 || (g.flags & ~FX_ZONE_ANY_CLASS) != 0) return false;
-    if (g.kind == FX_ZONE_LINE ? g.vert_count != 2 : (g.vert_count < 3 || g.vert_count > ZN_VERTS)) return false;
-    if (g.vert_first < 0 || (int64_t)g.vert_first + g.vert_count > V_total) return false;
-    const int32_t* v = verts + 2 * (int64_t)g.vert_first;
-    for (int i = 0; i < 2 * g.vert_count; ++i)
-      if (v[i] < -ZN_VCOORD || v[i] > ZN_VCOORD) return false;
-    if (g.kind == FX_ZONE_LINE && v[0] == v[2] && v[1] == v[3]) return false;
-  }
-  return true;
 }
 
 extern "C" int fx_zone_update(const int32_t* det_labels, const int32_t* det_boxes, const int32_t* det_count, int B, int T, const int32_t* track_ids,

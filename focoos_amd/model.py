@@ -282,14 +282,15 @@ class FocoosModel:
     def device(self):
         return self.model.device
 
-    def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate: bool = False, tracker=None,
+    def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate=False, tracker=None,
                     mask_format: str = "png", zones=None) -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
         reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``inputs`` may also be a
         ``frames.FrameBatch`` of NV12 / I420 / BGR / RGB video frames, host or device: the results are those of the same frames passed as
         RGB arrays (frames.py).  ``annotate``: every result
         also carries ``.image``, the uint8 input at its original size with the detections drawn on it on the device (annotate.py);
-        non-uint8 inputs then raise ValueError.  ``tracker``: a ``tracking.DeviceTracker`` of ``len(inputs)`` streams, for callers who
+        non-uint8 inputs then raise ValueError; an ``annotate.Overlay`` also draws the track ids, the zones with their counts and the traces
+        (it needs the ``tracker`` / ``zones`` it draws from, and its traces as a ``DeviceTraces``).  ``tracker``: a ``tracking.DeviceTracker`` of ``len(inputs)`` streams, for callers who
         feed one batch per call - image b is the next frame of stream b, and every tracked detection gets its ``track_id`` (the
         detections themselves are those of ``tracker=None``).  ``mask_format``: how the mask families hand out their masks - "png" (the
         reference's base64 PNG in ``FocoosDet.mask``, the default), "rle" (``FocoosDet.rle``: the full-frame uncompressed COCO RLE, encoded on
@@ -303,6 +304,12 @@ class FocoosModel:
         from .mask_rle import check_mask_format
 
         check_mask_format(mask_format, self.model.family, "infer_batch")
+        overlay = None
+        if annotate:
+            from .annotate import check_overlay
+
+            overlay = check_overlay(annotate, tracker is not None or getattr(zones, "tracker", None) is not None, zones is not None,
+                                    self.model.family, "infer_batch")
         inputs = as_frame_batch(inputs) or inputs      # a FrameBatch (or one Frame) goes where a list of images goes (frames.py)
         if zones is not None:
             from . import zones as Z
@@ -336,6 +343,13 @@ class FocoosModel:
             ids = tracker.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
         if zones is not None:        # one more launch, right after the tracker's
             zones.update(pl.det_labels, pl.det_boxes, pl.det_count, ids if zones.tracker is not None else None)
+        ovl = None
+        if overlay is not None:      # the traces' launch, then everything the drawing will read
+            from .annotate import OverlayPass, traces_for_batch
+
+            ovl = OverlayPass(overlay, ids, zones if overlay.zones else None, traces_for_batch(overlay, tracker, "infer_batch"))
+            if ovl.traces is not None:
+                ovl.traces.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
         if self.model.family == "fai_cls":
             out = self.processor.pack_detections(pl.logits.cpu(), self.model_info.classes, thr)   # the one D2H copy of the batch's logits
         elif self.model.family in ("fai_mf", "bisenetformer"):
@@ -349,14 +363,14 @@ class FocoosModel:
             Z.attach(out, zones.fetch())
         t3 = perf_counter()
         if annotate:
-            annotate_results(self, drawable(inputs, images, self.model.device), images, pl, out)
+            annotate_results(self, drawable(inputs, images, self.model.device), images, pl, out, ovl)
         t4 = perf_counter()
         for o in out:
             o.latency = InferLatency(preprocess=round(t1 - t0, 3), inference=round(t2 - t1, 3), postprocess=round(t3 - t2, 3),
                                      annotate=round(t4 - t3, 3) if annotate else None)
         return out
 
-    def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate: bool = False, track=None,
+    def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate=False, track=None,
                      mask_format: str = "png", zones=None, detections: bool = True):
         """Throughput inference (round 6): iterate over ``batches`` (each a list of images of ONE common shape after preprocessing and one
         batch size) and yield each batch's ``List[FocoosDetections]`` in order, with up to ``depth`` batches in flight on the engine's
@@ -364,7 +378,11 @@ class FocoosModel:
         ``infer_batch`` per batch, bit for bit - the lanes share nothing but the read-only weights; what changes is that the GPU is not
         drained between batches (RT-DETR-L bs = 32: +8 % images/s, MaskFormer-L +15 %, BiSeNetFormer-L +36 %).
         ``annotate``: as in ``infer_batch`` - each batch is drawn after its lane finished, from the lane's still-valid results and the
-        submitted frames, on the current stream; the detections are those of ``annotate=False``.
+        submitted frames, on the current stream; the detections are those of ``annotate=False``.  ``annotate.Overlay(ids, zones, traces)``
+        in the place of ``True`` also draws what ``track`` / ``zones`` know: "#17 " in front of a tracked label, the regions
+        tinted and outlined with "door: 3" / "gate: 12/9", and a tail of the last ``traces`` anchors behind every track (one more launch
+        after the zones'); a field that has nothing to draw from (ids or traces without ``track``, zones without ``zones``) raises
+        ValueError before anything touches the GPU, ``True`` draws exactly what it always drew.
         ``track``: identity across frames on the device (tracking.py) - batch index b is stream b (camera b), consecutive batches
         are consecutive frames.  ``True`` (the defaults), a ``TrackerConfig``, or a ``DeviceTracker`` whose state then outlives the call.
         Each batch is one more launch after its lane finished (batches finish in order) and every tracked detection carries ``track_id``;
@@ -391,11 +409,15 @@ class FocoosModel:
         Z.check_detections_flag(detections, zones, annotate, mask_format)
         check_mask_format(mask_format, self.model.family, "infer_stream")
 
-        from .annotate import annotate_results, check_inputs
+        from .annotate import OverlayPass, annotate_results, check_inputs, check_overlay, traces_for_batch
         from .tracking import TrackerConfig, attach_ids, for_batch, resolve, warn_drops
 
+        if annotate and self.model.family == "fai_cls":
+            check_overlay(annotate, False, False, "fai_cls")
         track = resolve(track, self.model.family, self.model.device)
         zones, track = Z.resolve(zones, track, self.model.family)
+        overlay = check_overlay(annotate, track is not None, zones is not None, self.model.family) if annotate else None
+        traces = None
         thr = threshold or self.processor.threshold
         if self.model.family == "fai_cls":
             yield from self._infer_stream_cls(batches, thr, depth, annotate)
@@ -411,6 +433,8 @@ class FocoosModel:
                 ids = track.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
             if zones is not None:      # one more launch, right after the tracker's, on the same packed results
                 zones.update(pl.det_labels, pl.det_boxes, pl.det_count, ids if zones.tracker is not None else None)
+            if traces is not None:     # the tail of every track, appended right after the tracker (and the zones)
+                traces.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
             if not detections:         # analytics only: no detection objects, no ids on the host
                 out = [FocoosDetections(detections=[]) for _ in range(pipe.B)]
             elif mask_family:
@@ -422,7 +446,8 @@ class FocoosModel:
             if zones is not None:
                 Z.attach(out, zones.fetch())
             if annotate:      # the lane's results stay valid until the lane is submitted to again, which happens after this returns
-                annotate_results(self, *frames.pop(ticket), pl, out)
+                ovl = None if overlay is None else OverlayPass(overlay, ids, zones if overlay.zones else None, traces)
+                annotate_results(self, *frames.pop(ticket), pl, out, ovl)
             return out
 
         for inputs in batches:
@@ -437,6 +462,8 @@ class FocoosModel:
                 track = for_batch(track, B, x.device)      # created with the first batch, which fixes B
             if zones is not None:
                 zones = Z.for_batch(zones, B, track, x.device)
+            if overlay is not None and overlay.traced and traces is None:
+                traces = traces_for_batch(overlay, track)      # created with the first batch, like the tracker it follows
             if pipe is None or (pipe.B, pipe.H, pipe.W) != (B, H, W):
                 while pending:
                     yield finish()
@@ -505,6 +532,10 @@ class FocoosModel:
         from .frames import Frame, FrameBatch
         from .mask_rle import check_mask_format
 
+        if annotate:
+            from .annotate import refuse_overlay
+
+            refuse_overlay(annotate, "infer")
         check_mask_format(mask_format, self.model.family, "infer")
         t0 = perf_counter()
         if isinstance(image, (str, os.PathLike)):
@@ -539,6 +570,10 @@ class FocoosModel:
         from .mask_rle import check_mask_format
 
         refuse_frames(image, "infer_tiled")      # before anything loads the library
+        if annotate:
+            from .annotate import refuse_overlay
+
+            refuse_overlay(annotate, "infer_tiled")
         from .tiled import infer_tiled as _infer_tiled
 
         if check_mask_format(mask_format, None, "infer_tiled") in ("rle", "polygon"):

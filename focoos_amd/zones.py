@@ -5,7 +5,8 @@ analytics a camera deployment asks for after identity.  Everything the counter n
 box family leaves there and the tracker's ids (tracking.py) - so it is one ``fx_zone_update`` launch per batch, one workgroup per stream
 (csrc/zone_ops.hip; the contract is in include/focoos_amd.h), and a few hundred bytes more in the copy back.  Batch index b is stream b
 (camera b).  All decisions are integer ones; tests/zones_ref.py restates them and the GPU tests ask for equality.  The reference has no
-counterpart.  Left out on purpose: drawing zones or ids, dwell times, heat maps and ``infer_tiled``.
+counterpart.  Left out on purpose: dwell times, heat maps and ``infer_tiled``; the regions and their counts are drawn by ``annotate=Overlay(...)``
+(annotate.py).
 
 A detection is represented by its anchor, one of nine points of its integer box.  A ``Zone`` is an even-odd polygon (an axis-aligned
 rectangle is half-open: left and top edges inside, right and bottom edges outside); a ``Line`` from ``start`` to ``end`` observes the side

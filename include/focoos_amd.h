@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 22
+#define FX_ABI_VERSION 23
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -550,6 +550,81 @@ typedef struct fx_frame_desc {
   int32_t reserved[3];
 } fx_frame_desc; /* 64 bytes */
 int fx_frames_ingest(const fx_frame_desc* descs, const fx_frame_desc* descs_host, int B, void* y, int out_f32, int Ho, int Wo, fx_stream_t stream);
+
+/* ---- Zones, lines, counts, track ids and traces drawn on device frames (ABI 23; csrc/overlay.hip):
+ * FocoosModel.infer_stream(annotate=Overlay(...)).  Five entry points beside the two of ABI 17; every output byte is an integer function of the
+ * inputs (the percentage of a label is the two rounded fp32 operations of ABI 17), no atomics, plain vector stores, contraction off.  Null
+ * (where required) or misaligned pointers (det_boxes 16, verts and trace_xy 8, everything else 4 bytes; frames 1) or anything else outside a
+ * contract: FX_ERR_INVALID_ARGUMENT, nothing launched, nothing written.  The same in both libraries.
+ *
+ * fx_annotate_labels_tracked = fx_annotate_labels_from_detections with track_ids i32 [B][T] (fx_track_update's).  A slot with id =
+ * track_ids[b][j] >= 0 gets the text "#", the decimal digits of id, " ", then the text of ABI 17 with the class name cut to
+ * min(FX_ANN_LNAME, FX_ANN_LMAX - 6 - prefix) glyphs, prefix = 2 + number of digits (so a ten-digit id and a long name still fit the 32 glyph
+ * slots); rectangle and colour follow from nchar and the label as in ABI 17.  A slot with id < 0 gets the record of ABI 17 byte for byte.
+ *
+ * fx_annotate_zone_records: rec [B][FX_ZONE_MAX_REGIONS], one thread per slot; slot k of stream b is region r = reg_first[b] + k of
+ * fx_zone_update's tables (regions / reg_first / verts: device buffers; *_host: host copies of the same bytes, validated before the
+ * launch as fx_zone_update does), k >= the stream's region count gives an all-zero record.  name_glyphs u8 [R_total][FX_OVL_RNAME] / name_len
+ * i32 [R_total] (clamped to 0..FX_OVL_RNAME) hold the region names as glyph indices.  in_total / out_total / now i32 [R_total] are
+ * fx_zone_update's device buffers, read on the device; a count is shown as clamp(count, 0, 999999) without leading zeros.  Text of a zone:
+ * name ": " now; of a line: name ": " in "/" out (at most 16 + 2 + 6 + 1 + 6 = 31 glyphs).  Geometry is the rule of ABI 17 with the region's
+ * first vertex (vx, vy) in the place of the box corner: w = nchar gw s + 4 s, h = gh s + 4 s, x0 = clamp(vx, 0, max(0, W - w)), y0 = vy - h
+ * when that is >= 0, else clamp(vy, 0, max(0, H - h)).  colour = FOCOOS_PALETTE[k mod 5].  fx_annotate_u8 draws them with FX_ANN_LABELS, T =
+ * FX_ZONE_MAX_REGIONS and the streams' region counts as det_count.  1 <= B <= FX_TRACK_MAX_STREAMS, H, W, s, gw, gh as in ABI 17.
+ *
+ * fx_annotate_overlay_u8: dst [B][H][W][3] = src (uint8 RGB; dst == src or disjoint) with the geometry of streams b0 .. b0 + B - 1 drawn
+ * on it; frame b is stream b0 + b of the tables, b0 + B <= streams.  All tests are made on the pixel centre in DOUBLED coordinates,
+ * P = (2 x + 1, 2 y + 1); region vertices are doubled as in fx_zone_update and a trace point is stored doubled.  Per pixel, in this order:
+ *  1. FX_OVL_FILL: the pixel is in a polygon region exactly when fx_zone_update's even-odd test holds for P, so the tinted pixels are
+ *     the centres the counter calls inside.  p = (3 p + c + 2) >> 2 per channel with c = FOCOOS_PALETTE[k mod 5] of the LOWEST region index k
+ *     (within the stream) that holds it.  Lines have no fill.
+ *  2. FX_OVL_STROKE: every polygon edge (the last vertex closes onto the first) and every line is a segment A -> B.  With d = B - A,
+ *     e = P - A, h = 2 s: when d.d > 0 and 0 <= e.d <= d.d the pixel is on the stroke iff cross(d, e)^2 <= h^2 (d.d); otherwise iff
+ *     |P - A|^2 <= h^2 (e.d <= 0) or |P - B|^2 <= h^2 (e.d > 0): round caps and joints, 2 s pixels wide; a segment of length 0 (a trace
+ *     that stood still) is the disc.  The comparison is exact for vertices in
+ *     [-32768, 32768]: a pixel with |cross| > h (|d.x| + |d.y|) is rejected first (then cross^2 > h^2 d.d, because d.d <= (|d.x| + |d.y|)^2),
+ *     and what remains has |cross| <= 2^23, so both sides fit int64.  A stroke pixel takes the opaque colour of the lowest region index.
+ *  3. FX_OVL_TRACES: slot t of stream b is drawn while trace_id[b][t] == trk_id[b][t] != 0 and n = clamp(trace_len, 0, L) >= 2: its points in
+ *     the order they were appended, point i = trace_xy[b][t][(head - n + i) mod L], head = clamp(trace_head, 0, L - 1), are joined
+ *     pairwise by the stroke of step 2 (a coordinate is clamped to [-65536, 65536] when read) in FOCOOS_PALETTE[trace_label mod 5]; the
+ *     lowest slot wins.
+ * A workgroup owns a tile of 4 rows x 256 pixels, a thread 4 consecutive pixels (three dword loads / stores when W % 4 == 0 and both bases
+ * are 4-byte aligned, bytes otherwise).  The segments are culled against the tile four regions / four surviving tracks at a time (one
+ * wavefront each, one ballot, survivors appended in order to an LDS list that holds all of them), the tracks by the bounding box of their
+ * points before that; nothing is dropped.  When dst == src a thread none of whose pixels is touched stores nothing, so a stream without
+ * regions and live traces keeps its bytes.  regions / reg_first / verts (+ host copies, R_total, V_total) are read only with FX_OVL_FILL |
+ * FX_OVL_STROKE, trk_id and the trace arrays only with FX_OVL_TRACES (may be null otherwise).  1 <= B, b0 >= 0, b0 + B <= streams <=
+ * FX_TRACK_MAX_STREAMS, 1 <= H, W <= 16384, 1 <= s <= 8, 1 <= max_tracks <= FX_TRACK_MAX_SLOTS, 1 <= L <= FX_TRACE_MAX_LEN, flags in 0 .. 7.
+ *
+ * fx_trace_update, one workgroup per stream, right after fx_track_update: the state is caller-owned device memory, all zero at first,
+ * trace_id / trace_label / trace_len / trace_head i32 [B][max_tracks] and the ring trace_xy i32 [B][max_tracks][L][2].  Slot t with id =
+ * trk_id[b][t] >= 0 is OBSERVED when no lower slot of the stream holds the same id and some detection j < clamp(det_count[b], 0, T) has
+ * track_ids[b][j] == id (fx_zone_update's lookup, seen from the slot); the lowest such j is taken.  Then, if trace_id != id: trace_id = id,
+ * trace_label = det_labels[b][j], len = 0.  The doubled bottom-centre anchor (x0 + x1, 2 y1) of the box clamped to [0, 16384] is stored at
+ * trace_xy[b][t][head], head = clamp(trace_head, 0, L - 1); head becomes (head + 1) mod L and len min(len + 1, L).  A slot that is not
+ * observed is left alone.  One thread is the only writer of a slot, so duplicate ids stay memory-safe.  1 <= B <= FX_TRACK_MAX_STREAMS,
+ * 1 <= T, max_tracks <= FX_TRACK_MAX_SLOTS, 1 <= L <= FX_TRACE_MAX_LEN.
+ * fx_trace_reset: stream b (0 <= b < B), or every stream when b = -1, gets trace_id = trace_label = trace_len = trace_head = 0. */
+#define FX_OVL_RNAME 16      /* a region name contributes at most this many glyphs */
+#define FX_TRACE_MAX_LEN 64  /* points kept per track */
+enum { FX_OVL_FILL = 1, FX_OVL_STROKE = 2, FX_OVL_TRACES = 4 };
+int fx_annotate_labels_tracked(const float* scores, const int32_t* labels, const int32_t* boxes, const int32_t* count, const int32_t* track_ids,
+                               int B, int T, const uint8_t* name_glyphs, const int32_t* name_len, int K, int H, int W, int s, int gw, int gh,
+                               fx_annotate_record* rec, fx_stream_t stream);
+int fx_annotate_zone_records(const fx_zone_region* regions, const int32_t* reg_first, const int32_t* verts, const fx_zone_region* regions_host,
+                             const int32_t* reg_first_host, const int32_t* verts_host, int R_total, int V_total, const uint8_t* name_glyphs,
+                             const int32_t* name_len, const int32_t* in_total, const int32_t* out_total, const int32_t* now, int B, int H, int W,
+                             int s, int gw, int gh, fx_annotate_record* rec, fx_stream_t stream);
+int fx_annotate_overlay_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int b0, int streams, const fx_zone_region* regions,
+                           const int32_t* reg_first, const int32_t* verts, const fx_zone_region* regions_host, const int32_t* reg_first_host,
+                           const int32_t* verts_host, int R_total, int V_total, const int32_t* trk_id, const int32_t* trace_id,
+                           const int32_t* trace_label, const int32_t* trace_len, const int32_t* trace_head, const int32_t* trace_xy,
+                           int max_tracks, int L, int s, int flags, fx_stream_t stream);
+int fx_trace_update(const int32_t* det_labels, const int32_t* det_boxes, const int32_t* det_count, int B, int T, const int32_t* track_ids,
+                    const int32_t* trk_id, int max_tracks, int L, int32_t* trace_id, int32_t* trace_label, int32_t* trace_len,
+                    int32_t* trace_head, int32_t* trace_xy, fx_stream_t stream);
+int fx_trace_reset(int32_t* trace_id, int32_t* trace_label, int32_t* trace_len, int32_t* trace_head, int B, int max_tracks, int b,
+                   fx_stream_t stream);
 
 /* F.max_pool2d(k=3,s=2,p=1) (resnet.py:254) on NHWC bf16. */
 int fx_maxpool3x3s2_nhwc_bf16(const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, fx_stream_t stream);
