@@ -146,6 +146,11 @@ SIGNATURES = {
                                _vp],
     "fx_trace_update": [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "fx_trace_reset": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "fx_dwell_update": [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "fx_dwell_reset": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "fx_heat_tiles": [_i, _i, _i],
+    "fx_heat_update": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "fx_annotate_heat_u8": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp],
     "fx_mask_rle_workspace_bytes": [_i, _i, _i, _i],
     "fx_mask_rle_encode": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "fx_mask_polygon_workspace_bytes": [_i, _i, _i, _i, _i],
@@ -325,7 +330,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 23  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 24  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:

@@ -11,7 +11,8 @@ colouring, the half-opacity masks with the smaller instance on top and the label
 what is already on the device when a lane finishes: "#17 " in front of a tracked label (``fx_annotate_labels_tracked``), the regions of a
 ``DeviceZones`` tinted and outlined and its lines stroked, a tail of the last N anchors behind every track (``DeviceTraces``, ``fx_trace_update``;
 all three in one geometry pass, ``fx_annotate_overlay_u8``) and "door: 3" / "gate: 12/9" at every region (``fx_annotate_zone_records``, drawn by
-``fx_annotate_u8``).  csrc/overlay.hip; tests/overlay_ref.py restates the contracts.  ``annotate=True`` draws exactly what it always drew."""
+``fx_annotate_u8``).  csrc/overlay.hip; tests/overlay_ref.py restates the contracts.  ``Overlay(heat=True)`` puts the call's heat map
+underneath all of it (heat.py, ``fx_annotate_heat_u8``).  ``annotate=True`` draws exactly what it always drew."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -181,13 +182,15 @@ class Overlay:
     """What ``annotate=`` draws beyond ``True`` (boxes, masks, "name: NN%") in ``infer_stream`` / ``infer_batch``: ``ids`` - "#17 " in front
     of the label of a tracked detection; ``zones`` - the regions tinted and outlined, the lines stroked, "door: 3" / "gate: 12/9" at each
     region's first vertex; ``traces`` - the last N (0..64, 0 = off) anchors of every track joined into a tail, or a ``DeviceTraces`` whose
-    state then outlives the call.  Validated at construction: ValueError names the field."""
+    state then outlives the call; ``heat`` - the heat map of ``heatmap=`` blended in as the bottom layer (heat.py).  Validated at
+    construction: ValueError names the field."""
     ids: bool = True
     zones: bool = True
     traces: Union[int, DeviceTraces] = 0
+    heat: bool = False
 
     def __post_init__(self):
-        for f in ("ids", "zones"):
+        for f in ("ids", "zones", "heat"):
             if not isinstance(getattr(self, f), (bool, np.bool_)):
                 raise ValueError(f"Overlay.{f} = {getattr(self, f)!r}: must be True or False")
         t = self.traces
@@ -199,7 +202,7 @@ class Overlay:
         return isinstance(self.traces, DeviceTraces) or self.traces > 0
 
 
-def check_overlay(annotate, tracked: bool, zoned: bool, family: str, what: str = "infer_stream") -> Optional[Overlay]:
+def check_overlay(annotate, tracked: bool, zoned: bool, family: str, what: str = "infer_stream", heated: bool = False) -> Optional[Overlay]:
     """The Overlay of ``annotate=`` (None for True / False), refused on the host, by field, when the call has nothing to draw it from."""
     if not isinstance(annotate, Overlay):
         return None
@@ -211,6 +214,8 @@ def check_overlay(annotate, tracked: bool, zoned: bool, family: str, what: str =
         raise ValueError(f"{what}: Overlay.traces = {annotate.traces!r} needs a tracker (pass track= / tracker=)")
     if annotate.zones and not zoned:
         raise ValueError(f"{what}: Overlay.zones = True needs zones= (or Overlay(zones=False))")
+    if annotate.heat and not heated:
+        raise ValueError(f"{what}: Overlay.heat = True needs heatmap= (there is no heat map to draw)")
     if what == "infer_batch" and annotate.traced and not isinstance(annotate.traces, DeviceTraces):
         raise ValueError(f"infer_batch: Overlay.traces = {annotate.traces!r} would start a new trace with every call: pass a DeviceTraces")
     return annotate
@@ -239,6 +244,7 @@ class OverlayPass:
     ids: Optional[torch.Tensor] = None
     zones: Optional[object] = None       # zones.DeviceZones, when Overlay.zones
     traces: Optional[DeviceTraces] = None
+    heat: Optional[object] = None        # heat.DeviceHeatmap, when Overlay.heat
 
 
 def region_name_table(names: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
@@ -399,11 +405,13 @@ class DeviceAnnotator:
         return dst
 
     def annotate_overlay(self, frames: torch.Tensor, results, b0: int, ov: OverlayPass) -> torch.Tensor:
-        """``annotate()`` with the layers of an Overlay, in place, bottom to top: zone fills, zone outlines and line strokes, traces
-        (one geometry pass), the three layers of ``annotate()`` with the id in the label, the region count labels."""
+        """``annotate()`` with the layers of an Overlay, in place, bottom to top: the heat map (its own pass), zone fills, zone outlines
+        and line strokes, traces (one geometry pass), the three layers of ``annotate()`` with the id in the label, the region count labels."""
         self._check_frames(frames)
         B, H, W, _ = frames.shape
         s = scale_for(H, W)
+        if ov.heat is not None:
+            ov.heat.render(frames, b0)
         geo = (OVL_FILL | OVL_STROKE if ov.zones is not None else 0) | (OVL_TRACES if ov.traces is not None else 0)
         if geo:
             self.geometry(frames, b0, ov.zones, ov.traces, geo)

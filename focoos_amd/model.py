@@ -283,7 +283,7 @@ class FocoosModel:
         return self.model.device
 
     def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate=False, tracker=None,
-                    mask_format: str = "png", zones=None) -> List[FocoosDetections]:
+                    mask_format: str = "png", zones=None, dwell=None, heatmap=None) -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
         reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``inputs`` may also be a
         ``frames.FrameBatch`` of NV12 / I420 / BGR / RGB video frames, host or device: the results are those of the same frames passed as
@@ -299,18 +299,31 @@ class FocoosModel:
         else raises ValueError, "rle" or "polygon" on a family without masks NotImplementedError.  ``annotate`` and ``tracker`` read the
         packed device results, so they compose.  ``zones``: a ``zones.DeviceZones`` of ``len(inputs)`` streams, the counterpart of
         ``tracker`` for zone and line counting (zones.py): every result carries ``.zones``; a DeviceZones built on a tracker
-        runs that tracker (``tracker`` must be None or that one)."""
+        runs that tracker (``tracker`` must be None or that one).  ``dwell``: a ``zones.DeviceDwell`` built on that DeviceZones - the dicts
+        of its zones also carry the dwell times; ``heatmap``: a ``heat.DeviceHeatmap`` of ``len(inputs)`` streams, updated from
+        every batch and drawn by ``annotate=Overlay(heat=True)`` (heat.py)."""
         from .frames import as_frame_batch, drawable
         from .mask_rle import check_mask_format
 
         check_mask_format(mask_format, self.model.family, "infer_batch")
+        tracked = tracker is not None or getattr(zones, "tracker", None) is not None
+        if heatmap is not None:
+            from . import heat as HM
+
+            heatmap = HM.resolve(heatmap, tracked, self.model.family, "infer_batch")
         overlay = None
         if annotate:
             from .annotate import check_overlay
 
-            overlay = check_overlay(annotate, tracker is not None or getattr(zones, "tracker", None) is not None, zones is not None,
-                                    self.model.family, "infer_batch")
+            overlay = check_overlay(annotate, tracked, zones is not None, self.model.family, "infer_batch", heatmap is not None)
         inputs = as_frame_batch(inputs) or inputs      # a FrameBatch (or one Frame) goes where a list of images goes (frames.py, DESIGN 21)
+        if dwell is not None:
+            from . import zones as Z
+
+            dwell = Z.resolve_dwell(dwell, zones, tracker, self.model.family, "infer_batch")
+        if heatmap is not None:
+            HM.for_batch(heatmap, len(inputs), self.model.device, "infer_batch")
+            HM.check_sizes(heatmap, self.processor.get_image_sizes(inputs), "infer_batch")
         if zones is not None:
             from . import zones as Z
 
@@ -342,12 +355,17 @@ class FocoosModel:
         if tracker is not None:      # one launch on the packed device results; the ids come back beside the packed copy
             ids = tracker.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
         if zones is not None:        # one more launch, right after the tracker's
-            zones.update(pl.det_labels, pl.det_boxes, pl.det_count, ids if zones.tracker is not None else None)
+            zv = zones.update(pl.det_labels, pl.det_boxes, pl.det_count, ids if zones.tracker is not None else None)
+            if dwell is not None:    # and the dwell times, from the masks the zones just wrote
+                dwell.update(pl.det_count, ids, zv["det_inside"])
+        if heatmap is not None:
+            heatmap.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
         ovl = None
         if overlay is not None:      # the traces' launch, then everything the drawing will read
             from .annotate import OverlayPass, traces_for_batch
 
-            ovl = OverlayPass(overlay, ids, zones if overlay.zones else None, traces_for_batch(overlay, tracker, "infer_batch"))
+            ovl = OverlayPass(overlay, ids, zones if overlay.zones else None, traces_for_batch(overlay, tracker, "infer_batch"),
+                              heatmap if overlay.heat else None)
             if ovl.traces is not None:
                 ovl.traces.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
         if self.model.family == "fai_cls":
@@ -360,7 +378,7 @@ class FocoosModel:
             attach_ids(out, ids.cpu().tolist())
             warn_drops(tracker, "infer_batch")
         if zones is not None:
-            Z.attach(out, zones.fetch())
+            Z.attach(out, zones.fetch() if dwell is None else dwell.fetch(zones.fetch()))
         t3 = perf_counter()
         if annotate:
             annotate_results(self, drawable(inputs, images, self.model.device), images, pl, out, ovl)
@@ -371,7 +389,7 @@ class FocoosModel:
         return out
 
     def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate=False, track=None,
-                     mask_format: str = "png", zones=None, detections: bool = True):
+                     mask_format: str = "png", zones=None, detections: bool = True, dwell=None, heatmap=None):
         """Throughput inference (round 6): iterate over ``batches`` (each a list of images of ONE common shape after preprocessing and one
         batch size) and yield each batch's ``List[FocoosDetections]`` in order, with up to ``depth`` batches in flight on the engine's
         pipeline (engine.pipeline(): batch i+1's backbone runs beside batch i's decoder tail; default depth 3).  Same results as
@@ -399,7 +417,14 @@ class FocoosModel:
         GPU, zones without ``track`` count occupancy only.  The detections are those of ``zones=None``, which changes nothing.
         ``detections=False`` (needs ``zones``; ValueError with ``annotate`` or another ``mask_format`` than the default): the analytics-only
         mode - the detection objects are not built, every result is ``FocoosDetections(detections=[], zones=...)`` with the same zone
-        dicts."""
+        dicts.
+        ``dwell``: dwell times on the device (zones.py ``DeviceDwell``) - ``True`` (every ``Zone``), a list of zone names, or a
+        ``DeviceDwell`` whose state then outlives the call; needs ``zones`` and ``track`` (ValueError otherwise).  One more launch right
+        after the zones'; the dict of a dwell zone also carries ``dwell`` (frames, aligned with its ``detections``), ``visits``,
+        ``dwell_total``, ``dwell_max`` and ``dwell_mean``.  ``heatmap``: a ``heat.Heatmap`` or a ``heat.DeviceHeatmap`` (heat.py) -
+        every batch's anchors are accumulated on a grid on the device, nothing is copied back per frame (``DeviceHeatmap.grid()`` reads the
+        map) and ``annotate=Overlay(heat=True)`` blends it in under everything else; every input must have the heat map's size.  Both run
+        with ``detections=False`` too, and with both unset nothing changes."""
         from collections import deque
 
         from . import zones as Z
@@ -416,7 +441,12 @@ class FocoosModel:
             check_overlay(annotate, False, False, "fai_cls")
         track = resolve(track, self.model.family, self.model.device)
         zones, track = Z.resolve(zones, track, self.model.family)
-        overlay = check_overlay(annotate, track is not None, zones is not None, self.model.family) if annotate else None
+        dwell = Z.resolve_dwell(dwell, zones, track, self.model.family)
+        if heatmap is not None:
+            from . import heat as HM
+
+            heatmap = HM.resolve(heatmap, track is not None, self.model.family)
+        overlay = check_overlay(annotate, track is not None, zones is not None, self.model.family, heated=heatmap is not None) if annotate else None
         traces = None
         thr = threshold or self.processor.threshold
         if self.model.family == "fai_cls":
@@ -432,7 +462,11 @@ class FocoosModel:
             if track is not None:      # batches finish in order, so the frames reach the tracker in order
                 ids = track.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
             if zones is not None:      # one more launch, right after the tracker's, on the same packed results
-                zones.update(pl.det_labels, pl.det_boxes, pl.det_count, ids if zones.tracker is not None else None)
+                zv = zones.update(pl.det_labels, pl.det_boxes, pl.det_count, ids if zones.tracker is not None else None)
+                if dwell is not None:  # and the dwell times, from the masks the zones just wrote
+                    dwell.update(pl.det_count, ids, zv["det_inside"])
+            if heatmap is not None:    # this frame's anchors onto the grid; nothing comes back
+                heatmap.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
             if traces is not None:     # the tail of every track, appended right after the tracker (and the zones)
                 traces.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
             if not detections:         # analytics only: no detection objects, no ids on the host
@@ -444,9 +478,10 @@ class FocoosModel:
             if ids is not None and detections:
                 attach_ids(out, ids.cpu().tolist())
             if zones is not None:
-                Z.attach(out, zones.fetch())
+                Z.attach(out, zones.fetch() if dwell is None else dwell.fetch(zones.fetch()))
             if annotate:      # the lane's results stay valid until the lane is submitted to again, which happens after this returns
-                ovl = None if overlay is None else OverlayPass(overlay, ids, zones if overlay.zones else None, traces)
+                ovl = None if overlay is None else OverlayPass(overlay, ids, zones if overlay.zones else None, traces,
+                                                               heatmap if overlay.heat else None)
                 annotate_results(self, *frames.pop(ticket), pl, out, ovl)
             return out
 
@@ -462,6 +497,11 @@ class FocoosModel:
                 track = for_batch(track, B, x.device)      # created with the first batch, which fixes B
             if zones is not None:
                 zones = Z.for_batch(zones, B, track, x.device)
+            if dwell is not None:
+                dwell = Z.dwell_for_batch(dwell, zones)      # created on the call's DeviceZones with the first batch
+            if heatmap is not None:
+                HM.check_sizes(heatmap, self.processor.get_image_sizes(inputs))
+                heatmap = HM.for_batch(heatmap, B, x.device)
             if overlay is not None and overlay.traced and traces is None:
                 traces = traces_for_batch(overlay, track)      # created with the first batch, like the tracker it follows
             if pipe is None or (pipe.B, pipe.H, pipe.W) != (B, H, W):

@@ -5,8 +5,9 @@ analytics a camera deployment asks for after identity.  Everything the counter n
 box family leaves there and the tracker's ids (tracking.py) - so it is one ``fx_zone_update`` launch per batch, one workgroup per stream
 (csrc/zone_ops.hip; the contract is in include/focoos_amd.h), and a few hundred bytes more in the copy back.  Batch index b is stream b
 (camera b).  All decisions are integer ones; tests/zones_ref.py restates them and the GPU tests ask for equality.  The reference has no
-counterpart.  Left out on purpose: dwell times, heat maps and ``infer_tiled``; the regions and their counts are drawn by ``annotate=Overlay(...)``
-(annotate.py).
+counterpart.  Left out on purpose: ``infer_tiled``; the regions and their counts are drawn by ``annotate=Overlay(...)`` (annotate.py,
+DESIGN.md section 22); how long a track stays in a zone is ``DeviceDwell`` below (``infer_stream(dwell=...)``) and
+where the detections stand over time is heat.py.
 
 A detection is represented by its anchor, one of nine points of its integer box.  A ``Zone`` is an even-odd polygon (an axis-aligned
 rectangle is half-open: left and top edges inside, right and bottom edges outside); a ``Line`` from ``start`` to ``end`` observes the side
@@ -15,7 +16,8 @@ onto the segment.  A track whose observed side flips is an event: into a zone / 
 "exited".  The first observation of a track only records its side, and a detection without an id takes part in the occupancy only.
 
 After ``DeviceTracker.reset(b)`` the ids of stream b restart at 1, so they would meet the sides stored for the old ids:
-``DeviceZones.reset(b, counters=False)`` must follow it.  ``infer_stream`` never resets either."""
+``DeviceZones.reset(b, counters=False)`` must follow it, and so must ``DeviceDwell.reset(b, totals=False)`` (the visits in progress are
+keyed by the old ids).  ``infer_stream`` never resets any of them."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -33,6 +35,7 @@ ANCHORS = ("top_left", "top_center", "top_right", "center_left", "center", "cent
 KIND_ZONE, KIND_LINE = 0, 1
 REC_WORDS = 16         # fx_zone_region: kind, anchor, flags, vert_first, vert_count, class_words[8], reserved[3]
 KEYS = ("kind", "count", "detections", "entered", "exited", "crossed_in", "crossed_out")
+DWELL_KEYS = ("dwell", "visits", "dwell_total", "dwell_max", "dwell_mean")      # added to a dwell zone's dict; with fps also "dwell_seconds"
 
 
 def _is_int(v) -> bool:
@@ -310,6 +313,191 @@ class DeviceZones:
         R = self.R
         src = dict(st_id=self.st_id, st_side=self.st_side, in_total=self._io[:R], out_total=self._io[R:2 * R])
         return {k: src[k].cpu().numpy().copy() for k in self.STATE}
+
+
+def check_dwell_names(regions: Sequence[Region], names, what: str = "DeviceDwell") -> List[str]:
+    """The names of the zones whose dwell is kept (``names`` None / True: every Zone), validated on the host: each must name a Zone of
+    ``regions``, once."""
+    zone_names = [r.name for r in regions if isinstance(r, Zone)]
+    if names is None or names is True:
+        if not zone_names:
+            raise ValueError(f"{what}: regions: there is no Zone to keep dwell times for (a Line has no inside)")
+        return list(dict.fromkeys(zone_names))
+    if isinstance(names, (str, bytes)) or not isinstance(names, (list, tuple)):
+        raise ValueError(f"{what}: regions = {names!r}: must be None (every Zone) or a list of Zone names")
+    out = []
+    for n in names:
+        if any(r.name == n and isinstance(r, Line) for r in regions) and n not in zone_names:
+            raise ValueError(f"{what}: regions: {n!r} is a Line (dwell needs an inside: name a Zone)")
+        if n not in zone_names:
+            raise ValueError(f"{what}: regions: there is no Zone named {n!r}")
+        if n in out:
+            raise ValueError(f"{what}: regions: {n!r} is named twice")
+        out.append(n)
+    if not out:
+        raise ValueError(f"{what}: regions is empty")
+    return out
+
+
+def check_fps(fps, what: str = "DeviceDwell") -> Optional[float]:
+    if fps is None:
+        return None
+    if isinstance(fps, bool) or not isinstance(fps, (int, float, np.integer, np.floating)) or not fps > 0 or not np.isfinite(fps):
+        raise ValueError(f"{what}: fps = {fps!r}: must be None or a positive number (frames per second of every stream)")
+    return float(fps)
+
+
+def build_dwell_tables(per_stream: Sequence[Sequence[Region]], reg_first: np.ndarray, names: Sequence[str]):
+    """The host tables of ``fx_dwell_update``: (dw_first int32 [streams + 1], dw_region int32 [D_total], dw_bit int32 [D_total], rows = for
+    every stream the [(name, bit)] of its dwell rows in bit order)."""
+    first, region, bit, rows = [0], [], [], []
+    for b, regs in enumerate(per_stream):
+        mine = [(r.name, k) for k, r in enumerate(regs) if isinstance(r, Zone) and r.name in names]
+        rows.append(mine)
+        region.extend(int(reg_first[b]) + k for _, k in mine)
+        bit.extend(k for _, k in mine)
+        first.append(len(bit))
+    return np.asarray(first, np.int32), np.asarray(region, np.int32), np.asarray(bit, np.int32), rows
+
+
+class DeviceDwell:
+    """How long every track has been inside the zones ``regions`` (names; None = every ``Zone``) of ``zones``, and per zone the finished
+    visits, their total and their longest, in frames: one ``fx_dwell_update`` launch right after ``zones.update`` (csrc/dwell_ops.hip, the
+    contract is in include/focoos_amd.h).  Needs ``zones.tracker``: a visit belongs to a track.  A visit lasts from
+    its first to its last inside observation, inclusive; a frame in which the track is not detected does not end it.  ``fps`` (constant,
+    the same for every stream) adds the seconds.  The state belongs to this object and outlives the ``infer_stream`` calls it is passed to;
+    ``reset(b, totals=False)`` must follow ``DeviceTracker.reset(b)``."""
+
+    STATE = ("dw_id", "dw_enter", "dw_last", "visits", "dwell_sum", "dwell_max", "frame")
+
+    def __init__(self, zones: DeviceZones, regions: Optional[Sequence[str]] = None, fps: Optional[float] = None):
+        if not isinstance(zones, DeviceZones):
+            raise TypeError(f"DeviceDwell: zones must be a DeviceZones, not {type(zones).__name__}")
+        if zones.tracker is None:
+            raise ValueError("DeviceDwell: zones.tracker is None: dwell times belong to tracks (build the DeviceZones with tracker=)")
+        self.names = check_dwell_names(zones.regions, regions)
+        self.fps = check_fps(fps)
+        self.zones, self.lib, self.device = zones, zones.lib, zones.device
+        self.streams, self.max_tracks = zones.streams, zones.max_tracks
+        # the host copies stay alive: the library validates them at every update
+        self.dw_first, self.dw_region, self.dw_bit, self.rows = build_dwell_tables(zones.per_stream, zones.reg_first, self.names)
+        self.D = int(self.dw_first[-1])
+        self._d_first, self._d_bit = torch.from_numpy(self.dw_first).to(self.device), torch.from_numpy(self.dw_bit).to(self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        D, M = self.D, self.max_tracks
+        self.dw_id, self.dw_enter, self.dw_last = torch.zeros(D, M, **i32), torch.zeros(D, M, **i32), torch.zeros(D, M, **i32)
+        self.frame = torch.zeros(self.streams, **i32)
+        # one buffer = one copy back: dwell_sum [D] as int64 (2 D words, first: 8-byte aligned) | visits [D] | dwell_max [D] | det_dwell [D, T];
+        # the totals persist, det_dwell is written by every update; reallocated (totals carried over) when T changes
+        self._io, self._T = torch.zeros(4 * D, **i32), 0
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _views(self) -> Dict[str, torch.Tensor]:
+        D, io = self.D, self._io
+        return dict(dwell_sum=io[:2 * D].view(torch.int64), visits=io[2 * D:3 * D], dwell_max=io[3 * D:4 * D], det_dwell=io[4 * D:].view(D, self._T))
+
+    def update(self, det_count: torch.Tensor, track_ids: torch.Tensor, det_inside: torch.Tensor) -> torch.Tensor:
+        """One frame of every stream: ``det_count`` i32 [B], the ids the tracker gave THIS frame's detections (i32 [B, T]) and the
+        ``det_inside`` masks ``zones.update`` returned for it (i32 [B, T]).  Returns ``det_dwell`` i32 [D_total, T] on the device (a view the
+        next update overwrites): the frames the track of detection j has been in the zone of row d, 0 when it is not tracked or not inside."""
+        from ._lib import check
+
+        if track_ids is None or track_ids.dim() != 2:
+            raise ValueError("DeviceDwell.update: track_ids must be the tracker's ids of this frame, [B, T]")
+        B, T = int(track_ids.shape[0]), int(track_ids.shape[1])
+        if B != self.streams:
+            raise ValueError(f"DeviceDwell.update: a batch of {B} for dwell times of {self.streams} streams (batch index b is stream b)")
+        if not 1 <= T <= MAX_SLOTS:
+            raise ValueError(f"DeviceDwell.update: T = {T} detections per stream, must be in 1..{MAX_SLOTS}")
+        for name, t, shape in (("det_count", det_count, (B,)), ("track_ids", track_ids, (B, T)), ("det_inside", det_inside, (B, T))):
+            if tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != self.dw_id.device or not t.is_contiguous():
+                raise ValueError(f"DeviceDwell.update: {name} must be a contiguous torch.int32 tensor {shape} on {self.dw_id.device}, got "
+                                 f"{t.dtype} {tuple(t.shape)} on {t.device}")
+        if T != self._T:
+            io = torch.zeros(4 * self.D + self.D * T, dtype=torch.int32, device=self.device)
+            io[:4 * self.D] = self._io[:4 * self.D]
+            self._io, self._T = io, T
+        v = self._views()
+        check(self.lib.fx_dwell_update(det_count.data_ptr(), track_ids.data_ptr(), det_inside.data_ptr(), B, T, self.zones.tracker.id.data_ptr(),
+                                       self.max_tracks, self._d_first.data_ptr(), self._d_bit.data_ptr(), self.dw_first.ctypes.data,
+                                       self.dw_region.ctypes.data, self.dw_bit.ctypes.data, self.zones.reg_first.ctypes.data, self.D,
+                                       self.dw_id.data_ptr(), self.dw_enter.data_ptr(), self.dw_last.data_ptr(), v["visits"].data_ptr(),
+                                       v["dwell_sum"].data_ptr(), v["dwell_max"].data_ptr(), self.frame.data_ptr(), v["det_dwell"].data_ptr(),
+                                       self._stream()), "fx_dwell_update")
+        return v["det_dwell"]
+
+    def fetch(self, zone_dicts: Optional[List[Dict[str, dict]]] = None) -> List[Dict[str, dict]]:
+        """The last update on the host, in one copy, merged into ``zone_dicts`` (what ``zones.fetch()`` returned for the same frame; fetched
+        when None) and returned: the dict of every dwell zone gets ``dwell`` (frames, aligned with its ``detections``; 0 for an untracked
+        detection), ``visits`` / ``dwell_total`` / ``dwell_max`` (finished visits so far, in frames), ``dwell_mean`` = dwell_total / visits
+        (0.0 without a visit) and, with ``fps``, ``dwell_seconds`` (``dwell`` divided by fps)."""
+        if self._T == 0:
+            raise RuntimeError("DeviceDwell.fetch: no update yet")
+        if zone_dicts is None:
+            zone_dicts = self.zones.fetch()
+        h = self._io.cpu().numpy()
+        D = self.D
+        total = h[:2 * D].view(np.int64).tolist()
+        visits, longest = h[2 * D:3 * D].tolist(), h[3 * D:4 * D].tolist()
+        det = h[4 * D:].reshape(D, self._T)
+        for b, rows in enumerate(self.rows):
+            d0 = int(self.dw_first[b])
+            for i, (name, _) in enumerate(rows):
+                d, z = d0 + i, zone_dicts[b][name]
+                z["dwell"] = det[d, z["detections"]].tolist() if z["detections"] else []
+                z["visits"], z["dwell_total"], z["dwell_max"] = visits[d], total[d], longest[d]
+                z["dwell_mean"] = total[d] / visits[d] if visits[d] else 0.0
+                if self.fps is not None:
+                    z["dwell_seconds"] = [n / self.fps for n in z["dwell"]]
+        return zone_dicts
+
+    def reset(self, stream: Optional[int] = None, totals: bool = True) -> None:
+        """Forget the visits in progress of ``stream`` (all streams when None) and start its frame count again; with ``totals`` the
+        visits, their total and their longest start at 0 again.  ``reset(b, totals=False)`` is what must follow ``DeviceTracker.reset(b)``."""
+        from ._lib import check
+
+        if stream is not None and (not _is_int(stream) or not 0 <= stream < self.streams):
+            raise ValueError(f"DeviceDwell.reset: stream = {stream!r} must be in 0..{self.streams - 1} or None")
+        v = self._views()
+        check(self.lib.fx_dwell_reset(self.dw_id.data_ptr(), self.dw_enter.data_ptr(), self.dw_last.data_ptr(), v["visits"].data_ptr(),
+                                      v["dwell_sum"].data_ptr(), v["dwell_max"].data_ptr(), self.frame.data_ptr(), self.dw_first.ctypes.data,
+                                      self.streams, self.max_tracks, -1 if stream is None else int(stream), 1 if totals else 0, self._stream()),
+              "fx_dwell_reset")
+
+    def state(self) -> Dict[str, np.ndarray]:
+        """Host copies of the state arrays: dw_id / dw_enter / dw_last [D_total, max_tracks], visits / dwell_max int32 and dwell_sum int64
+        [D_total], frame [streams]."""
+        v = self._views()
+        src = dict(dw_id=self.dw_id, dw_enter=self.dw_enter, dw_last=self.dw_last, visits=v["visits"], dwell_sum=v["dwell_sum"],
+                   dwell_max=v["dwell_max"], frame=self.frame)
+        return {k: src[k].cpu().numpy().copy() for k in self.STATE}
+
+
+def resolve_dwell(dwell, zones, track, family: str, what: str = "infer_stream"):
+    """What ``dwell=`` means, decided on the host before anything touches the GPU (after ``resolve``): None / False -> None; True, a list of
+    Zone names or a DeviceDwell need ``zones=`` and a tracker.  Returns None, the DeviceDwell, or (names, None) to build with the first batch."""
+    if dwell is None or dwell is False:
+        return None
+    check_family(family, what)
+    if zones is None:
+        raise ValueError(f"{what}: dwell= needs zones= (dwell times are kept per Zone)")
+    if isinstance(dwell, DeviceDwell):
+        if dwell.zones is not zones:
+            raise ValueError(f"{what}: dwell: the DeviceDwell was built for another DeviceZones: pass that one as zones=")
+        return dwell
+    if what == "infer_batch":
+        raise TypeError(f"infer_batch: dwell must be a DeviceDwell, not {type(dwell).__name__}")
+    if track is None or (isinstance(zones, DeviceZones) and zones.tracker is None):
+        raise ValueError(f"{what}: dwell= needs track= (dwell times belong to tracks; a DeviceZones passed as zones= must be built on a tracker)")
+    regions = zones.regions if isinstance(zones, DeviceZones) else zones
+    return check_dwell_names(regions, None if dwell is True else dwell, f"{what}: dwell"), None
+
+
+def dwell_for_batch(dwell, zones: DeviceZones) -> DeviceDwell:
+    """The DeviceDwell of a call: created on the call's DeviceZones with the first batch from the validated names."""
+    return dwell if isinstance(dwell, DeviceDwell) else DeviceDwell(zones, dwell[0])
 
 
 def check_detections_flag(detections: bool, zones, annotate: bool, mask_format: str, what: str = "infer_stream") -> None:

@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 23
+#define FX_ABI_VERSION 24
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -625,6 +625,65 @@ int fx_trace_update(const int32_t* det_labels, const int32_t* det_boxes, const i
                     int32_t* trace_head, int32_t* trace_xy, fx_stream_t stream);
 int fx_trace_reset(int32_t* trace_id, int32_t* trace_label, int32_t* trace_len, int32_t* trace_head, int B, int max_tracks, int b,
                    fx_stream_t stream);
+
+/* ---- Dwell times and heat maps on the device (ABI 24; csrc/dwell_ops.hip, csrc/heat_ops.hip):
+ * FocoosModel.infer_stream(dwell=..., heatmap=..., annotate=Overlay(heat=True)).  Two independent accumulators over the packed results and
+ * one drawing pass.  Every decision is an integer one: tests/dwell_ref.py and tests/heat_ref.py restate the contracts and the GPU tests ask
+ * for equality.  No atomics; one writer per state element.  A refused argument returns FX_ERR_INVALID_ARGUMENT with nothing launched and
+ * nothing written.
+ *
+ * fx_dwell_update, one workgroup per stream, right after fx_zone_update (whose det_inside u32 [B][T] it reads; det_count i32 [B], track_ids
+ * i32 [B][T] and trk_id i32 [B][max_tracks] are the tracker's, ids >= 1, 0 = a free slot).  A DWELL ROW d is one (stream, zone) pair: row
+ * d of stream b (dw_first i32 [B + 1], dw_first[0] = 0, dw_first[B] = D_total, at most FX_ZONE_MAX_REGIONS rows per stream) watches bit
+ * dw_bit[d] of the stream's masks, which is region dw_region[d] = reg_first[b] + dw_bit[d] of fx_zone_update's tables.  dw_first / dw_bit
+ * are device buffers; dw_first_host / dw_region_host / dw_bit_host / reg_first_host are host copies, validated before the launch (offsets
+ * as above, every bit one the stream has, once per stream, dw_region consistent).  State, caller-owned device memory, all zero at first:
+ * dw_id / dw_enter / dw_last i32 [D_total][max_tracks], visits / dwell_max i32 [D_total], dwell_sum i64 [D_total] (8-byte aligned), frame
+ * i32 [B].  One update of stream b sets f = ++frame[b].  Slot t with id = trk_id[b][t] is OBSERVED when id > 0, no lower slot of the
+ * stream holds the same id and some j < clamp(det_count[b], 0, T) has track_ids[b][j] == id; the lowest such j is taken.  Then for every
+ * row d of the stream, in this order:
+ *  (a) dw_id[d][t] != 0 and != id (the tracker dropped or replaced the track): the visit is CLOSED - visits[d] += 1, dur = dw_last -
+ *      dw_enter + 1, dwell_sum[d] += dur, dwell_max[d] = max(dwell_max[d], dur), dw_id = 0 (dw_enter / dw_last keep their values);
+ *  (b) observed and bit dw_bit[d] of det_inside[b][j] set: dw_id == id -> dw_last = f; otherwise dw_id = id, dw_enter = dw_last = f;
+ *  (c) observed, the bit clear and dw_id == id: the visit is closed as in (a).
+ * An unobserved slot whose id is still alive is left alone: an occlusion inside a zone does not end the visit and the gap counts, so a
+ * visit lasts from its first to its last inside observation, inclusive, however it ends.  det_dwell i32 [D_total][T], every element
+ * written: f - dw_enter + 1 at the j of an observed slot inside, 0 elsewhere.  1 <= B <= FX_TRACK_MAX_STREAMS, 1 <= T, max_tracks <=
+ * FX_TRACK_MAX_SLOTS, D_total >= 1.  Duplicate ids stay memory-safe (one thread is the only writer of a slot).
+ * fx_dwell_reset: stream b (0 <= b < B), or every stream when b = -1: dw_id = dw_enter = dw_last = 0 in its rows, frame = 0 and, with
+ * clear_totals, visits = dwell_sum = dwell_max = 0.
+ *
+ * fx_heat_update: state heat i32 [B][Gh][Gw] (Gw = ceil(W / cell), Gh = ceil(H / cell); one hit = FX_HEAT_ONE) and heat_max i32 [B];
+ * part i32 [B][fx_heat_tiles(H, W, cell)] is scratch the call overwrites.  Per stream and per cell: (1) h -= h >> decay_shift when
+ * decay_shift > 0; (2) every detection j < clamp(det_count[b], 0, T) whose label passes class_words_host (8 words as in fx_zone_region,
+ * host memory, read during the call; FX_HEAT_ANY_CLASS admits every label) and, with FX_HEAT_TRACKED_ONLY, has track_ids[b][j] > 0, has the
+ * doubled anchor P of fx_zone_update (box clamped to [0, 16384], anchor 0 .. 8); it takes part iff P.x <= 2 W and P.y <= 2 H, its cell is
+ * ax = min(P.x div (2 cell), Gw - 1), ay likewise, and cell (gx, gy) receives FX_HEAT_ONE for every such detection with (gx - ax)^2 +
+ * (gy - ay)^2 <= radius^2; (3) h = min(h, 2^30).  heat_max[b] = the maximum of stream b's grid after the update.  1 <= B <=
+ * FX_TRACK_MAX_STREAMS, 1 <= T <= FX_TRACK_MAX_SLOTS, 1 <= H, W <= 16384, cell in {4, 8, 16, 32}, 0 <= radius <= 16, 0 <= decay_shift <= 15;
+ * det_boxes 16-byte aligned; track_ids may be null without FX_HEAT_TRACKED_ONLY.
+ *
+ * fx_annotate_heat_u8: dst [B][H][W][3] = src with the map of stream b0 + b blended in (dst == src or disjoint).  Per pixel (x, y), with
+ * c = cell: u = 2 x + 1 - c, gx0 = floor(u / 2c), fx = u - 2c gx0, the neighbours gx0 and gx0 + 1 clamped to [0, Gw - 1]; y alike.  A cell
+ * is read as clamp(h, 0, 2^30).  v = (h00 (2c - fx)(2c - fy) + h10 fx (2c - fy) + h01 (2c - fx) fy + h11 fx fy) >> (2 log2(2c)) in int64.
+ * S = 256 full_scale when full_scale > 0 (<= 2^22), else clamp(heat_max[b0 + b], 0, 2^30); with S <= 0 the frame is left alone (copied when
+ * dst != src).  idx = min(255, floor(255 v / S)); lut u32 [256] (device) holds R | G << 8 | B << 16 | A << 24; a = A + (A >> 7); when a > 0
+ * every channel becomes (p (256 - a) + colour a + 128) >> 8, otherwise the pixel keeps its bytes.  With dst == src a thread whose four
+ * pixels are untouched stores nothing.  1 <= B, b0 >= 0, b0 + B <= streams <= FX_TRACK_MAX_STREAMS. */
+#define FX_HEAT_ONE 256
+enum { FX_HEAT_ANY_CLASS = 1, FX_HEAT_TRACKED_ONLY = 2 };
+int fx_dwell_update(const int32_t* det_count, const int32_t* track_ids, const uint32_t* det_inside, int B, int T, const int32_t* trk_id,
+                    int max_tracks, const int32_t* dw_first, const int32_t* dw_bit, const int32_t* dw_first_host, const int32_t* dw_region_host,
+                    const int32_t* dw_bit_host, const int32_t* reg_first_host, int D_total, int32_t* dw_id, int32_t* dw_enter, int32_t* dw_last,
+                    int32_t* visits, int64_t* dwell_sum, int32_t* dwell_max, int32_t* frame, int32_t* det_dwell, fx_stream_t stream);
+int fx_dwell_reset(int32_t* dw_id, int32_t* dw_enter, int32_t* dw_last, int32_t* visits, int64_t* dwell_sum, int32_t* dwell_max, int32_t* frame,
+                   const int32_t* dw_first_host, int B, int max_tracks, int b, int clear_totals, fx_stream_t stream);
+int fx_heat_tiles(int H, int W, int cell); /* the length of a stream's row of `part`, or FX_ERR_INVALID_ARGUMENT (< 0) */
+int fx_heat_update(const int32_t* det_labels, const int32_t* det_boxes, const int32_t* det_count, const int32_t* track_ids, int B, int T, int H,
+                   int W, int cell, int radius, int anchor, int decay_shift, int flags, const uint32_t* class_words_host, int32_t* heat,
+                   int32_t* heat_max, int32_t* part, fx_stream_t stream);
+int fx_annotate_heat_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int b0, int streams, const int32_t* heat, const int32_t* heat_max,
+                        int cell, int full_scale, const uint32_t* lut, fx_stream_t stream);
 
 /* F.max_pool2d(k=3,s=2,p=1) (resnet.py:254) on NHWC bf16. */
 int fx_maxpool3x3s2_nhwc_bf16(const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, fx_stream_t stream);
