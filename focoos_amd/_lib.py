@@ -134,6 +134,9 @@ SIGNATURES = {
     "fx_frames_ingest": [_vp, _vp, _i, _vp, _i, _i, _i, _vp],
     "fx_merge_detections_workspace_bytes": [_i, _i],
     "fx_merge_detections_nms": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
+    "fx_frames_tile_gather_f32": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "fx_merge_detections_batched_workspace_bytes": [_i, _i, _i],
+    "fx_merge_detections_nms_batched": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "fx_annotate_labels_from_detections": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
     "fx_annotate_u8": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, C.c_int64, _vp, _vp, _i, _i, _i, _i, _vp],
     "fx_track_update": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _f, _i, _i, _f, _vp, _vp],
@@ -330,7 +333,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 24  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 25  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:
@@ -361,6 +364,7 @@ def load(name: str = None) -> C.CDLL:
     lib.fx_coco_match_workspace_bytes.restype = C.c_size_t
     lib.fx_mf_eval_masks_workspace_bytes.restype = C.c_size_t
     lib.fx_merge_detections_workspace_bytes.restype = C.c_size_t
+    lib.fx_merge_detections_batched_workspace_bytes.restype = C.c_size_t
     lib.fx_mask_rle_workspace_bytes.restype = C.c_size_t
     lib.fx_mask_polygon_workspace_bytes.restype = C.c_size_t
     lib.fx_error_string.argtypes = [C.c_int]

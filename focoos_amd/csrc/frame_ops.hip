@@ -6,6 +6,10 @@
 //                                   the tap / weight arithmetic is the one tile_gather_kernel uses (resize_common.h: multiply-adds spelled as
 //                                   fmaf for the reason given there), and the integer colour conversion is applied to every tap before the filter.
 //   fx_frames_ingest, out_f32 = 0   B frames of exactly (Ho, Wo) -> uint8 [B][Ho][Wo][3], the converted bytes.
+//   fx_frames_tile_gather_f32       S frames of ONE size x V shared windows -> float32 [S * V][Ho][Wo][3], the views of tiled inference of video
+//                                   streams in one launch.  View (s, v) is, bit for bit, what fx_tile_gather_u8_f32
+//                                   (tile_ops.hip) writes for window v of the bytes the uint8 path writes for frame s: the float path's row
+//                                   function with a window in the place of the whole frame.
 //
 // The conversion is integer only (include/focoos_amd.h states it; tests/frames_ref.py restates it in numpy), so both paths are pure
 // functions of their inputs.  fp32 / integer only: the FX_FP16 switch of the second library does not touch this file.
@@ -87,16 +91,18 @@ __device__ __forceinline__ void fi_tap(const FiRows& r, int x, const FiCoef& k, 
 }
 
 // ---- float path ----------------------------------------------------------------------------------------------------------------------------
-// One thread = 4 consecutive output pixels of one row; the two source lines and the vertical weights are computed once per thread.
+// One thread = 4 consecutive output pixels of one row of output image b; the two source lines and the vertical weights are computed once
+// per thread.  The source is the window (x0, y0, W, H) of the frame: taps are clamped to the WINDOW, then shifted by its origin, so the
+// chroma of a tap is read at its absolute frame position ((y0 + h) >> 1, (x0 + w) >> 1).  The whole frame is the window (0, 0, width, height).
 template <int FMT, bool VEC>
-__device__ __forceinline__ void fi_resize_row(const fx_frame_desc& d, float* __restrict__ y, int b, int ho, int wo0, int Ho, int Wo) {
-  const int H = d.height, W = d.width;
+__device__ __forceinline__ void fi_resize_row(const fx_frame_desc& d, int x0, int y0, int W, int H, float* __restrict__ y, int b, int ho, int wo0,
+                                              int Ho, int Wo) {
   const FiCoef k = fi_coef(d.matrix);
   const float sh = (float)H / (float)Ho, sw = (float)W / (float)Wo;
   int h0, h1;
   float lh0, lh1;
   fx_resize_src(ho, sh, H, h0, h1, lh0, lh1);
-  const FiRows r0 = fi_rows<FMT>(d, h0), r1 = fi_rows<FMT>(d, h1);
+  const FiRows r0 = fi_rows<FMT>(d, y0 + h0), r1 = fi_rows<FMT>(d, y0 + h1);
   float v[12];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -105,10 +111,10 @@ __device__ __forceinline__ void fi_resize_row(const fx_frame_desc& d, float* __r
     float lw0, lw1;
     fx_resize_src(wo, sw, W, w0, w1, lw0, lw1);
     int t00[3], t01[3], t10[3], t11[3];
-    fi_tap<FMT>(r0, w0, k, t00[0], t00[1], t00[2]);
-    fi_tap<FMT>(r0, w1, k, t01[0], t01[1], t01[2]);
-    fi_tap<FMT>(r1, w0, k, t10[0], t10[1], t10[2]);
-    fi_tap<FMT>(r1, w1, k, t11[0], t11[1], t11[2]);
+    fi_tap<FMT>(r0, x0 + w0, k, t00[0], t00[1], t00[2]);
+    fi_tap<FMT>(r0, x0 + w1, k, t01[0], t01[1], t01[2]);
+    fi_tap<FMT>(r1, x0 + w0, k, t10[0], t10[1], t10[2]);
+    fi_tap<FMT>(r1, x0 + w1, k, t11[0], t11[1], t11[2]);
 #pragma unroll
     for (int c = 0; c < 3; ++c)
       v[i * 3 + c] = fx_resize_filter(lh0, lh1, lw0, lw1, (float)t00[c], (float)t01[c], (float)t10[c], (float)t11[c]);
@@ -125,7 +131,19 @@ __device__ __forceinline__ void fi_resize_row(const fx_frame_desc& d, float* __r
   }
 }
 
-// Grid (row segments of 256 pixels, groups of 4 rows, frames).  The format is uniform within a workgroup: one branch.
+// The format is uniform within a workgroup: one branch.
+template <bool VEC>
+__device__ __forceinline__ void fi_resize_any(const fx_frame_desc& d, int x0, int y0, int W, int H, float* __restrict__ y, int b, int ho, int wo0,
+                                              int Ho, int Wo) {
+  switch (d.format) {
+    case FX_FRAME_RGB24: fi_resize_row<FX_FRAME_RGB24, VEC>(d, x0, y0, W, H, y, b, ho, wo0, Ho, Wo); break;
+    case FX_FRAME_BGR24: fi_resize_row<FX_FRAME_BGR24, VEC>(d, x0, y0, W, H, y, b, ho, wo0, Ho, Wo); break;
+    case FX_FRAME_NV12: fi_resize_row<FX_FRAME_NV12, VEC>(d, x0, y0, W, H, y, b, ho, wo0, Ho, Wo); break;
+    default: fi_resize_row<FX_FRAME_I420, VEC>(d, x0, y0, W, H, y, b, ho, wo0, Ho, Wo); break;
+  }
+}
+
+// Grid (row segments of 256 pixels, groups of 4 rows, frames).
 template <bool VEC>
 __global__ __launch_bounds__(FI_BX * FI_BY) void frames_resize_kernel(const fx_frame_desc* __restrict__ descs, float* __restrict__ y, int Ho,
                                                                       int Wo) {
@@ -135,12 +153,27 @@ __global__ __launch_bounds__(FI_BX * FI_BY) void frames_resize_kernel(const fx_f
   const int ho = blockIdx.y * FI_BY + threadIdx.y;
   const int wo0 = (blockIdx.x * FI_BX + threadIdx.x) * 4;
   if (ho >= Ho || wo0 >= Wo) return;
-  switch (s_d.format) {
-    case FX_FRAME_RGB24: fi_resize_row<FX_FRAME_RGB24, VEC>(s_d, y, b, ho, wo0, Ho, Wo); break;
-    case FX_FRAME_BGR24: fi_resize_row<FX_FRAME_BGR24, VEC>(s_d, y, b, ho, wo0, Ho, Wo); break;
-    case FX_FRAME_NV12: fi_resize_row<FX_FRAME_NV12, VEC>(s_d, y, b, ho, wo0, Ho, Wo); break;
-    default: fi_resize_row<FX_FRAME_I420, VEC>(s_d, y, b, ho, wo0, Ho, Wo); break;
-  }
+  fi_resize_any<VEC>(s_d, 0, 0, s_d.width, s_d.height, y, b, ho, wo0, Ho, Wo);
+}
+
+// Tiled inference of video streams (fx_frames_tile_gather_f32): view (s, v) = window v of frame s, resized to
+// (Ho, Wo).  Grid (row segments of 256 pixels, groups of 4 rows, S * V views); threads 0-15 load the frame's record and threads 16-19 the
+// window, once per workgroup.  A thread reads 2 lines x 8 taps; neighbouring threads read neighbouring taps of the same two lines, so a
+// wavefront's loads of one line fall into a run of 64 x 4 x scale source pixels (768 bytes of RGB or 256 of luma at scale 1).
+template <bool VEC>
+__global__ __launch_bounds__(FI_BX * FI_BY) void frames_tile_gather_kernel(const fx_frame_desc* __restrict__ descs,
+                                                                           const int32_t* __restrict__ windows, int V, float* __restrict__ y,
+                                                                           int Ho, int Wo) {
+  __shared__ fx_frame_desc s_d;
+  __shared__ int s_win[4];
+  const int n = blockIdx.z, s = n / V, v = n - s * V;
+  const int t = threadIdx.y * FI_BX + threadIdx.x;
+  if (t >= 16 && t < 20) s_win[t - 16] = windows[4 * v + t - 16];
+  fi_load_desc(&s_d, descs, s);
+  const int ho = blockIdx.y * FI_BY + threadIdx.y;
+  const int wo0 = (blockIdx.x * FI_BX + threadIdx.x) * 4;
+  if (ho >= Ho || wo0 >= Wo) return;
+  fi_resize_any<VEC>(s_d, s_win[0], s_win[1], s_win[2], s_win[3], y, n, ho, wo0, Ho, Wo);
 }
 
 // ---- uint8 same-size path ------------------------------------------------------------------------------------------------------------------
@@ -288,5 +321,21 @@ extern "C" int fx_frames_ingest(const fx_frame_desc* descs, const fx_frame_desc*
     if (fi_vec_ok(descs_host, B, Wo, y)) hipLaunchKernelGGL(frames_convert_kernel<true>, grid, block, 0, stream, descs, yb, Ho, Wo);
     else hipLaunchKernelGGL(frames_convert_kernel<false>, grid, block, 0, stream, descs, yb, Ho, Wo);
   }
+  return fx_launch_status();
+}
+
+extern "C" int fx_frames_tile_gather_f32(const fx_frame_desc* descs, const fx_frame_desc* descs_host, int S, const int32_t* windows,
+                                         const int32_t* windows_host, int V, float* y, int Ho, int Wo, fx_stream_t stream_) {
+  FX_CHECK_ARG(descs && descs_host && windows && windows_host && y && ((uintptr_t)descs & 7) == 0 && ((uintptr_t)windows & 3) == 0 &&
+               ((uintptr_t)y & 3) == 0);
+  FX_CHECK_ARG(S >= 1 && S <= FX_FRAME_MAX_BATCH && V >= 1 && (int64_t)S * V <= 65535 && Ho >= 1 && Wo >= 1 && Ho <= FX_FRAME_MAX_DIM &&
+               Wo <= FX_FRAME_MAX_DIM);
+  const int H = descs_host[0].height, W = descs_host[0].width;   // every frame must have this size: fi_descs_ok checks it and its range
+  FX_CHECK_ARG(fi_descs_ok(descs_host, S, 1, H, W) && fx_windows_ok(windows_host, V, H, W));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const dim3 grid((Wo + FI_BX * 4 - 1) / (FI_BX * 4), (Ho + FI_BY - 1) / FI_BY, S * V), block(FI_BX, FI_BY);
+  if (Wo % 4 == 0 && ((uintptr_t)y & 15) == 0)
+    hipLaunchKernelGGL(frames_tile_gather_kernel<true>, grid, block, 0, stream, descs, windows, V, y, Ho, Wo);
+  else hipLaunchKernelGGL(frames_tile_gather_kernel<false>, grid, block, 0, stream, descs, windows, V, y, Ho, Wo);
   return fx_launch_status();
 }

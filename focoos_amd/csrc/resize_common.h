@@ -25,3 +25,13 @@ __device__ __forceinline__ float fx_resize_filter(float lh0, float lh1, float lw
   const float top = fmaf(lw1, p01, lw0 * p00), bottom = fmaf(lw1, p11, lw0 * p10);
   return fmaf(lh0, top, lh1 * bottom);
 }
+
+// Windows (x0, y0, w, h) of an H x W frame, int32 [N][4]: the HOST copy is what the gathers check (the device copy is what their kernels
+// read).  A window that leaves the frame or has no extent would index out of bounds.
+static inline bool fx_windows_ok(const int32_t* wh, int N, int H, int W) {
+  for (int i = 0; i < N; ++i) {
+    const int x0 = wh[4 * i], y0 = wh[4 * i + 1], w = wh[4 * i + 2], h = wh[4 * i + 3];
+    if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > W - w || y0 > H - h) return false;
+  }
+  return true;
+}

@@ -7,6 +7,9 @@
 //   fx_merge_detections_nms  the per-view packed detections -> frame coordinates -> class-aware greedy NMS -> one packed list.  Integer
 //                            areas, one IEEE operation per side of the decision (contraction is off in this unit), so the result is a
 //                            pure function of the inputs and is compared for equality with the numpy restatement (tests/tiled_ref.py).
+//   fx_merge_detections_nms_batched  the same three kernels for S streams of V views (tiled inference of video streams, DESIGN.md section
+//                            24): the stream is a grid dimension, every stream has its own slice of the inputs, the outputs and the
+//                            workspace, and the single-frame entry point is the S = 1 case.
 //
 // fp32 / fp64 / integer only: the FX_FP16 switch of the second library does not touch this file.
 #include "det_common.h"
@@ -66,22 +69,12 @@ __global__ __launch_bounds__(TG_BX * TG_BY) void tile_gather_kernel(const uint8_
   }
 }
 
-// The host copy of the windows is what is checked (the device copy is what the kernel reads): a window that leaves the frame or has no
-// extent would index out of bounds.
-static bool tg_windows_ok(const int32_t* wh, int N, int H, int W) {
-  for (int i = 0; i < N; ++i) {
-    const int x0 = wh[4 * i], y0 = wh[4 * i + 1], w = wh[4 * i + 2], h = wh[4 * i + 3];
-    if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 > W - w || y0 > H - h) return false;
-  }
-  return true;
-}
-
 extern "C" int fx_tile_gather_u8_f32(const uint8_t* frame, int H, int W, const int32_t* windows, const int32_t* windows_host, int N, float* y,
                                      int Ho, int Wo, fx_stream_t stream_) {
   FX_CHECK_ARG(frame && windows && windows_host && y && ((uintptr_t)windows & 3) == 0 && ((uintptr_t)y & 3) == 0);
   FX_CHECK_ARG(N > 0 && N <= TG_MAX_VIEWS && H > 0 && W > 0 && Ho > 0 && Wo > 0 && H <= TG_MAX_DIM && W <= TG_MAX_DIM && Ho <= TG_MAX_DIM &&
                Wo <= TG_MAX_DIM);
-  FX_CHECK_ARG(tg_windows_ok(windows_host, N, H, W));
+  FX_CHECK_ARG(fx_windows_ok(windows_host, N, H, W));
   const dim3 grid((Wo + TG_BX * 4 - 1) / (TG_BX * 4), (Ho + TG_BY - 1) / TG_BY, N), block(TG_BX, TG_BY);
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (Wo % 4 == 0 && ((uintptr_t)y & 15) == 0) hipLaunchKernelGGL(tile_gather_kernel<true>, grid, block, 0, stream, frame, W, windows, y, Ho, Wo);
@@ -112,13 +105,16 @@ __device__ __forceinline__ uint64_t mg_key(float score, int flat) {
 // One thread per slot of [N][T].  A valid slot (slot < count[view]) counts the valid slots that precede it in the total order (every lane
 // reads the same address in the loop, so the compared keys arrive as broadcast loads) and, when that rank is below the cap, writes itself
 // into the sorted arrays: its box moved by its window's origin and clamped to the frame.  Ranks are a permutation of 0..M-1, so every
-// sorted entry below min(M, cap) is written exactly once.  Thread 0 also leaves M in the header.
+// sorted entry below min(M, cap) is written exactly once.  Thread 0 also leaves M in the header.  blockIdx.y is the stream: its N views
+// (the shared windows, its own slice of the packed results and of the workspace); the single-frame entry point is one stream.
 __global__ __launch_bounds__(256) void merge_rank_kernel(const float* __restrict__ scores, const int32_t* __restrict__ labels,
                                                           const int32_t* __restrict__ boxes, const int32_t* __restrict__ count,
                                                           const int32_t* __restrict__ windows, int N, int T, int frame_h, int frame_w,
                                                           unsigned char* __restrict__ ws) {
   const int64_t flat64 = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (flat64 >= (int64_t)N * T) return;
+  const int64_t first = (int64_t)blockIdx.y * N * T;   // S * N * T < 2^31 slots in all
+  scores += first, labels += first, boxes += first * 4, count += (int64_t)blockIdx.y * N, ws += (size_t)blockIdx.y * MG_WS_BYTES;
   const int flat = (int)flat64, n = flat / T, j = flat - n * T;
   const bool valid = j < fx_det_count(count, n, T);
   if (!valid && flat != 0) return;
@@ -144,10 +140,11 @@ __global__ __launch_bounds__(256) void merge_rank_kernel(const float* __restrict
 
 // Phase 1: workgroup (bj, bi) = one wavefront = the 64 x 64 block (rows 64 bi.., columns 64 bj..) of the upper triangle.  Lane l owns column
 // 64 bj + l; for each row the wave's ballot of "row removes column" is one mask word, kept by lane (row % 64) and stored after the loop.
-// Blocks below the diagonal or beyond the candidates exit; phase 2 reads exactly the words written here.
+// Blocks below the diagonal or beyond the candidates exit; phase 2 reads exactly the words written here.  blockIdx.z is the stream.
 __global__ __launch_bounds__(64) void merge_mask_kernel(unsigned char* __restrict__ ws, float thr, int ios) {
   __shared__ int4 s_box[64];
   __shared__ int s_lab[64];
+  ws += (size_t)blockIdx.z * MG_WS_BYTES;
   const int total = *reinterpret_cast<const int32_t*>(ws);
   const int M = total < MG_CAP ? total : MG_CAP;
   const int bj = blockIdx.x, bi = blockIdx.y, lane = threadIdx.x;
@@ -182,10 +179,14 @@ __global__ __launch_bounds__(64) void merge_mask_kernel(unsigned char* __restric
 // Phase 2: one wavefront.  Lane l keeps word l of the removed set.  Rows are walked in order, 8 at a time: the 8 mask rows are loaded
 // first (the loads do not depend on the walk, so their latencies overlap), then for each row the removed bit of the row is broadcast and, when
 // it is clear, every lane ORs its word of that row in.  Then the survivors are compacted in order: per word one ballot, positions from
-// its prefix popcount.  Slots from the count on are zeroed, so the outputs are fully defined.
+// its prefix popcount.  Slots from the count on are zeroed, so the outputs are fully defined.  blockIdx.x is the stream: its own
+// [max_det] slice of every output.
 __global__ __launch_bounds__(64) void merge_reduce_kernel(const unsigned char* __restrict__ ws, int max_det, float* __restrict__ out_scores,
                                                           int32_t* __restrict__ out_labels, int32_t* __restrict__ out_boxes,
                                                           int32_t* __restrict__ out_count, int32_t* __restrict__ status) {
+  const int64_t first = (int64_t)blockIdx.x * max_det;
+  ws += (size_t)blockIdx.x * MG_WS_BYTES, out_scores += first, out_labels += first, out_boxes += first * 4, out_count += blockIdx.x,
+      status += blockIdx.x;
   const int total = *reinterpret_cast<const int32_t*>(ws);
   const int M = total < MG_CAP ? total : MG_CAP;
   const int lane = threadIdx.x;
@@ -235,6 +236,40 @@ __global__ __launch_bounds__(64) void merge_reduce_kernel(const unsigned char* _
   }
 }
 
+// The three launches for S streams of N views each; S = 1 is the single-frame entry point.  Every argument has been checked.
+static int mg_launch(const float* det_scores, const int32_t* det_labels, const int32_t* det_boxes, const int32_t* det_count,
+                     const int32_t* windows, int S, int N, int T, int frame_h, int frame_w, float merge_threshold, int metric, int max_detections,
+                     float* out_scores, int32_t* out_labels, int32_t* out_boxes, int32_t* out_count, int32_t* status, void* workspace,
+                     fx_stream_t stream_) {
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
+  const int64_t slots = (int64_t)N * T;
+  hipLaunchKernelGGL(merge_rank_kernel, dim3((unsigned)((slots + 255) / 256), S), dim3(256), 0, stream, det_scores, det_labels, det_boxes,
+                     det_count, windows, N, T, frame_h, frame_w, ws);
+  if (fx_launch_status() != FX_OK) return FX_ERR_LAUNCH;
+  hipLaunchKernelGGL(merge_mask_kernel, dim3(MG_WORDS, MG_WORDS, S), dim3(64), 0, stream, ws, merge_threshold, metric == FX_MERGE_IOS ? 1 : 0);
+  if (fx_launch_status() != FX_OK) return FX_ERR_LAUNCH;
+  hipLaunchKernelGGL(merge_reduce_kernel, dim3(S), dim3(64), 0, stream, ws, max_detections, out_scores, out_labels, out_boxes, out_count, status);
+  return fx_launch_status();
+}
+
+static bool mg_args_ok(const void* det_scores, const void* det_labels, const void* det_boxes, const void* det_count, const void* windows, int64_t S,
+                       int N, int T, int frame_h, int frame_w, float merge_threshold, int metric, int max_detections, const void* out_scores,
+                       const void* out_labels, const void* out_boxes, const void* out_count, const void* status, const void* workspace,
+                       size_t workspace_bytes) {
+  if (!(det_scores && det_labels && det_boxes && det_count && windows && out_scores && out_labels && out_boxes && out_count && status && workspace))
+    return false;
+  if ((((uintptr_t)det_scores | (uintptr_t)det_labels | (uintptr_t)det_boxes | (uintptr_t)det_count | (uintptr_t)windows | (uintptr_t)out_scores |
+        (uintptr_t)out_labels | (uintptr_t)out_count | (uintptr_t)status) & 3) != 0)
+    return false;
+  if ((((uintptr_t)out_boxes | (uintptr_t)workspace) & 15) != 0) return false;
+  if (!(S > 0 && S <= 65535 && N > 0 && T > 0 && (int64_t)N * T < (1ll << 31) && S * ((int64_t)N * T) < (1ll << 31) && frame_h > 0 && frame_w > 0 && frame_h <= TG_MAX_DIM &&
+        frame_w <= TG_MAX_DIM))
+    return false;
+  if (!(merge_threshold > 0.0f && merge_threshold <= 1.0f && (metric == FX_MERGE_IOU || metric == FX_MERGE_IOS) && max_detections >= 1)) return false;
+  return workspace_bytes >= (size_t)S * MG_WS_BYTES;
+}
+
 extern "C" size_t fx_merge_detections_workspace_bytes(int N, int T) {
   if (N <= 0 || T <= 0 || (int64_t)N * T >= (1ll << 31)) return 0;
   return MG_WS_BYTES;
@@ -243,23 +278,25 @@ extern "C" size_t fx_merge_detections_workspace_bytes(int N, int T) {
 extern "C" int fx_merge_detections_nms(const float* det_scores, const int32_t* det_labels, const int32_t* det_boxes, const int32_t* det_count,
                                        const int32_t* windows, int N, int T, int frame_h, int frame_w, float merge_threshold, int metric,
                                        int max_detections, float* out_scores, int32_t* out_labels, int32_t* out_boxes, int32_t* out_count,
-                                       int32_t* status, void* workspace, size_t workspace_bytes, fx_stream_t stream_) {
-  FX_CHECK_ARG(det_scores && det_labels && det_boxes && det_count && windows && out_scores && out_labels && out_boxes && out_count && status &&
-               workspace);
-  FX_CHECK_ARG((((uintptr_t)det_scores | (uintptr_t)det_labels | (uintptr_t)det_boxes | (uintptr_t)det_count | (uintptr_t)windows |
-                 (uintptr_t)out_scores | (uintptr_t)out_labels | (uintptr_t)out_count | (uintptr_t)status) & 3) == 0);
-  FX_CHECK_ARG((((uintptr_t)out_boxes | (uintptr_t)workspace) & 15) == 0);
-  FX_CHECK_ARG(N > 0 && T > 0 && (int64_t)N * T < (1ll << 31) && frame_h > 0 && frame_w > 0 && frame_h <= TG_MAX_DIM && frame_w <= TG_MAX_DIM);
-  FX_CHECK_ARG(merge_threshold > 0.0f && merge_threshold <= 1.0f && (metric == FX_MERGE_IOU || metric == FX_MERGE_IOS) && max_detections >= 1);
-  FX_CHECK_ARG(workspace_bytes >= MG_WS_BYTES);
-  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-  const int64_t slots = (int64_t)N * T;
-  hipLaunchKernelGGL(merge_rank_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, det_scores, det_labels, det_boxes, det_count,
-                     windows, N, T, frame_h, frame_w, ws);
-  if (fx_launch_status() != FX_OK) return FX_ERR_LAUNCH;
-  hipLaunchKernelGGL(merge_mask_kernel, dim3(MG_WORDS, MG_WORDS), dim3(64), 0, stream, ws, merge_threshold, metric == FX_MERGE_IOS ? 1 : 0);
-  if (fx_launch_status() != FX_OK) return FX_ERR_LAUNCH;
-  hipLaunchKernelGGL(merge_reduce_kernel, dim3(1), dim3(64), 0, stream, ws, max_detections, out_scores, out_labels, out_boxes, out_count, status);
-  return fx_launch_status();
+                                       int32_t* status, void* workspace, size_t workspace_bytes, fx_stream_t stream) {
+  FX_CHECK_ARG(mg_args_ok(det_scores, det_labels, det_boxes, det_count, windows, 1, N, T, frame_h, frame_w, merge_threshold, metric, max_detections,
+                          out_scores, out_labels, out_boxes, out_count, status, workspace, workspace_bytes));
+  return mg_launch(det_scores, det_labels, det_boxes, det_count, windows, 1, N, T, frame_h, frame_w, merge_threshold, metric, max_detections,
+                   out_scores, out_labels, out_boxes, out_count, status, workspace, stream);
+}
+
+extern "C" size_t fx_merge_detections_batched_workspace_bytes(int S, int V, int T) {
+  if (S <= 0 || S > 65535 || V <= 0 || T <= 0 || (int64_t)V * T >= (1ll << 31) || (int64_t)S * ((int64_t)V * T) >= (1ll << 31)) return 0;
+  return (size_t)S * MG_WS_BYTES;
+}
+
+extern "C" int fx_merge_detections_nms_batched(const float* det_scores, const int32_t* det_labels, const int32_t* det_boxes,
+                                               const int32_t* det_count, const int32_t* windows, int S, int V, int T, int frame_h, int frame_w,
+                                               float merge_threshold, int metric, int max_detections, float* out_scores, int32_t* out_labels,
+                                               int32_t* out_boxes, int32_t* out_count, int32_t* status, void* workspace, size_t workspace_bytes,
+                                               fx_stream_t stream) {
+  FX_CHECK_ARG(mg_args_ok(det_scores, det_labels, det_boxes, det_count, windows, S, V, T, frame_h, frame_w, merge_threshold, metric, max_detections,
+                          out_scores, out_labels, out_boxes, out_count, status, workspace, workspace_bytes));
+  return mg_launch(det_scores, det_labels, det_boxes, det_count, windows, S, V, T, frame_h, frame_w, merge_threshold, metric, max_detections,
+                   out_scores, out_labels, out_boxes, out_count, status, workspace, stream);
 }

@@ -283,7 +283,7 @@ class FocoosModel:
         return self.model.device
 
     def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate=False, tracker=None,
-                    mask_format: str = "png", zones=None, dwell=None, heatmap=None) -> List[FocoosDetections]:
+                    mask_format: str = "png", zones=None, dwell=None, heatmap=None, tiling=None) -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
         reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``inputs`` may also be a
         ``frames.FrameBatch`` of NV12 / I420 / BGR / RGB video frames, host or device: the results are those of the same frames passed as
@@ -301,11 +301,20 @@ class FocoosModel:
         ``tracker`` for zone and line counting (zones.py): every result carries ``.zones``; a DeviceZones built on a tracker
         runs that tracker (``tracker`` must be None or that one).  ``dwell``: a ``zones.DeviceDwell`` built on that DeviceZones - the dicts
         of its zones also carry the dwell times; ``heatmap``: a ``heat.DeviceHeatmap`` of ``len(inputs)`` streams, updated from
-        every batch and drawn by ``annotate=Overlay(heat=True)`` (heat.py)."""
+        every batch and drawn by ``annotate=Overlay(heat=True)`` (heat.py).  ``tiling``: a ``tiled.Tiling`` - every input is a
+        large frame of stream b (a ``FrameBatch``, or a list of ``Frame`` s and / or uint8 RGB arrays, all of one size) that is cut into
+        windows, run through the engine in chunks and merged per stream on the device into one packed result in frame pixels, which the
+        tracker, the zones, the heat map, the overlay and the detections then read as they read the engine's (tiled.py); fai_detr
+        only (NotImplementedError otherwise), mixed sizes or non-uint8 inputs raise ValueError, all before anything touches the GPU."""
         from .frames import as_frame_batch, drawable
         from .mask_rle import check_mask_format
 
         check_mask_format(mask_format, self.model.family, "infer_batch")
+        if tiling is not None:
+            from . import tiled as TL
+
+            TL.check_tiling(self, tiling, "infer_batch")
+            inputs = TL.stream_frames(inputs, "infer_batch")
         tracked = tracker is not None or getattr(zones, "tracker", None) is not None
         if heatmap is not None:
             from . import heat as HM
@@ -344,11 +353,16 @@ class FocoosModel:
                 raise TypeError(f"infer_batch: tracker must be a DeviceTracker, not {type(tracker).__name__}")
             for_batch(tracker, len(inputs), self.model.device, "infer_batch")
         t0 = perf_counter()
-        images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
-        t1 = perf_counter()
-        sizes = torch.tensor(self.processor.get_image_sizes(inputs), dtype=torch.int32)
         thr = threshold or self.processor.threshold
-        pl = self.model.detect(images, sizes=sizes, threshold=thr)
+        if tiling is not None:       # the views of every frame in one launch, the chunks on one plan, one merge: `pl` is the merged result
+            t1 = t0
+            pl, tiler = TL.infer_batch_tiled(self, inputs, tiling, thr)
+            images = tiler.rgb(inputs) if annotate else None      # the full-size frames, already resident, are what is drawn on
+        else:
+            images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
+            t1 = perf_counter()
+            sizes = torch.tensor(self.processor.get_image_sizes(inputs), dtype=torch.int32)
+            pl = self.model.detect(images, sizes=sizes, threshold=thr)
         torch.cuda.current_stream(self.model.device).synchronize()
         t2 = perf_counter()
         ids = None
@@ -379,6 +393,8 @@ class FocoosModel:
             warn_drops(tracker, "infer_batch")
         if zones is not None:
             Z.attach(out, zones.fetch() if dwell is None else dwell.fetch(zones.fetch()))
+        if tiling is not None:
+            TL.warn_dropped(tiler.status, "infer_batch")
         t3 = perf_counter()
         if annotate:
             annotate_results(self, drawable(inputs, images, self.model.device), images, pl, out, ovl)
@@ -389,7 +405,7 @@ class FocoosModel:
         return out
 
     def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate=False, track=None,
-                     mask_format: str = "png", zones=None, detections: bool = True, dwell=None, heatmap=None):
+                     mask_format: str = "png", zones=None, detections: bool = True, dwell=None, heatmap=None, tiling=None):
         """Throughput inference (round 6): iterate over ``batches`` (each a list of images of ONE common shape after preprocessing and one
         batch size) and yield each batch's ``List[FocoosDetections]`` in order, with up to ``depth`` batches in flight on the engine's
         pipeline (engine.pipeline(): batch i+1's backbone runs beside batch i's decoder tail; default depth 3).  Same results as
@@ -424,7 +440,15 @@ class FocoosModel:
         ``dwell_total``, ``dwell_max`` and ``dwell_mean``.  ``heatmap``: a ``heat.Heatmap`` or a ``heat.DeviceHeatmap`` (heat.py) -
         every batch's anchors are accumulated on a grid on the device, nothing is copied back per frame (``DeviceHeatmap.grid()`` reads the
         map) and ``annotate=Overlay(heat=True)`` blends it in under everything else; every input must have the heat map's size.  Both run
-        with ``detections=False`` too, and with both unset nothing changes."""
+        with ``detections=False`` too, and with both unset nothing changes.
+        ``tiling``: a ``tiled.Tiling`` - tiled inference of video streams (tiled.py).  Every input of a batch (a ``FrameBatch``,
+        or a list of ``Frame`` s and / or uint8 RGB arrays, all of one size) is a large frame of stream b; it is cut into the windows of
+        ``tiled.views_of``, all windows of all frames run through ONE engine pipeline in chunks of ``Tiling.batch_size`` (the chunks of
+        frame batch i+1 are in flight while batch i is merged and packed) and are merged per stream on the device into one packed result in
+        frame pixels.  Everything above then reads that result exactly as it reads the engine's: ``track``, ``zones``, ``dwell``,
+        ``heatmap``, ``annotate`` (drawn on the full-size frames, which are resident), ``detections=False``.  fai_detr only
+        (NotImplementedError before anything touches the GPU); frames of one batch that differ in size, or non-uint8 inputs, raise
+        ValueError; candidates dropped by the suppression cap warn once per call.  With ``None`` nothing changes."""
         from collections import deque
 
         from . import zones as Z
@@ -433,6 +457,10 @@ class FocoosModel:
 
         Z.check_detections_flag(detections, zones, annotate, mask_format)
         check_mask_format(mask_format, self.model.family, "infer_stream")
+        if tiling is not None:
+            from . import tiled as TL
+
+            TL.check_tiling(self, tiling, "infer_stream")
 
         from .annotate import OverlayPass, annotate_results, check_inputs, check_overlay, traces_for_batch
         from .tracking import TrackerConfig, attach_ids, for_batch, resolve, warn_drops
@@ -457,7 +485,9 @@ class FocoosModel:
 
         def finish():
             ticket = pending.popleft()
-            pl = pipe.wait(ticket)
+            return analyse(pipe.wait(ticket), pipe.B, frames.pop(ticket, None))
+
+        def analyse(pl, B, drawn):      # `pl`: a lane's plan, or with tiling the merged result, which has the same packed fields
             ids = None
             if track is not None:      # batches finish in order, so the frames reach the tracker in order
                 ids = track.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
@@ -470,7 +500,7 @@ class FocoosModel:
             if traces is not None:     # the tail of every track, appended right after the tracker (and the zones)
                 traces.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
             if not detections:         # analytics only: no detection objects, no ids on the host
-                out = [FocoosDetections(detections=[]) for _ in range(pipe.B)]
+                out = [FocoosDetections(detections=[]) for _ in range(B)]
             elif mask_family:
                 out = self.processor.pack_detections(pl, self.model_info.classes, mask_format=mask_format)
             else:
@@ -482,9 +512,28 @@ class FocoosModel:
             if annotate:      # the lane's results stay valid until the lane is submitted to again, which happens after this returns
                 ovl = None if overlay is None else OverlayPass(overlay, ids, zones if overlay.zones else None, traces,
                                                                heatmap if overlay.heat else None)
-                annotate_results(self, *frames.pop(ticket), pl, out, ovl)
+                annotate_results(self, *drawn, pl, out, ovl)
             return out
 
+        def prepare(inputs, B, device):      # the call's device state, created with the first batch, which fixes B
+            nonlocal track, zones, dwell, heatmap, traces
+            if track is not None:
+                track = for_batch(track, B, device)
+            if zones is not None:
+                zones = Z.for_batch(zones, B, track, device)
+            if dwell is not None:
+                dwell = Z.dwell_for_batch(dwell, zones)      # created on the call's DeviceZones with the first batch
+            if heatmap is not None:
+                HM.check_sizes(heatmap, self.processor.get_image_sizes(inputs))
+                heatmap = HM.for_batch(heatmap, B, device)
+            if overlay is not None and overlay.traced and traces is None:
+                traces = traces_for_batch(overlay, track)      # created with the first batch, like the tracker it follows
+
+        if tiling is not None:      # the same tail (`analyse`) on the merged result of every frame batch (tiled.py)
+            yield from TL.infer_stream_tiled(self, batches, tiling, thr, depth, prepare, analyse, bool(annotate))
+            if track is not None and not isinstance(track, TrackerConfig):
+                warn_drops(track)
+            return
         for inputs in batches:
             inputs = as_frame_batch(inputs) or inputs
             if annotate:
@@ -493,17 +542,7 @@ class FocoosModel:
             x = self.model._to_nhwc(images)
             sizes = torch.tensor(self.processor.get_image_sizes(inputs), dtype=torch.int32, device=x.device)
             B, H, W, _ = x.shape
-            if track is not None:
-                track = for_batch(track, B, x.device)      # created with the first batch, which fixes B
-            if zones is not None:
-                zones = Z.for_batch(zones, B, track, x.device)
-            if dwell is not None:
-                dwell = Z.dwell_for_batch(dwell, zones)      # created on the call's DeviceZones with the first batch
-            if heatmap is not None:
-                HM.check_sizes(heatmap, self.processor.get_image_sizes(inputs))
-                heatmap = HM.for_batch(heatmap, B, x.device)
-            if overlay is not None and overlay.traced and traces is None:
-                traces = traces_for_batch(overlay, track)      # created with the first batch, like the tracker it follows
+            prepare(inputs, B, x.device)
             if pipe is None or (pipe.B, pipe.H, pipe.W) != (B, H, W):
                 while pending:
                     yield finish()

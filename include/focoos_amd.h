@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 24
+#define FX_ABI_VERSION 25
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -305,6 +305,20 @@ int fx_merge_detections_nms(const float* det_scores, const int32_t* det_labels, 
                             float* out_scores, int32_t* out_labels, int32_t* out_boxes, int32_t* out_count, int32_t* status, void* workspace,
                             size_t workspace_bytes, fx_stream_t stream);
 
+/* fx_merge_detections_nms_batched (ABI 25): S streams of V views each in the same three launches.  The packed results
+ * are [S * V][T] (view v of stream s is row s * V + v), the windows int32 [V][4] are shared by every stream; out_scores f32 [S][max_detections],
+ * out_labels i32 [S][max_detections], out_boxes i32 [S][max_detections][4] (16-byte aligned), out_count i32 [S], status i32 [S] (zeroed by the
+ * caller).  Stream s's outputs are, bit for bit, what fx_merge_detections_nms gives on its own V views: order, clamp, the cap of
+ * FX_MERGE_NMS_CAP per stream, the zeroed tail, status[s] += dropped.  The kernels are the same ones with the stream as a grid dimension
+ * (fx_merge_detections_nms is S = 1); no atomics.  workspace: fx_merge_detections_batched_workspace_bytes(S, V, T) bytes = S times the
+ * single-frame layout (0 for invalid S, V, T), 16-byte aligned.  S <= 65535, S * V * T < 2^31, everything else as above; anything outside the
+ * contract: FX_ERR_INVALID_ARGUMENT, nothing launched, nothing written.  The same in both libraries. */
+size_t fx_merge_detections_batched_workspace_bytes(int S, int V, int T);
+int fx_merge_detections_nms_batched(const float* det_scores, const int32_t* det_labels, const int32_t* det_boxes, const int32_t* det_count,
+                                    const int32_t* windows, int S, int V, int T, int frame_h, int frame_w, float merge_threshold, int metric,
+                                    int max_detections, float* out_scores, int32_t* out_labels, int32_t* out_boxes, int32_t* out_count,
+                                    int32_t* status, void* workspace, size_t workspace_bytes, fx_stream_t stream);
+
 /* ---- Drawing the detections on uint8 frames on the device (ABI 17; csrc/annotate.hip): FocoosModel.infer(annotate=True).
  * A label record is the filled rectangle (x0, y0, w, h) of one text line in frame pixels, its colour (R | G << 8 | B << 16) and nchar glyph
  * indices (ASCII code - 32, 0..94); nchar = 0 (w = h = 0) draws nothing. */
@@ -550,6 +564,19 @@ typedef struct fx_frame_desc {
   int32_t reserved[3];
 } fx_frame_desc; /* 64 bytes */
 int fx_frames_ingest(const fx_frame_desc* descs, const fx_frame_desc* descs_host, int B, void* y, int out_f32, int Ho, int Wo, fx_stream_t stream);
+
+/* fx_frames_tile_gather_f32 (ABI 25; csrc/frame_ops.hip): the views of tiled inference straight from S video frames, one
+ * launch.  descs / descs_host = fx_frame_desc [S] as for fx_frames_ingest, here all of ONE height and width; windows = int32 [V][4]
+ * (x0, y0, w, h), a DEVICE array shared by every frame, windows_host the same values in host memory; y = float32 [S * V][Ho][Wo][3] on the
+ * 0..255 scale, every element written.  View s * V + v is, bit for bit, what fx_tile_gather_u8_f32 writes for window v of the bytes that
+ * fx_frames_ingest (out_f32 = 0) writes for frame s: taps are clamped to the window and shifted by its origin, the conversion is applied per
+ * tap before the filter, and the chroma of a tap is read at its absolute frame position ((y0 + y) >> 1, (x0 + x) >> 1).  16-byte stores when
+ * Wo % 4 == 0 and y is 16-byte aligned.  The host copies are validated before anything is launched: the descriptors as for fx_frames_ingest
+ * plus the common size, the windows with positive extents inside the frame, 1 <= S <= 65535, S * V <= 65535, Ho, Wo <= 16384, descs 8-byte,
+ * windows and y 4-byte aligned.  Anything outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched, nothing written.  The same in
+ * both libraries. */
+int fx_frames_tile_gather_f32(const fx_frame_desc* descs, const fx_frame_desc* descs_host, int S, const int32_t* windows,
+                              const int32_t* windows_host, int V, float* y, int Ho, int Wo, fx_stream_t stream);
 
 /* ---- Zones, lines, counts, track ids and traces drawn on device frames (ABI 23; csrc/overlay.hip):
  * FocoosModel.infer_stream(annotate=Overlay(...)).  Five entry points beside the two of ABI 17; every output byte is an integer function of the
