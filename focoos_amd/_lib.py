@@ -135,6 +135,9 @@ SIGNATURES = {
     "fx_merge_detections_workspace_bytes": [_i, _i],
     "fx_merge_detections_nms": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "fx_frames_tile_gather_f32": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "fx_roi_select": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp],
+    "fx_frames_roi_gather_f32": [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp],
+    "fx_roi_attributes": [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "fx_merge_detections_batched_workspace_bytes": [_i, _i, _i],
     "fx_merge_detections_nms_batched": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "fx_annotate_labels_from_detections": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp],
@@ -333,7 +336,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 25  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 26  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:

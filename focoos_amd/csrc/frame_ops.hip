@@ -10,9 +10,13 @@
 //                                   streams in one launch.  View (s, v) is, bit for bit, what fx_tile_gather_u8_f32
 //                                   (tile_ops.hip) writes for window v of the bytes the uint8 path writes for frame s: the float path's row
 //                                   function with a window in the place of the whole frame.
+//   fx_frames_roi_gather_f32        S frames of any sizes x K windows each, read from a DEVICE array and clamped to the frame by the kernel ->
+//                                   float32 [S * K][Ho][Wo][3], the crops a second model classifies.  A crop with an extent
+//                                   is, bit for bit, the tile gather's view of that window of that frame; one without is left untouched.
 //
 // The conversion is integer only (include/focoos_amd.h states it; tests/frames_ref.py restates it in numpy), so both paths are pure
 // functions of their inputs.  fp32 / integer only: the FX_FP16 switch of the second library does not touch this file.
+#include "frame_common.h"
 #include "resize_common.h"
 
 #pragma clang fp contract(off)
@@ -20,8 +24,6 @@
 #define FI_BX 64   // threads along a row: 64 x 4 pixels = 256 pixels per row segment (float path), 64 x 16 = 1024 (uint8 path)
 #define FI_BY 4    // rows per workgroup
 #define FI_PX 16   // pixels of one thread on the uint8 path
-
-static_assert(sizeof(fx_frame_desc) == 64, "fx_frame_desc is 16 dwords: one per thread of the descriptor load");
 
 // (cy, crv, cgu, cgv, cbu, luma offset) of matrix 0..3: the standard matrices times 256, rounded
 struct FiCoef {
@@ -176,6 +178,33 @@ __global__ __launch_bounds__(FI_BX * FI_BY) void frames_tile_gather_kernel(const
   fi_resize_any<VEC>(s_d, s_win[0], s_win[1], s_win[2], s_win[3], y, n, ho, wo0, Ho, Wo);
 }
 
+// Crops for a second model (fx_frames_roi_gather_f32): crop (s, k) = window roi_win[s][k] of frame s, resized to
+// (Ho, Wo).  The same grid and loads as the tile gather, with S * K crops; here the windows are DEVICE values that no host check has seen
+// (fx_roi_select wrote them), so every workgroup clamps its window to its own frame before use: the origin into [0, W - 1] x [0, H - 1],
+// the extent to what is left of the frame from there.  After the clamp 0 <= x0, x0 + w <= W, 0 <= y0, y0 + h <= H, which is all
+// fi_resize_row needs to stay inside the planes.  A window without an extent writes nothing.
+template <bool VEC>
+__global__ __launch_bounds__(FI_BX * FI_BY) void frames_roi_gather_kernel(const fx_frame_desc* __restrict__ descs,
+                                                                          const int32_t* __restrict__ roi_win, int K, float* __restrict__ y,
+                                                                          int Ho, int Wo) {
+  __shared__ fx_frame_desc s_d;
+  __shared__ int s_win[4];
+  const int n = blockIdx.z, s = n / K;
+  const int t = threadIdx.y * FI_BX + threadIdx.x;
+  if (t >= 16 && t < 20) s_win[t - 16] = roi_win[4 * (int64_t)n + t - 16];
+  fi_load_desc(&s_d, descs, s);
+  const int ho = blockIdx.y * FI_BY + threadIdx.y;
+  const int wo0 = (blockIdx.x * FI_BX + threadIdx.x) * 4;
+  if (ho >= Ho || wo0 >= Wo) return;
+  const int W = s_d.width, H = s_d.height;
+  const int x0 = s_win[0] < 0 ? 0 : (s_win[0] > W - 1 ? W - 1 : s_win[0]);
+  const int y0 = s_win[1] < 0 ? 0 : (s_win[1] > H - 1 ? H - 1 : s_win[1]);
+  const int w = s_win[2] < W - x0 ? s_win[2] : W - x0;
+  const int h = s_win[3] < H - y0 ? s_win[3] : H - y0;
+  if (w < 1 || h < 1) return;
+  fi_resize_any<VEC>(s_d, x0, y0, w, h, y, n, ho, wo0, Ho, Wo);
+}
+
 // ---- uint8 same-size path ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int fi_byte(const uint32_t* w, int i) { return (int)((w[i >> 2] >> (8 * (i & 3))) & 255u); }
 __device__ __forceinline__ void fi_put(uint32_t* w, int i, int v) { w[i >> 2] |= (uint32_t)v << (8 * (i & 3)); }
@@ -269,28 +298,6 @@ __global__ __launch_bounds__(FI_BX * FI_BY) void frames_convert_kernel(const fx_
 }
 
 // ---- launcher ------------------------------------------------------------------------------------------------------------------------------
-static int fi_planes(int format) { return format == FX_FRAME_I420 ? 3 : (format == FX_FRAME_NV12 ? 2 : 1); }
-
-// bytes of one row of plane p
-static int fi_row_bytes(int format, int p, int W) {
-  if (format == FX_FRAME_RGB24 || format == FX_FRAME_BGR24) return 3 * W;
-  if (p == 0) return W;
-  return format == FX_FRAME_NV12 ? 2 * ((W + 1) / 2) : (W + 1) / 2;
-}
-
-// The host copy of the descriptors is what is checked (the device copy is what the kernels read).
-static bool fi_descs_ok(const fx_frame_desc* d, int B, int same_size, int Ho, int Wo) {
-  for (int b = 0; b < B; ++b) {
-    const fx_frame_desc& f = d[b];
-    if (f.format < FX_FRAME_RGB24 || f.format > FX_FRAME_I420 || f.matrix < FX_FRAME_BT601_LIMITED || f.matrix > FX_FRAME_BT709_FULL) return false;
-    if (f.height < 1 || f.width < 1 || f.height > FX_FRAME_MAX_DIM || f.width > FX_FRAME_MAX_DIM) return false;
-    if (same_size && (f.height != Ho || f.width != Wo)) return false;
-    for (int p = 0; p < fi_planes(f.format); ++p)
-      if (!f.plane[p] || f.pitch[p] < fi_row_bytes(f.format, p, f.width)) return false;
-  }
-  return true;
-}
-
 // Whether every frame of a same-size batch allows the 16-byte form: W % 16 == 0 and every plane base and pitch a multiple of its load width.
 static bool fi_vec_ok(const fx_frame_desc* d, int B, int Wo, const void* y) {
   if (Wo % FI_PX != 0 || ((uintptr_t)y & 15) != 0) return false;
@@ -337,5 +344,18 @@ extern "C" int fx_frames_tile_gather_f32(const fx_frame_desc* descs, const fx_fr
   if (Wo % 4 == 0 && ((uintptr_t)y & 15) == 0)
     hipLaunchKernelGGL(frames_tile_gather_kernel<true>, grid, block, 0, stream, descs, windows, V, y, Ho, Wo);
   else hipLaunchKernelGGL(frames_tile_gather_kernel<false>, grid, block, 0, stream, descs, windows, V, y, Ho, Wo);
+  return fx_launch_status();
+}
+
+extern "C" int fx_frames_roi_gather_f32(const fx_frame_desc* descs, const fx_frame_desc* descs_host, int S, const int32_t* roi_win, int K, float* y,
+                                        int Ho, int Wo, fx_stream_t stream_) {
+  FX_CHECK_ARG(descs && descs_host && roi_win && y && ((uintptr_t)descs & 7) == 0 && ((uintptr_t)roi_win & 3) == 0 && ((uintptr_t)y & 3) == 0);
+  FX_CHECK_ARG(S >= 1 && S <= FX_FRAME_MAX_BATCH && K >= 1 && (int64_t)S * K <= 65535 && Ho >= 1 && Wo >= 1 && Ho <= FX_FRAME_MAX_DIM &&
+               Wo <= FX_FRAME_MAX_DIM);
+  FX_CHECK_ARG(fi_descs_ok(descs_host, S, 0, 0, 0));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const dim3 grid((Wo + FI_BX * 4 - 1) / (FI_BX * 4), (Ho + FI_BY - 1) / FI_BY, S * K), block(FI_BX, FI_BY);
+  if (Wo % 4 == 0 && ((uintptr_t)y & 15) == 0) hipLaunchKernelGGL(frames_roi_gather_kernel<true>, grid, block, 0, stream, descs, roi_win, K, y, Ho, Wo);
+  else hipLaunchKernelGGL(frames_roi_gather_kernel<false>, grid, block, 0, stream, descs, roi_win, K, y, Ho, Wo);
   return fx_launch_status();
 }

@@ -283,7 +283,7 @@ class FocoosModel:
         return self.model.device
 
     def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate=False, tracker=None,
-                    mask_format: str = "png", zones=None, dwell=None, heatmap=None, tiling=None) -> List[FocoosDetections]:
+                    mask_format: str = "png", zones=None, dwell=None, heatmap=None, tiling=None, classify=None) -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
         reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``inputs`` may also be a
         ``frames.FrameBatch`` of NV12 / I420 / BGR / RGB video frames, host or device: the results are those of the same frames passed as
@@ -305,16 +305,31 @@ class FocoosModel:
         large frame of stream b (a ``FrameBatch``, or a list of ``Frame`` s and / or uint8 RGB arrays, all of one size) that is cut into
         windows, run through the engine in chunks and merged per stream on the device into one packed result in frame pixels, which the
         tracker, the zones, the heat map, the overlay and the detections then read as they read the engine's (tiled.py); fai_detr
-        only (NotImplementedError otherwise), mixed sizes or non-uint8 inputs raise ValueError, all before anything touches the GPU."""
+        only (NotImplementedError otherwise), mixed sizes or non-uint8 inputs raise ValueError, all before anything touches the GPU.
+        ``classify``: a ``cascade.DeviceCascade`` of ``len(inputs)`` streams - a second model on every detected object (cascade.py, DESIGN
+        25): after the tracker, at most ``Cascade.max_objects`` detections per stream are cropped from the resident frames on the device,
+        run through the cascade's fai_cls classifier and handed ``attr_id`` / ``attr_label`` / ``attr_conf``; a cascade built on a tracker
+        runs that tracker (``tracker`` must be None or that one) and remembers the attribute per track.  The inputs are uint8 frames (a
+        list of RGB arrays is wrapped into one ``FrameBatch``; sizes may differ without ``tiling``); everything else is that of
+        ``classify=None``.  A family without boxes raises NotImplementedError, anything but a DeviceCascade TypeError, a classifier on
+        another device or non-uint8 inputs ValueError, all before anything touches the GPU."""
         from .frames import as_frame_batch, drawable
         from .mask_rle import check_mask_format
 
         check_mask_format(mask_format, self.model.family, "infer_batch")
+        if classify is not None:
+            from . import cascade as CS
+
+            CS.check(self, classify, True, "infer_batch", device_only=True)
         if tiling is not None:
             from . import tiled as TL
 
             TL.check_tiling(self, tiling, "infer_batch")
             inputs = TL.stream_frames(inputs, "infer_batch")
+        if classify is not None:
+            inputs = CS.stream_frames(inputs, "infer_batch")
+            classify, tracker = CS.bind_tracker(classify, tracker or getattr(zones, "tracker", None), "infer_batch")
+            CS.for_batch(classify, len(inputs), tracker, self.model.device, "infer_batch")
         tracked = tracker is not None or getattr(zones, "tracker", None) is not None
         if heatmap is not None:
             from . import heat as HM
@@ -382,6 +397,8 @@ class FocoosModel:
                               heatmap if overlay.heat else None)
             if ovl.traces is not None:
                 ovl.traces.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
+        if classify is not None:     # select, crop, classify, attribute: four steps on the current stream, nothing comes back yet
+            classify.update(pl, inputs, ids, self.model_info.classes)
         if self.model.family == "fai_cls":
             out = self.processor.pack_detections(pl.logits.cpu(), self.model_info.classes, thr)   # the one D2H copy of the batch's logits
         elif self.model.family in ("fai_mf", "bisenetformer"):
@@ -393,6 +410,9 @@ class FocoosModel:
             warn_drops(tracker, "infer_batch")
         if zones is not None:
             Z.attach(out, zones.fetch() if dwell is None else dwell.fetch(zones.fetch()))
+        if classify is not None:
+            CS.attach(out, classify.fetch(), classify.cascade)
+            CS.warn_left(classify, "infer_batch")
         if tiling is not None:
             TL.warn_dropped(tiler.status, "infer_batch")
         t3 = perf_counter()
@@ -405,7 +425,7 @@ class FocoosModel:
         return out
 
     def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate=False, track=None,
-                     mask_format: str = "png", zones=None, detections: bool = True, dwell=None, heatmap=None, tiling=None):
+                     mask_format: str = "png", zones=None, detections: bool = True, dwell=None, heatmap=None, tiling=None, classify=None):
         """Throughput inference (round 6): iterate over ``batches`` (each a list of images of ONE common shape after preprocessing and one
         batch size) and yield each batch's ``List[FocoosDetections]`` in order, with up to ``depth`` batches in flight on the engine's
         pipeline (engine.pipeline(): batch i+1's backbone runs beside batch i's decoder tail; default depth 3).  Same results as
@@ -448,7 +468,21 @@ class FocoosModel:
         frame pixels.  Everything above then reads that result exactly as it reads the engine's: ``track``, ``zones``, ``dwell``,
         ``heatmap``, ``annotate`` (drawn on the full-size frames, which are resident), ``detections=False``.  fai_detr only
         (NotImplementedError before anything touches the GPU); frames of one batch that differ in size, or non-uint8 inputs, raise
-        ValueError; candidates dropped by the suppression cap warn once per call.  With ``None`` nothing changes."""
+        ValueError; candidates dropped by the suppression cap warn once per call.  With ``None`` nothing changes.
+        ``classify``: a ``cascade.Cascade`` or a ``cascade.DeviceCascade`` whose state then outlives the call - a second model on every
+        detected object, on the device (cascade.py).  Per batch, after the tracker: one launch picks at most
+        ``Cascade.max_objects`` detections per stream (the classes, sizes and scores the cascade asks for; tracks that were never
+        classified first, then the ones whose answer is oldest), one launch crops and resizes their padded boxes straight from the
+        resident frames (NV12 / I420 / BGR / RGB) to the classifier's input size, the cascade's fai_cls classifier runs on that buffer,
+        and one launch hands every detection its attribute and remembers it per track (``interval``: frames before a track is classified
+        again; ``hold``: "latest" or "best").  Three small arrays more come back with the packed copy; a detection whose
+        ``attr_conf`` = sigmoid(logit) exceeds ``Cascade.threshold`` carries ``attr_id`` / ``attr_label`` / ``attr_conf``.  The inputs are
+        uint8 frames: a list of RGB arrays or tensors is wrapped into one ``FrameBatch`` (one upload; sizes may differ per stream without
+        ``tiling``), with ``tiling`` the crops come from the tiler's resident full-size frames and the merged result.  The detections,
+        ids, zone dicts and drawn images are those of ``classify=None``.  A family without boxes raises NotImplementedError; anything but
+        a Cascade / DeviceCascade TypeError; a classifier on another device, non-uint8 inputs, ``detections=False``, ``interval > 1`` or
+        ``hold="best"`` without ``track``, or more than 65535 crops per batch ValueError - all before anything touches the GPU; eligible
+        objects left out for want of crop budget warn once per call.  With ``None`` nothing changes."""
         from collections import deque
 
         from . import zones as Z
@@ -461,6 +495,10 @@ class FocoosModel:
             from . import tiled as TL
 
             TL.check_tiling(self, tiling, "infer_stream")
+        if classify is not None:
+            from . import cascade as CS
+
+            CS.check(self, classify, detections, "infer_stream")
 
         from .annotate import OverlayPass, annotate_results, check_inputs, check_overlay, traces_for_batch
         from .tracking import TrackerConfig, attach_ids, for_batch, resolve, warn_drops
@@ -468,8 +506,12 @@ class FocoosModel:
         if annotate and self.model.family == "fai_cls":
             check_overlay(annotate, False, False, "fai_cls")
         track = resolve(track, self.model.family, self.model.device)
+        if classify is not None and track is None:
+            track = getattr(classify, "tracker", None)      # a DeviceCascade built on a tracker runs that tracker, for the zones too
         zones, track = Z.resolve(zones, track, self.model.family)
         dwell = Z.resolve_dwell(dwell, zones, track, self.model.family)
+        if classify is not None:
+            classify, track = CS.bind_tracker(classify, track, "infer_stream")
         if heatmap is not None:
             from . import heat as HM
 
@@ -481,13 +523,13 @@ class FocoosModel:
             yield from self._infer_stream_cls(batches, thr, depth, annotate)
             return
         mask_family = self.model.family in ("fai_mf", "bisenetformer")
-        pipe, pending, frames = None, deque(), {}
+        pipe, pending, frames, held = None, deque(), {}, {}
 
         def finish():
             ticket = pending.popleft()
-            return analyse(pipe.wait(ticket), pipe.B, frames.pop(ticket, None))
+            return analyse(pipe.wait(ticket), pipe.B, frames.pop(ticket, None), held.pop(ticket, None))
 
-        def analyse(pl, B, drawn):      # `pl`: a lane's plan, or with tiling the merged result, which has the same packed fields
+        def analyse(pl, B, drawn, fb=None):      # `pl`: a lane's plan, or with tiling the merged result, which has the same packed fields
             ids = None
             if track is not None:      # batches finish in order, so the frames reach the tracker in order
                 ids = track.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
@@ -499,6 +541,8 @@ class FocoosModel:
                 heatmap.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
             if traces is not None:     # the tail of every track, appended right after the tracker (and the zones)
                 traces.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
+            if classify is not None:   # select, crop, classify, attribute on the batch's own frames `fb`; nothing comes back yet
+                classify.update(pl, fb, ids, self.model_info.classes)
             if not detections:         # analytics only: no detection objects, no ids on the host
                 out = [FocoosDetections(detections=[]) for _ in range(B)]
             elif mask_family:
@@ -509,6 +553,8 @@ class FocoosModel:
                 attach_ids(out, ids.cpu().tolist())
             if zones is not None:
                 Z.attach(out, zones.fetch() if dwell is None else dwell.fetch(zones.fetch()))
+            if classify is not None:
+                CS.attach(out, classify.fetch(), classify.cascade)
             if annotate:      # the lane's results stay valid until the lane is submitted to again, which happens after this returns
                 ovl = None if overlay is None else OverlayPass(overlay, ids, zones if overlay.zones else None, traces,
                                                                heatmap if overlay.heat else None)
@@ -516,9 +562,13 @@ class FocoosModel:
             return out
 
         def prepare(inputs, B, device):      # the call's device state, created with the first batch, which fixes B
-            nonlocal track, zones, dwell, heatmap, traces
+            nonlocal track, zones, dwell, heatmap, traces, classify
+            if classify is not None:
+                CS.check_budget(classify, B, "infer_stream")      # before the tracker below loads the library
             if track is not None:
                 track = for_batch(track, B, device)
+            if classify is not None:
+                classify = CS.for_batch(classify, B, track, device)
             if zones is not None:
                 zones = Z.for_batch(zones, B, track, device)
             if dwell is not None:
@@ -533,9 +583,15 @@ class FocoosModel:
             yield from TL.infer_stream_tiled(self, batches, tiling, thr, depth, prepare, analyse, bool(annotate))
             if track is not None and not isinstance(track, TrackerConfig):
                 warn_drops(track)
+            if classify is not None:
+                CS.warn_left(classify)
             return
         for inputs in batches:
-            inputs = as_frame_batch(inputs) or inputs
+            if classify is not None:      # uint8 frames: the detector's preprocess and the crops read the same resident planes
+                inputs = CS.stream_frames(inputs, "infer_stream")
+                CS.check_budget(classify, len(inputs), "infer_stream")
+            else:
+                inputs = as_frame_batch(inputs) or inputs
             if annotate:
                 check_inputs(inputs, "infer_stream")
             images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
@@ -554,10 +610,14 @@ class FocoosModel:
             pending.append(pipe.submit(x, sizes, thr))
             if annotate:
                 frames[pending[-1]] = (drawable(inputs, x, x.device), x)      # the submitted batch stays referenced until it is drawn
+            if classify is not None:
+                held[pending[-1]] = inputs      # and so do the frames the crops are taken from, until the batch is analysed
         while pending:
             yield finish()
         if track is not None and not isinstance(track, TrackerConfig):
             warn_drops(track)
+        if classify is not None:
+            CS.warn_left(classify)
 
     def _infer_stream_cls(self, batches, thr: float, depth: Optional[int], annotate: bool = False):
         """infer_stream of the classifiers: a pipeline is reused only when (B, H, W, input dtype) all match - a uint8 batch and a resized

@@ -71,6 +71,12 @@ class FocoosDet:
     cls_id: Optional[int] = None
     label: Optional[str] = None
     mask: Optional[str] = None
+    # set by infer_stream(classify=...) / infer_batch(classify=...) (cascade.py) when attr_conf exceeds the cascade's threshold: the
+    # classifier's top class of the object's crop (or the one its track remembers), that class's name, and torch.sigmoid of its logit.
+    # Keyword-only, so the positional order of the fields around them is the one it always was.
+    attr_id: Optional[int] = field(default=None, kw_only=True)
+    attr_label: Optional[str] = field(default=None, kw_only=True)
+    attr_conf: Optional[float] = field(default=None, kw_only=True)
     keypoints: Optional[List[Tuple[int, int, float]]] = None
     # set by mask_format="polygon" (mask_polygon.py): every ring of the mask's boundary as a flat [x0, y0, x1, y1, ...] in frame pixels, holes too
     polygons: Optional[List[List[int]]] = None

@@ -369,7 +369,8 @@ def infer_stream_tiled(fm, batches, tiling: Tiling, thr: float, depth: Optional[
     for) before that lane is submitted to again; a frame batch is finished - merged, then ``analyse``d like an engine plan's result - once
     the next one has been submitted, so its chunks run while this one is merged and packed.  Two view buffers alternate: the gather of
     frame batch i + 2 overwrites what the chunks of batch i read, and batch i has been finished (every chunk waited for) by then.
-    ``prepare(fb, S, device)`` creates the per-call analytics state, ``analyse(result, S, drawn)`` is infer_stream's own tail."""
+    ``prepare(fb, S, device)`` creates the per-call analytics state (called before anything here loads the library),
+    ``analyse(result, S, drawn, fb)`` is infer_stream's own tail; ``fb`` are the batch's frames, which ``classify=`` crops from."""
     from collections import deque
 
     tl, pipe, T = None, None, 0      # the tiler loads the library: created once the first batch has passed the host checks
@@ -388,14 +389,14 @@ def infer_stream_tiled(fm, batches, tiling: Tiling, thr: float, depth: Optional[
             collect()
         res = tl.merge(rec["bufs"])
         drawn = (rec["fb"], tl.rgb(rec["fb"])) if annotate else None
-        return analyse(res, tl.S, drawn)
+        return analyse(res, tl.S, drawn, rec["fb"])
 
     for inputs in batches:
         fb = stream_frames(inputs, "infer_stream")
         S, (H, W) = len(fb), fb.sizes[0]
+        prepare(fb, S, fm.model.device)
         if tl is None:
             tl = StreamTiler(fm, tiling, 2)
-        prepare(fb, S, tl.dev)
         if tl.changed(S, H, W):
             while pending:
                 yield finish()

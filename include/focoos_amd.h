@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 25
+#define FX_ABI_VERSION 26
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -577,6 +577,58 @@ int fx_frames_ingest(const fx_frame_desc* descs, const fx_frame_desc* descs_host
  * both libraries. */
 int fx_frames_tile_gather_f32(const fx_frame_desc* descs, const fx_frame_desc* descs_host, int S, const int32_t* windows,
                               const int32_t* windows_host, int V, float* y, int Ho, int Wo, fx_stream_t stream);
+
+/* ---- A second model on every detected object (ABI 26; csrc/roi_ops.hip and csrc/frame_ops.hip):
+ * FocoosModel.infer_stream(classify=...).  Three entry points around the classifier engine: which detections are cropped, the crops, and what
+ * every detection and every track then knows.  No atomics, plain vector stores, contraction off; every output is a copy or an exact
+ * comparison (the sigmoid of a logit is the host's).  Null or misaligned pointers (det_boxes and roi_win 16, descs 8, everything else 4
+ * bytes) or anything else outside a contract: FX_ERR_INVALID_ARGUMENT, nothing launched, nothing written.  The same in both libraries.
+ *
+ * The packed result (det_scores, det_labels, det_boxes, det_count; [S][T]) and the tracker's track_ids i32 [S][T] / trk_id i32 [S][max_tracks]
+ * are those of fx_track_update; track_ids and trk_id may be null TOGETHER (no tracker: every detection is untracked).  The cascade state is
+ * caller-owned device memory, all zero at first: at_id, at_label, at_frame i32 [S][max_tracks], at_logit f32 [S][max_tracks], frame i32 [S].
+ * descs / descs_host = fx_frame_desc [S] as for fx_frames_ingest; sizes may differ per stream.  n = clamp(det_count[s], 0, T).
+ * The track slot t(j) of detection j is the lowest t with trk_id[s][t] == track_ids[s][j], when that id is >= 1 and such a t exists; the
+ * lowest j among those sharing the id OWNS the slot, every other detection counts as untracked.
+ *
+ * fx_roi_select, one launch, one workgroup per stream.  f = frame[s] + 1 (read, not written), (H, W) = the stream's descriptor.  For j < n:
+ *   each box coordinate is clamped to [0, 16384]; bw = x1 - x0, bh = y1 - y0; px = (bw * pad_q + 128) >> 8, py likewise;
+ *   the window is wx0 = max(0, x0 - px), wy0 = max(0, y0 - py), wx1 = min(W, x1 + px), wy1 = min(H, y1 + py), ww = wx1 - wx0, wh = wy1 - wy0;
+ *   staleness a(j) = INT32_MAX when j is untracked or at_id[s][t] != id, else f - at_frame[s][t];
+ *   j is ELIGIBLE iff its label's bit is set in class_words (u32 [n_words], bit l & 31 of word l >> 5; null = every label; a label outside
+ *   the words is not eligible), det_scores >= min_score (fp32), bw >= min_size and bh >= min_size, ww >= 1 and wh >= 1, a(j) >= interval.
+ * The eligible detections are ranked by a descending, then score descending (fp32 comparison), then j ascending; the detection of rank
+ * k < K writes roi_win[s][k] = (wx0, wy0, ww, wh) and roi_det[s][k] = j.  Rows from the count on are (0, 0, 0, 0) and -1;
+ * roi_count[s] = min(eligible, K), roi_left[s] = eligible - roi_count[s].  roi_win i32 [S][K][4], roi_det i32 [S][K], roi_count and roi_left
+ * i32 [S], every element written.  Limits: 1 <= S <= FX_TRACK_MAX_STREAMS, 1 <= T, max_tracks <= FX_TRACK_MAX_SLOTS, 1 <= K <= 64,
+ * 0 <= pad_q <= 256, min_size >= 1, interval >= 1, min_score not NaN, 1 <= n_words <= 256 when class_words is given; the descriptors are
+ * validated on the host copy as for fx_frames_ingest.
+ *
+ * fx_frames_roi_gather_f32, one launch: y = float32 [S * K][Ho][Wo][3] on the 0..255 scale.  roi_win is a DEVICE array the host never sees:
+ * the kernel clamps every window to its own frame before use - the origin into [0, W - 1] x [0, H - 1], the extent to min(extent, what is
+ * left of the frame from the clamped origin) - so no value in roi_win can index outside a plane.  A crop whose clamped window has an extent
+ * is, bit for bit, what fx_frames_tile_gather_f32 writes for that window of frame s alone (taps clamped to the window, chroma at the
+ * absolute position, conversion per tap before the filter); a crop without an extent is left untouched.  16-byte stores when Wo % 4 == 0
+ * and y is 16-byte aligned.  1 <= S, S * K <= 65535, 1 <= Ho, Wo <= 16384.
+ *
+ * fx_roi_attributes, one launch, one workgroup per stream, after the classifier; logits f32 [S * K][C].  f = ++frame[s].  The top class of
+ * crop k < clamp(roi_count[s], 0, K) is (l, v): starting from (0, -inf), class c replaces it when logits[c] > v, in ascending c - ties go to
+ * the lowest class, a NaN never wins, a row of NaNs gives (0, -inf).  With j = roi_det[s][k] (ignored outside 0 .. n - 1): if j owns a slot
+ * t, then when at_id != id the record (at_id, at_label, at_logit, at_frame) becomes (id, l, v, f); otherwise at_frame = f and
+ * (at_label, at_logit) = (l, v) always for hold 0 ("latest") or only when v >= at_logit for hold 1 ("best").  Then for each j < n: a
+ * detection that owns a slot whose record is valid (at_id == id) reports that record and attr_age = f - at_frame; an untracked detection
+ * cropped this frame reports (l, v) and age 0; every other j, and every j >= n, gets attr_label = -1, attr_logit = 0, attr_age = -1.
+ * attr_label i32, attr_logit f32, attr_age i32, each [S][T], every element written.  Limits as for fx_roi_select, C >= 1, hold in {0, 1}. */
+int fx_roi_select(const float* det_scores, const int32_t* det_labels, const int32_t* det_boxes, const int32_t* det_count, int S, int T,
+                  const int32_t* track_ids, const int32_t* trk_id, int max_tracks, const int32_t* at_id, const int32_t* at_frame,
+                  const int32_t* frame, const fx_frame_desc* descs, const fx_frame_desc* descs_host, const uint32_t* class_words, int n_words,
+                  int K, int pad_q, int min_size, float min_score, int interval, int32_t* roi_win, int32_t* roi_det, int32_t* roi_count,
+                  int32_t* roi_left, fx_stream_t stream);
+int fx_frames_roi_gather_f32(const fx_frame_desc* descs, const fx_frame_desc* descs_host, int S, const int32_t* roi_win, int K, float* y, int Ho,
+                             int Wo, fx_stream_t stream);
+int fx_roi_attributes(const float* logits, int C, const int32_t* roi_det, const int32_t* roi_count, int K, const int32_t* det_count, int S, int T,
+                      const int32_t* track_ids, const int32_t* trk_id, int max_tracks, int32_t* at_id, int32_t* at_label, float* at_logit,
+                      int32_t* at_frame, int32_t* frame, int hold, int32_t* attr_label, float* attr_logit, int32_t* attr_age, fx_stream_t stream);
 
 /* ---- Zones, lines, counts, track ids and traces drawn on device frames (ABI 23; csrc/overlay.hip):
  * FocoosModel.infer_stream(annotate=Overlay(...)).  Five entry points beside the two of ABI 17; every output byte is an integer function of the
