@@ -157,6 +157,8 @@ SIGNATURES = {
     "fx_heat_tiles": [_i, _i, _i],
     "fx_heat_update": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "fx_annotate_heat_u8": [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp],
+    "fx_redact_regions": [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "fx_redact_u8": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, C.c_int64, _i, _i, _i, _i, _i, _i, _vp],
     "fx_mask_rle_workspace_bytes": [_i, _i, _i, _i],
     "fx_mask_rle_encode": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "fx_mask_polygon_workspace_bytes": [_i, _i, _i, _i, _i],
@@ -336,7 +338,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 26  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 27  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:

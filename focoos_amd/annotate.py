@@ -12,7 +12,11 @@ what is already on the device when a lane finishes: "#17 " in front of a tracked
 ``DeviceZones`` tinted and outlined and its lines stroked, a tail of the last N anchors behind every track (``DeviceTraces``, ``fx_trace_update``;
 all three in one geometry pass, ``fx_annotate_overlay_u8``) and "door: 3" / "gate: 12/9" at every region (``fx_annotate_zone_records``, drawn by
 ``fx_annotate_u8``).  csrc/overlay.hip; tests/overlay_ref.py restates the contracts.  ``Overlay(heat=True)`` puts the call's heat map
-underneath all of it (heat.py, ``fx_annotate_heat_u8``).  ``annotate=True`` draws exactly what it always drew."""
+underneath all of it (heat.py, ``fx_annotate_heat_u8``).  ``Overlay(redact=Redact(...))`` makes the selected
+objects unreadable first, under every other layer: their boxes, and the predicted boxes of tracks the detector has just missed, are
+pixelated, blurred or filled from the packed results and the tracker's slots (``fx_redact_regions``, ``fx_redact_u8``, csrc/redact.hip,
+DESIGN.md section 26; tests/redact_ref.py restates the contracts), and ``draw=False`` leaves the boxes, masks and labels out.
+``annotate=True`` draws exactly what it always drew."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -29,6 +33,12 @@ FLAG_BOXES, FLAG_MASKS, FLAG_LABELS = 1, 2, 4
 RNAME = 16      # FX_OVL_RNAME: glyphs of a region name
 MAX_TRACE = 64  # FX_TRACE_MAX_LEN: points kept per track
 OVL_FILL, OVL_STROKE, OVL_TRACES = 1, 2, 4
+REDACT_MODES = {"pixelate": 0, "blur": 1, "fill": 2}      # FX_REDACT_PIXELATE / _BLUR / _FILL
+REDACT_SHAPES = {"box": 0, "ellipse": 1, "mask": 2}       # FX_REDACT_BOX / _ELLIPSE / _MASK
+REDACT_CELLS = (4, 8, 16, 32, 64)
+REDACT_MAX_RADIUS = 32    # FX_REDACT_MAX_RADIUS
+REDACT_MAX_HOLD = 1024    # FX_REDACT_MAX_HOLD
+MASK_FAMILIES = ("fai_mf", "bisenetformer")
 FOCOOS_PALETTE = ("#015fe6", "#3faebd", "#63dba6", "#a151ff", "#df923a")
 # ctypes-free mirror of fx_annotate_record (56 bytes)
 REC_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"), ("colour", "<u4"), ("nchar", "<i4"), ("glyph", "u1", (LMAX,))])
@@ -178,19 +188,122 @@ class DeviceTraces:
 
 
 @dataclass(frozen=True)
+class Redact:
+    """What ``Overlay(redact=...)`` makes unreadable before anything is drawn.  ``classes``: class names or ids,
+    None = every class (resolved against the model's classes when the call starts; an unknown name raises ValueError); ``mode``:
+    "pixelate" (the mean of the pixel's ``cell`` x ``cell`` cell, grid anchored at the frame origin), "blur" (the mean of the
+    (2 ``radius`` + 1)^2 window) or "fill" (``colour``, RGB); ``shape``: "box", "ellipse" (inscribed in the box) or "mask" (the
+    instance's own pixels, mask families only); ``pad``: the box grows by this fraction of its width and height on every side; ``top``:
+    only the upper fraction of the box is covered (a person detector then hides heads); ``hold``: also cover the predicted boxes of
+    tracks of the selected classes that have gone undetected for 1 .. ``hold`` frames (needs a tracker).  Validated at construction:
+    ValueError names the field."""
+    classes: Optional[Sequence[Union[str, int]]] = None
+    mode: str = "pixelate"
+    cell: int = 16
+    radius: int = 16
+    colour: Tuple[int, int, int] = (0, 0, 0)
+    shape: str = "box"
+    pad: float = 0.0
+    top: float = 1.0
+    hold: int = 0
+
+    def __post_init__(self):
+        def bad(name, why):
+            raise ValueError(f"Redact.{name} = {getattr(self, name)!r}: {why}")
+
+        def integer(v):
+            return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer))
+
+        c = self.classes
+        if c is not None:
+            if isinstance(c, (str, bytes)) or not isinstance(c, (list, tuple)) or not c:
+                bad("classes", "must be None or a non-empty list of class names or ids")
+            for v in c:
+                if not (isinstance(v, str) or (integer(v) and v >= 0)):
+                    bad("classes", "every entry must be a class name or an id >= 0")
+            object.__setattr__(self, "classes", tuple(v if isinstance(v, str) else int(v) for v in c))
+        if self.mode not in REDACT_MODES:
+            bad("mode", f"must be one of {', '.join(REDACT_MODES)}")
+        if not integer(self.cell) or self.cell not in REDACT_CELLS:
+            bad("cell", f"must be one of {', '.join(str(v) for v in REDACT_CELLS)}")
+        if not integer(self.radius) or not 1 <= self.radius <= REDACT_MAX_RADIUS:
+            bad("radius", f"must be an integer in 1..{REDACT_MAX_RADIUS}")
+        col = self.colour
+        if not isinstance(col, (list, tuple)) or len(col) != 3 or not all(integer(v) and 0 <= v <= 255 for v in col):
+            bad("colour", "must be three integers (R, G, B) in 0..255")
+        object.__setattr__(self, "colour", tuple(int(v) for v in col))
+        if self.shape not in REDACT_SHAPES:
+            bad("shape", f"must be one of {', '.join(REDACT_SHAPES)}")
+        for name, lo_open in (("pad", False), ("top", True)):
+            v = getattr(self, name)
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+                bad(name, "must be a finite number")
+            if not (0 < v <= 1 if lo_open else 0 <= v <= 1):
+                bad(name, "must be in (0, 1]" if lo_open else "must be in [0, 1]")
+        if not integer(self.hold) or not 0 <= self.hold <= REDACT_MAX_HOLD:
+            bad("hold", f"must be an integer in 0..{REDACT_MAX_HOLD}")
+
+    @property
+    def pad256(self) -> int:
+        """``pad`` as the kernel takes it: round(pad * 256), 0 .. 256."""
+        return int(round(float(self.pad) * 256))
+
+    @property
+    def top256(self) -> int:
+        """``top`` as the kernel takes it: max(1, round(top * 256)), 1 .. 256."""
+        return max(1, int(round(float(self.top) * 256)))
+
+    @property
+    def colour_word(self) -> int:
+        return self.colour[0] | (self.colour[1] << 8) | (self.colour[2] << 16)
+
+    def class_ids(self, classes: Sequence[str]) -> Optional[List[int]]:
+        """The ids of ``classes`` (the model's names) this object selects, None for every class; an unknown name or an id past the last
+        class raises ValueError and names it."""
+        if self.classes is None:
+            return None
+        names = [str(n) for n in classes or []]
+        ids = []
+        for v in self.classes:
+            if isinstance(v, str):
+                if v not in names:
+                    raise ValueError(f"Redact.classes: unknown class name {v!r} (the model has {len(names)} classes)")
+                ids.append(names.index(v))
+            else:
+                if v >= len(names):
+                    raise ValueError(f"Redact.classes: class id {v} is not in 0..{len(names) - 1}")
+                ids.append(v)
+        return sorted(set(ids))
+
+
+def class_words(ids: Sequence[int], K: int) -> np.ndarray:
+    """The class bitmap fx_redact_regions reads: uint32 [ceil(K / 32)], bit l & 31 of word l >> 5 set for every id l."""
+    w = np.zeros(max(1, (int(K) + 31) // 32), dtype=np.uint32)
+    for l in ids:
+        w[l >> 5] |= np.uint32(1 << (l & 31))
+    return w
+
+
+@dataclass(frozen=True)
 class Overlay:
     """What ``annotate=`` draws beyond ``True`` (boxes, masks, "name: NN%") in ``infer_stream`` / ``infer_batch``: ``ids`` - "#17 " in front
     of the label of a tracked detection; ``zones`` - the regions tinted and outlined, the lines stroked, "door: 3" / "gate: 12/9" at each
     region's first vertex; ``traces`` - the last N (0..64, 0 = off) anchors of every track joined into a tail, or a ``DeviceTraces`` whose
-    state then outlives the call; ``heat`` - the heat map of ``heatmap=`` blended in as the bottom layer (heat.py).  Validated at
-    construction: ValueError names the field."""
+    state then outlives the call; ``heat`` - the heat map of ``heatmap=`` blended in above the redaction and below the rest (heat.py);
+    ``redact`` - a ``Redact``: the selected objects are made unreadable first, under every other layer; ``draw`` - False leaves out the
+    box outlines, the mask tints and the "name: NN%" labels (``Overlay(ids=False, zones=False, redact=Redact(...), draw=False)`` is the
+    anonymised frame alone).  Validated at construction: ValueError names the field."""
     ids: bool = True
     zones: bool = True
     traces: Union[int, DeviceTraces] = 0
     heat: bool = False
+    redact: Optional[Redact] = None
+    draw: bool = True
 
     def __post_init__(self):
-        for f in ("ids", "zones", "heat"):
+        if self.redact is not None and not isinstance(self.redact, Redact):
+            raise ValueError(f"Overlay.redact = {self.redact!r}: must be None or a Redact")
+        for f in ("ids", "zones", "heat", "draw"):
             if not isinstance(getattr(self, f), (bool, np.bool_)):
                 raise ValueError(f"Overlay.{f} = {getattr(self, f)!r}: must be True or False")
         t = self.traces
@@ -202,8 +315,10 @@ class Overlay:
         return isinstance(self.traces, DeviceTraces) or self.traces > 0
 
 
-def check_overlay(annotate, tracked: bool, zoned: bool, family: str, what: str = "infer_stream", heated: bool = False) -> Optional[Overlay]:
-    """The Overlay of ``annotate=`` (None for True / False), refused on the host, by field, when the call has nothing to draw it from."""
+def check_overlay(annotate, tracked: bool, zoned: bool, family: str, what: str = "infer_stream", heated: bool = False,
+                  fm=None) -> Optional[Overlay]:
+    """The Overlay of ``annotate=`` (None for True / False), refused on the host, by field, when the call has nothing to draw it from.
+    ``fm``: the model, whose class names ``Overlay.redact.classes`` is resolved against."""
     if not isinstance(annotate, Overlay):
         return None
     if family == "fai_cls":
@@ -218,6 +333,16 @@ def check_overlay(annotate, tracked: bool, zoned: bool, family: str, what: str =
         raise ValueError(f"{what}: Overlay.heat = True needs heatmap= (there is no heat map to draw)")
     if what == "infer_batch" and annotate.traced and not isinstance(annotate.traces, DeviceTraces):
         raise ValueError(f"infer_batch: Overlay.traces = {annotate.traces!r} would start a new trace with every call: pass a DeviceTraces")
+    red = annotate.redact
+    if red is not None:
+        if red.hold > 0 and not tracked:
+            raise ValueError(f"{what}: Redact.hold = {red.hold} covers the predicted boxes of missed tracks: it needs a tracker (pass track= / "
+                             f"tracker=, or Redact(hold=0))")
+        if red.shape == "mask" and family not in MASK_FAMILIES:
+            raise NotImplementedError(f"{what}: Redact.shape = 'mask' covers an instance's own pixels; model family {family!r} packs no masks "
+                                      f"(supported: {', '.join(MASK_FAMILIES)})")
+        if fm is not None:
+            red.class_ids(fm.model_info.classes)      # an unknown name is a ValueError now, not at the first batch
     return annotate
 
 
@@ -245,6 +370,7 @@ class OverlayPass:
     zones: Optional[object] = None       # zones.DeviceZones, when Overlay.zones
     traces: Optional[DeviceTraces] = None
     heat: Optional[object] = None        # heat.DeviceHeatmap, when Overlay.heat
+    tracker: Optional[object] = None     # tracking.DeviceTracker, when Overlay.redact.hold > 0
 
 
 def region_name_table(names: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
@@ -280,6 +406,9 @@ class DeviceAnnotator:
         self.flags = TASK_FLAGS[task] | (FLAG_LABELS if labels else 0)
         self.gw = self.gh = 1
         self.atlas = self.names = self.name_len = None
+        self._redact_words: dict = {}     # Redact -> its class bitmap on the device (None: every class)
+        self._redact_regions: dict = {}   # (rows, R) -> regions, region_slot, region_count
+        self._redact_scratch: dict = {}   # frame shape -> the frame blur writes into
         if labels:
             atlas, self.gw, self.gh = glyph_atlas()
             tab, ln = name_table(self.classes)
@@ -404,22 +533,71 @@ class DeviceAnnotator:
                                               self._stream()), "fx_annotate_overlay_u8")
         return dst
 
+    def redact(self, frames: torch.Tensor, results, b0: int, red: Redact, tracker=None) -> torch.Tensor:
+        """Cover the selected objects of images b0 .. b0+B-1 of ``results`` on ``frames``: fx_redact_regions over every row of the results
+        (with ``tracker``, a DeviceTracker of as many streams, also its coasting slots), then fx_redact_u8 - in place for "fill" and
+        "pixelate", into the scratch frame of this frame shape for "blur".  Returns the frames that now hold the picture."""
+        from ._lib import check
+
+        self._check_frames(frames)
+        B, H, W, _ = frames.shape
+        rows, T = int(results.det_labels.shape[0]), int(results.det_labels.shape[1])
+        if red not in self._redact_words:      # the class bitmap goes up once per Redact
+            ids = red.class_ids(self.classes)
+            self._redact_words[red] = None if ids is None else torch.from_numpy(class_words(ids, len(self.classes)).view(np.int32)).to(self.device)
+        words = self._redact_words[red]
+        trk = [None] * 4 + [0]
+        if tracker is not None:
+            if tracker.streams != rows:
+                raise ValueError(f"redact: a tracker of {tracker.streams} streams for results of {rows} rows (batch index b is stream b)")
+            trk = [tracker.id.data_ptr(), tracker.label.data_ptr(), tracker.tsu.data_ptr(), tracker.box.data_ptr(), tracker.config.max_tracks]
+        R = T + trk[4]
+        if (rows, R) not in self._redact_regions:
+            i32 = dict(dtype=torch.int32, device=self.device)
+            self._redact_regions[(rows, R)] = (torch.zeros(rows, R, 4, **i32), torch.zeros(rows, R, **i32), torch.zeros(rows, **i32))
+        reg, slot, count = self._redact_regions[(rows, R)]
+        check(self.lib.fx_redact_regions(results.det_labels.data_ptr(), results.det_boxes.data_ptr(), results.det_count.data_ptr(), rows, T,
+                                         None if words is None else words.data_ptr(), len(self.classes) if words is not None else 0, *trk,
+                                         red.hold if tracker is not None else 0, red.pad256, red.top256, reg.data_ptr(), slot.data_ptr(),
+                                         count.data_ptr(), self._stream()), "fx_redact_regions")
+        mw, wpr, stride = None, 0, 0
+        if red.shape == "mask":
+            mw = results.mask_words
+            if tuple(mw.shape[1:3]) != (T, H) or not mw.is_contiguous():
+                raise ValueError(f"redact: mask planes {tuple(mw.shape)} do not match {T} slots of {H} rows")
+            wpr, stride = int(mw.shape[3]), int(mw.shape[2]) * int(mw.shape[3])
+        dst = frames
+        if red.mode == "blur":      # cannot run in place: one scratch frame per frame shape, the later layers draw there
+            key = tuple(frames.shape)
+            if key not in self._redact_scratch:
+                self._redact_scratch[key] = torch.empty_like(frames)
+            dst = self._redact_scratch[key]
+        check(self.lib.fx_redact_u8(frames.data_ptr(), dst.data_ptr(), B, H, W, int(b0), reg.data_ptr(), slot.data_ptr(), count.data_ptr(), R,
+                                    None if mw is None else mw.data_ptr(), wpr, stride, T, REDACT_MODES[red.mode], REDACT_SHAPES[red.shape],
+                                    red.cell, red.radius, red.colour_word, self._stream()), "fx_redact_u8")
+        return dst
+
     def annotate_overlay(self, frames: torch.Tensor, results, b0: int, ov: OverlayPass) -> torch.Tensor:
-        """``annotate()`` with the layers of an Overlay, in place, bottom to top: the heat map (its own pass), zone fills, zone outlines
-        and line strokes, traces (one geometry pass), the three layers of ``annotate()`` with the id in the label, the region count labels."""
+        """``annotate()`` with the layers of an Overlay, in place, bottom to top: the redaction (its own pass; "blur" moves the picture to
+        the scratch frame, where the rest is then drawn), the heat map (its own pass), zone fills, zone outlines and line strokes, traces
+        (one geometry pass), the three layers of ``annotate()`` with the id in the label (left out with ``draw=False``), the region
+        count labels."""
         self._check_frames(frames)
         B, H, W, _ = frames.shape
         s = scale_for(H, W)
+        if ov.overlay.redact is not None:
+            frames = self.redact(frames, results, b0, ov.overlay.redact, ov.tracker)
         if ov.heat is not None:
             ov.heat.render(frames, b0)
         geo = (OVL_FILL | OVL_STROKE if ov.zones is not None else 0) | (OVL_TRACES if ov.traces is not None else 0)
         if geo:
             self.geometry(frames, b0, ov.zones, ov.traces, geo)
         labels = bool(self.flags & FLAG_LABELS)
-        rec = None
-        if labels:
-            rec = self.records_tracked(results, ov.ids, b0, B, H, W, s) if ov.overlay.ids else self.records(results, b0, B, H, W, s)
-        self.draw(frames, results, rec, b0)
+        if ov.overlay.draw:
+            rec = None
+            if labels:
+                rec = self.records_tracked(results, ov.ids, b0, B, H, W, s) if ov.overlay.ids else self.records(results, b0, B, H, W, s)
+            self.draw(frames, results, rec, b0)
         if labels and ov.zones is not None:
             from ._lib import check
 

@@ -339,7 +339,7 @@ class FocoosModel:
         if annotate:
             from .annotate import check_overlay
 
-            overlay = check_overlay(annotate, tracked, zones is not None, self.model.family, "infer_batch", heatmap is not None)
+            overlay = check_overlay(annotate, tracked, zones is not None, self.model.family, "infer_batch", heatmap is not None, fm=self)
         inputs = as_frame_batch(inputs) or inputs      # a FrameBatch (or one Frame) goes where a list of images goes (frames.py)
         if dwell is not None:
             from . import zones as Z
@@ -394,7 +394,7 @@ class FocoosModel:
             from .annotate import OverlayPass, traces_for_batch
 
             ovl = OverlayPass(overlay, ids, zones if overlay.zones else None, traces_for_batch(overlay, tracker, "infer_batch"),
-                              heatmap if overlay.heat else None)
+                              heatmap if overlay.heat else None, tracker if overlay.redact is not None and overlay.redact.hold > 0 else None)
             if ovl.traces is not None:
                 ovl.traces.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
         if classify is not None:     # select, crop, classify, attribute: four steps on the current stream, nothing comes back yet
@@ -436,7 +436,11 @@ class FocoosModel:
         in the place of ``True`` also draws what ``track`` / ``zones`` know: "#17 " in front of a tracked label, the regions
         tinted and outlined with "door: 3" / "gate: 12/9", and a tail of the last ``traces`` anchors behind every track (one more launch
         after the zones'); a field that has nothing to draw from (ids or traces without ``track``, zones without ``zones``) raises
-        ValueError before anything touches the GPU, ``True`` draws exactly what it always drew.
+        ValueError before anything touches the GPU, ``True`` draws exactly what it always drew.  ``Overlay(redact=annotate.Redact(...))``
+        first makes the selected objects unreadable on the device (pixelate / blur / fill; box, ellipse or the instance's mask; with
+        ``hold`` also the predicted boxes of tracks the detector has just missed) and ``Overlay(draw=False)`` leaves out boxes, masks and
+        labels; ``Redact.hold`` without ``track``, ``shape="mask"`` on a family without masks or an unknown class name raise on
+        the host.
         ``track``: identity across frames on the device (tracking.py) - batch index b is stream b (camera b), consecutive batches
         are consecutive frames.  ``True`` (the defaults), a ``TrackerConfig``, or a ``DeviceTracker`` whose state then outlives the call.
         Each batch is one more launch after its lane finished (batches finish in order) and every tracked detection carries ``track_id``;
@@ -516,7 +520,8 @@ class FocoosModel:
             from . import heat as HM
 
             heatmap = HM.resolve(heatmap, track is not None, self.model.family)
-        overlay = check_overlay(annotate, track is not None, zones is not None, self.model.family, heated=heatmap is not None) if annotate else None
+        overlay = (check_overlay(annotate, track is not None, zones is not None, self.model.family, heated=heatmap is not None, fm=self)
+                   if annotate else None)
         traces = None
         thr = threshold or self.processor.threshold
         if self.model.family == "fai_cls":
@@ -557,7 +562,8 @@ class FocoosModel:
                 CS.attach(out, classify.fetch(), classify.cascade)
             if annotate:      # the lane's results stay valid until the lane is submitted to again, which happens after this returns
                 ovl = None if overlay is None else OverlayPass(overlay, ids, zones if overlay.zones else None, traces,
-                                                               heatmap if overlay.heat else None)
+                                                               heatmap if overlay.heat else None,
+                                                               track if overlay.redact is not None and overlay.redact.hold > 0 else None)
                 annotate_results(self, *drawn, pl, out, ovl)
             return out
 

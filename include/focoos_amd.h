@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 26
+#define FX_ABI_VERSION 27
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -763,6 +763,54 @@ int fx_heat_update(const int32_t* det_labels, const int32_t* det_boxes, const in
                    int32_t* heat_max, int32_t* part, fx_stream_t stream);
 int fx_annotate_heat_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int b0, int streams, const int32_t* heat, const int32_t* heat_max,
                         int cell, int full_scale, const uint32_t* lut, fx_stream_t stream);
+
+/* Redacting detected objects on uint8 frames (ABI 27; csrc/redact.hip): annotate=Overlay(redact=Redact(...)).  Every
+ * output byte is an integer function of the inputs; no float decides anything but clamp(rint(x), 0, 16384) (half to even, NaN = 0) of a
+ * tracker box, the tracker's own conversion.  No atomics, plain vector stores.  On FX_ERR_INVALID_ARGUMENT nothing is launched or written.
+ *
+ * fx_redact_regions: one launch, one workgroup per stream b < B, builds regions i32 [B][R][4] (x0, y0, x1, y1, inclusive), region_slot
+ * i32 [B][R] and region_count i32 [B]; R = T + max_tracks (R = T without a tracker: the four trk pointers null and max_tracks = 0, and
+ * then hold must be 0).  A label is SELECTED when class_words (device u32 [ceil(K / 32)], bit l & 31 of word l >> 5) is null, or when
+ * 0 <= l < K and its bit is set.  The list of a stream, compacted in this order: (1) the detection slots j < clamp(det_count[b], 0, T)
+ * with a selected label, ascending, region_slot = j; (2) with a tracker and hold > 0, the slots t < max_tracks with trk_id != 0,
+ * 0 < trk_tsu <= hold and a selected trk_label, ascending, region_slot = -1, their box = the four coordinates of trk_box f32 [B][M][4]
+ * converted as above (fx_track_update stores the predicted box of every unmatched live slot there).  A box is read with every coordinate
+ * clamped to [0, 16384]; one with x1 < x0 or y1 < y0 is skipped.  With w = x1 - x0 + 1 and h = y1 - y0 + 1: first
+ * h' = max(1, (h top256 + 128) >> 8) and y1 = y0 + h' - 1, then gx = (w pad256 + 128) >> 8, gy = (h' pad256 + 128) >> 8 and the box grows
+ * by gx on the left and the right and by gy above and below; it may leave the frame.  Entries at and past region_count[b] are zero.
+ * 1 <= B <= FX_TRACK_MAX_STREAMS, 1 <= T <= FX_TRACK_MAX_SLOTS, 1 <= max_tracks <= FX_TRACK_MAX_SLOTS with a tracker, 1 <= K <= 2^24 with a
+ * bitmap, 0 <= hold <= FX_REDACT_MAX_HOLD, 0 <= pad256 <= 256, 1 <= top256 <= 256; det_boxes, trk_box and regions 16-byte aligned, every other
+ * pointer 4-byte aligned.
+ *
+ * fx_redact_u8: dst [B][H][W][3] = src with the regions of stream b0 + b covered; region arrays as above with any 1 <= R <=
+ * FX_REDACT_MAX_REGIONS.  Pixel (x, y) is COVERED when for some k < clamp(region_count[b0 + b], 0, R) it lies in region k's box clipped to
+ * the frame (inclusive) and passes the shape test: FX_REDACT_BOX always; FX_REDACT_ELLIPSE, on the UNCLIPPED box's w and h, with
+ * u = 2 x + 1 - (x0 + x1 + 1) and v = 2 y + 1 - (y0 + y1 + 1): u u h h + v v w w <= w w h h in int64; FX_REDACT_MASK, for 0 <= region_slot
+ * < T, bit x & 31 of word mask_words[((b0 + b) T + slot) plane_stride_words + y words_per_row + (x >> 5)] (the layout fx_annotate_u8
+ * reads), for any other slot (a coasting region's -1) the box.  Why the ellipse's products fit: a box of fx_redact_regions has w, h <=
+ * 3 x 16385 < 2^16, and x0 + x1 and y0 + y1 are those of a box inside [0, 16384] (the growth is symmetric, the top cut keeps y0 + y1 in
+ * [0, 32768]), so |u|, |v| <= 32768 at a frame pixel: each product is at most 32768^2 x 49155^2 < 2^61.2, their sum < 2^62.2, and
+ * w w h h <= 49155^4 < 2^62.4.  Regions from elsewhere must keep to these bounds.  An uncovered pixel keeps src's bytes.  A covered pixel
+ * becomes, per channel and always from src: FX_REDACT_FILL - the byte of colour (R | G << 8 | B << 16); FX_REDACT_PIXELATE -
+ * (S + n div 2) div n, S the sum over the n pixels of its cell (x div cell, y div cell) that lie inside the frame (grid anchored at the
+ * frame origin); FX_REDACT_BLUR - (S + n div 2) div n over the window [x - radius, x + radius] x [y - radius, y + radius] clipped to the
+ * frame.  So overlapping regions give what their union gives and the order of the list never matters.  dst == src is allowed for fill and
+ * pixelate (a workgroup reads a tile of whole cells before it writes any of it) and refused for blur; otherwise the buffers must be
+ * disjoint.  A tile no region touches does no arithmetic: it stores nothing in place and is copied otherwise.  cell in {4, 8, 16, 32, 64}
+ * and 1 <= radius <= FX_REDACT_MAX_RADIUS and 0 <= colour <= 0xffffff are checked in every mode; mask_words (4-byte aligned, words_per_row
+ * >= ceil(W / 32), plane_stride_words >= H words_per_row) is read with FX_REDACT_MASK only.  1 <= B <= 65535, 0 <= b0 <= 2^24,
+ * 1 <= H, W <= 16384, 1 <= T <= FX_TRACK_MAX_SLOTS; regions 16-byte aligned, region_slot / region_count 4-byte aligned. */
+#define FX_REDACT_MAX_REGIONS 2048
+#define FX_REDACT_MAX_RADIUS 32
+#define FX_REDACT_MAX_HOLD 1024
+enum { FX_REDACT_PIXELATE = 0, FX_REDACT_BLUR = 1, FX_REDACT_FILL = 2 };
+enum { FX_REDACT_BOX = 0, FX_REDACT_ELLIPSE = 1, FX_REDACT_MASK = 2 };
+int fx_redact_regions(const int32_t* det_labels, const int32_t* det_boxes, const int32_t* det_count, int B, int T, const uint32_t* class_words,
+                      int K, const int32_t* trk_id, const int32_t* trk_label, const int32_t* trk_tsu, const float* trk_box, int max_tracks,
+                      int hold, int pad256, int top256, int32_t* regions, int32_t* region_slot, int32_t* region_count, fx_stream_t stream);
+int fx_redact_u8(const uint8_t* src, uint8_t* dst, int B, int H, int W, int b0, const int32_t* regions, const int32_t* region_slot,
+                 const int32_t* region_count, int R, const int32_t* mask_words, int words_per_row, int64_t plane_stride_words, int T, int mode,
+                 int shape, int cell, int radius, int colour, fx_stream_t stream);
 
 /* F.max_pool2d(k=3,s=2,p=1) (resnet.py:254) on NHWC bf16. */
 int fx_maxpool3x3s2_nhwc_bf16(const void* x, int ldx, void* y, int ldy, int B, int H, int W, int C, fx_stream_t stream);
