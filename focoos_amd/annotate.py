@@ -316,9 +316,10 @@ class Overlay:
 
 
 def check_overlay(annotate, tracked: bool, zoned: bool, family: str, what: str = "infer_stream", heated: bool = False,
-                  fm=None) -> Optional[Overlay]:
+                  fm=None, device_only: bool = False) -> Optional[Overlay]:
     """The Overlay of ``annotate=`` (None for True / False), refused on the host, by field, when the call has nothing to draw it from.
-    ``fm``: the model, whose class names ``Overlay.redact.classes`` is resolved against."""
+    ``fm``: the model, whose class names ``Overlay.redact.classes`` is resolved against.  ``device_only`` (infer_batch, one batch per
+    call): the traces must be a DeviceTraces."""
     if not isinstance(annotate, Overlay):
         return None
     if family == "fai_cls":
@@ -331,8 +332,8 @@ def check_overlay(annotate, tracked: bool, zoned: bool, family: str, what: str =
         raise ValueError(f"{what}: Overlay.zones = True needs zones= (or Overlay(zones=False))")
     if annotate.heat and not heated:
         raise ValueError(f"{what}: Overlay.heat = True needs heatmap= (there is no heat map to draw)")
-    if what == "infer_batch" and annotate.traced and not isinstance(annotate.traces, DeviceTraces):
-        raise ValueError(f"infer_batch: Overlay.traces = {annotate.traces!r} would start a new trace with every call: pass a DeviceTraces")
+    if device_only and annotate.traced and not isinstance(annotate.traces, DeviceTraces):
+        raise ValueError(f"{what}: Overlay.traces = {annotate.traces!r} would start a new trace with every call: pass a DeviceTraces")
     red = annotate.redact
     if red is not None:
         if red.hold > 0 and not tracked:

@@ -185,22 +185,9 @@ def stream_frames(inputs, what: str):
     """One batch of ``classify=`` inputs as a FrameBatch (sizes may differ per stream): a FrameBatch, a Frame, or a list of Frames and / or
     uint8 RGB arrays or tensors [H, W, 3], which are wrapped as RGB24 frames - the detector's preprocess and the crops then read the same
     resident planes.  ValueError for anything else; host only."""
-    from .frames import Frame, FrameBatch, as_frame_batch
+    from .frames import wrap_frames
 
-    fb = as_frame_batch(inputs)
-    if fb is not None:
-        return fb
-    if not isinstance(inputs, (list, tuple)) or not inputs:
-        raise ValueError(f"{what}(classify=) takes a FrameBatch or a non-empty list of Frames / uint8 RGB arrays, got {type(inputs).__name__}")
-    frames = []
-    for i, im in enumerate(inputs):
-        if not isinstance(im, Frame):
-            dt = getattr(im, "dtype", None)
-            if dt not in (np.uint8, torch.uint8):
-                raise ValueError(f"{what}(classify=) takes uint8 frames: input {i} is {dt if dt is not None else type(im).__name__}")
-            im = Frame.from_rgb(im)
-        frames.append(im)
-    return FrameBatch(frames)
+    return wrap_frames(inputs, f"{what}(classify=)")
 
 
 def for_batch(classify, S: int, track, device, what: str = "infer_stream") -> "DeviceCascade":
@@ -373,4 +360,4 @@ def warn_left(classify, what: str = "infer_stream") -> None:
     if isinstance(classify, DeviceCascade) and classify.left_seen:
         n, classify.left_seen = classify.left_seen, 0
         warnings.warn(f"{what}(classify=): {n} eligible objects were not classified in their frame: every one of Cascade.max_objects = "
-                      f"{classify.cascade.max_objects} crops of their stream was taken (raise max_objects or interval)", RuntimeWarning, stacklevel=3)
+                      f"{classify.cascade.max_objects} crops of their stream was taken (raise max_objects or interval)", RuntimeWarning, stacklevel=4)

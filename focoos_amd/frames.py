@@ -304,6 +304,25 @@ def as_frame_batch(inputs) -> Optional[FrameBatch]:
     return None
 
 
+def wrap_frames(inputs, what: str) -> FrameBatch:
+    """One batch of uint8 frames as a FrameBatch: a FrameBatch, a Frame, or a list of Frames and / or uint8 RGB arrays or tensors [H, W, 3],
+    which are wrapped as RGB24 frames.  ValueError, with ``what`` (entry point and argument) in front, for anything else; host only."""
+    fb = as_frame_batch(inputs)
+    if fb is not None:
+        return fb
+    if not isinstance(inputs, (list, tuple)) or not inputs:
+        raise ValueError(f"{what} takes a FrameBatch or a non-empty list of Frames / uint8 RGB arrays, got {type(inputs).__name__}")
+    frames = []
+    for i, im in enumerate(inputs):
+        if not isinstance(im, Frame):
+            dt = getattr(im, "dtype", None)
+            if dt not in (np.uint8, torch.uint8):
+                raise ValueError(f"{what} takes uint8 frames: input {i} is {dt if dt is not None else type(im).__name__}")
+            im = Frame.from_rgb(im)
+        frames.append(im)
+    return FrameBatch(frames)
+
+
 def refuse_frames(inputs, what: str) -> None:
     """ValueError naming ``what`` for an entry point that does not take frames.  Host only."""
     if isinstance(inputs, (Frame, FrameBatch)):

@@ -216,14 +216,14 @@ class DeviceHeatmap:
         return dict(heat=self.heat.cpu().numpy().copy(), heat_max=self.heat_max.cpu().numpy().copy())
 
 
-def resolve(heatmap, tracked: bool, family: str, what: str = "infer_stream"):
-    """What ``heatmap=`` means, decided on the host before anything touches the GPU: None -> None; a Heatmap (infer_stream: the
-    DeviceHeatmap is created with the first batch) or a DeviceHeatmap, whose ``tracked_only`` needs a tracker."""
+def resolve(heatmap, tracked: bool, family: str, what: str = "infer_stream", device_only: bool = False):
+    """What ``heatmap=`` means, decided on the host before anything touches the GPU: None -> None; a Heatmap (not with ``device_only``,
+    which is infer_batch: the DeviceHeatmap is created with the first batch) or a DeviceHeatmap, whose ``tracked_only`` needs a tracker."""
     if heatmap is None:
         return None
     check_family(family, what)
-    if not isinstance(heatmap, DeviceHeatmap if what == "infer_batch" else (Heatmap, DeviceHeatmap)):
-        raise TypeError(f"{what}: heatmap must be a " + ("DeviceHeatmap" if what == "infer_batch" else "Heatmap or a DeviceHeatmap") +
+    if not isinstance(heatmap, DeviceHeatmap if device_only else (Heatmap, DeviceHeatmap)):
+        raise TypeError(f"{what}: heatmap must be a " + ("DeviceHeatmap" if device_only else "Heatmap or a DeviceHeatmap") +
                         f", not {type(heatmap).__name__}")
     cfg = heatmap.config if isinstance(heatmap, DeviceHeatmap) else heatmap
     if cfg.tracked_only and not tracked:

@@ -313,112 +313,36 @@ class FocoosModel:
         list of RGB arrays is wrapped into one ``FrameBatch``; sizes may differ without ``tiling``); everything else is that of
         ``classify=None``.  A family without boxes raises NotImplementedError, anything but a DeviceCascade TypeError, a classifier on
         another device or non-uint8 inputs ValueError, all before anything touches the GPU."""
-        from .frames import as_frame_batch, drawable
-        from .mask_rle import check_mask_format
+        from .analytics import StreamAnalytics, batch_size
+        from .frames import drawable
 
-        check_mask_format(mask_format, self.model.family, "infer_batch")
-        if classify is not None:
-            from . import cascade as CS
-
-            CS.check(self, classify, True, "infer_batch", device_only=True)
-        if tiling is not None:
+        an = StreamAnalytics.resolve(self, "infer_batch", device_only=True, track=tracker, zones=zones, dwell=dwell, heatmap=heatmap,
+                                     annotate=annotate, classify=classify, tiling=tiling, detections=True, mask_format=mask_format,
+                                     threshold=threshold)
+        inputs = an.frames(inputs)      # a FrameBatch (or one Frame) goes where a list of images goes (frames.py, DESIGN 21)
+        an.prepare(inputs, batch_size(inputs))
+        t0 = perf_counter()
+        if tiling is not None:       # the views of every frame in one launch, the chunks on one plan, one merge: `pl` is the merged result
             from . import tiled as TL
 
-            TL.check_tiling(self, tiling, "infer_batch")
-            inputs = TL.stream_frames(inputs, "infer_batch")
-        if classify is not None:
-            inputs = CS.stream_frames(inputs, "infer_batch")
-            classify, tracker = CS.bind_tracker(classify, tracker or getattr(zones, "tracker", None), "infer_batch")
-            CS.for_batch(classify, len(inputs), tracker, self.model.device, "infer_batch")
-        tracked = tracker is not None or getattr(zones, "tracker", None) is not None
-        if heatmap is not None:
-            from . import heat as HM
-
-            heatmap = HM.resolve(heatmap, tracked, self.model.family, "infer_batch")
-        overlay = None
-        if annotate:
-            from .annotate import check_overlay
-
-            overlay = check_overlay(annotate, tracked, zones is not None, self.model.family, "infer_batch", heatmap is not None, fm=self)
-        inputs = as_frame_batch(inputs) or inputs      # a FrameBatch (or one Frame) goes where a list of images goes (frames.py, DESIGN 21)
-        if dwell is not None:
-            from . import zones as Z
-
-            dwell = Z.resolve_dwell(dwell, zones, tracker, self.model.family, "infer_batch")
-        if heatmap is not None:
-            HM.for_batch(heatmap, len(inputs), self.model.device, "infer_batch")
-            HM.check_sizes(heatmap, self.processor.get_image_sizes(inputs), "infer_batch")
-        if zones is not None:
-            from . import zones as Z
-
-            if not isinstance(zones, Z.DeviceZones):
-                Z.check_family(self.model.family, "infer_batch")
-                raise TypeError(f"infer_batch: zones must be a DeviceZones, not {type(zones).__name__}")
-            zones, tracker = Z.resolve(zones, tracker, self.model.family, "infer_batch")
-            Z.for_batch(zones, len(inputs), tracker, self.model.device, "infer_batch")
-        if annotate:
-            from .annotate import annotate_results, check_inputs
-
-            check_inputs(inputs)
-        if tracker is not None:
-            from .tracking import DeviceTracker, attach_ids, check_family, for_batch, warn_drops
-
-            check_family(self.model.family, "infer_batch")
-            if not isinstance(tracker, DeviceTracker):
-                raise TypeError(f"infer_batch: tracker must be a DeviceTracker, not {type(tracker).__name__}")
-            for_batch(tracker, len(inputs), self.model.device, "infer_batch")
-        t0 = perf_counter()
-        thr = threshold or self.processor.threshold
-        if tiling is not None:       # the views of every frame in one launch, the chunks on one plan, one merge: `pl` is the merged result
             t1 = t0
-            pl, tiler = TL.infer_batch_tiled(self, inputs, tiling, thr)
+            pl, tiler = TL.infer_batch_tiled(self, inputs, tiling, an.thr)
             images = tiler.rgb(inputs) if annotate else None      # the full-size frames, already resident, are what is drawn on
         else:
             images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
             t1 = perf_counter()
             sizes = torch.tensor(self.processor.get_image_sizes(inputs), dtype=torch.int32)
-            pl = self.model.detect(images, sizes=sizes, threshold=thr)
+            pl = self.model.detect(images, sizes=sizes, threshold=an.thr)
         torch.cuda.current_stream(self.model.device).synchronize()
         t2 = perf_counter()
-        ids = None
-        if tracker is not None:      # one launch on the packed device results; the ids come back beside the packed copy
-            ids = tracker.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
-        if zones is not None:        # one more launch, right after the tracker's
-            zv = zones.update(pl.det_labels, pl.det_boxes, pl.det_count, ids if zones.tracker is not None else None)
-            if dwell is not None:    # and the dwell times, from the masks the zones just wrote
-                dwell.update(pl.det_count, ids, zv["det_inside"])
-        if heatmap is not None:
-            heatmap.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
-        ovl = None
-        if overlay is not None:      # the traces' launch, then everything the drawing will read
-            from .annotate import OverlayPass, traces_for_batch
-
-            ovl = OverlayPass(overlay, ids, zones if overlay.zones else None, traces_for_batch(overlay, tracker, "infer_batch"),
-                              heatmap if overlay.heat else None, tracker if overlay.redact is not None and overlay.redact.hold > 0 else None)
-            if ovl.traces is not None:
-                ovl.traces.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
-        if classify is not None:     # select, crop, classify, attribute: four steps on the current stream, nothing comes back yet
-            classify.update(pl, inputs, ids, self.model_info.classes)
-        if self.model.family == "fai_cls":
-            out = self.processor.pack_detections(pl.logits.cpu(), self.model_info.classes, thr)   # the one D2H copy of the batch's logits
-        elif self.model.family in ("fai_mf", "bisenetformer"):
-            out = self.processor.pack_detections(pl, self.model_info.classes, mask_format=mask_format)
-        else:
-            out = self.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, self.model_info.classes)
-        if ids is not None:
-            attach_ids(out, ids.cpu().tolist())
-            warn_drops(tracker, "infer_batch")
-        if zones is not None:
-            Z.attach(out, zones.fetch() if dwell is None else dwell.fetch(zones.fetch()))
-        if classify is not None:
-            CS.attach(out, classify.fetch(), classify.cascade)
-            CS.warn_left(classify, "infer_batch")
+        out = an.analyse(pl, batch_size(inputs), inputs)
         if tiling is not None:
             TL.warn_dropped(tiler.status, "infer_batch")
         t3 = perf_counter()
         if annotate:
-            annotate_results(self, drawable(inputs, images, self.model.device), images, pl, out, ovl)
+            an.draw((drawable(inputs, images, self.model.device), images), pl, out)
         t4 = perf_counter()
+        an.close()
         for o in out:
             o.latency = InferLatency(preprocess=round(t1 - t0, 3), inference=round(t2 - t1, 3), postprocess=round(t3 - t2, 3),
                                      annotate=round(t4 - t3, 3) if annotate else None)
@@ -488,180 +412,57 @@ class FocoosModel:
         ``hold="best"`` without ``track``, or more than 65535 crops per batch ValueError - all before anything touches the GPU; eligible
         objects left out for want of crop budget warn once per call.  With ``None`` nothing changes."""
         from collections import deque
+        from types import SimpleNamespace
 
-        from . import zones as Z
-        from .frames import as_frame_batch, drawable
-        from .mask_rle import check_mask_format
+        from .analytics import StreamAnalytics, batch_size
+        from .frames import drawable
 
-        Z.check_detections_flag(detections, zones, annotate, mask_format)
-        check_mask_format(mask_format, self.model.family, "infer_stream")
-        if tiling is not None:
+        an = StreamAnalytics.resolve(self, "infer_stream", device_only=False, track=track, zones=zones, dwell=dwell, heatmap=heatmap,
+                                     annotate=annotate, classify=classify, tiling=tiling, detections=detections, mask_format=mask_format,
+                                     threshold=threshold)
+        if tiling is not None:      # the same tail on the merged result of every frame batch, in the tiler's own loop (tiled.py)
             from . import tiled as TL
 
-            TL.check_tiling(self, tiling, "infer_stream")
-        if classify is not None:
-            from . import cascade as CS
-
-            CS.check(self, classify, detections, "infer_stream")
-
-        from .annotate import OverlayPass, annotate_results, check_inputs, check_overlay, traces_for_batch
-        from .tracking import TrackerConfig, attach_ids, for_batch, resolve, warn_drops
-
-        if annotate and self.model.family == "fai_cls":
-            check_overlay(annotate, False, False, "fai_cls")
-        track = resolve(track, self.model.family, self.model.device)
-        if classify is not None and track is None:
-            track = getattr(classify, "tracker", None)      # a DeviceCascade built on a tracker runs that tracker, for the zones too
-        zones, track = Z.resolve(zones, track, self.model.family)
-        dwell = Z.resolve_dwell(dwell, zones, track, self.model.family)
-        if classify is not None:
-            classify, track = CS.bind_tracker(classify, track, "infer_stream")
-        if heatmap is not None:
-            from . import heat as HM
-
-            heatmap = HM.resolve(heatmap, track is not None, self.model.family)
-        overlay = (check_overlay(annotate, track is not None, zones is not None, self.model.family, heated=heatmap is not None, fm=self)
-                   if annotate else None)
-        traces = None
-        thr = threshold or self.processor.threshold
-        if self.model.family == "fai_cls":
-            yield from self._infer_stream_cls(batches, thr, depth, annotate)
+            yield from TL.infer_stream_tiled(self, batches, tiling, an.thr, depth, an)
+            an.close()
             return
-        mask_family = self.model.family in ("fai_mf", "bisenetformer")
-        pipe, pending, frames, held = None, deque(), {}, {}
-
-        def finish():
-            ticket = pending.popleft()
-            return analyse(pipe.wait(ticket), pipe.B, frames.pop(ticket, None), held.pop(ticket, None))
-
-        def analyse(pl, B, drawn, fb=None):      # `pl`: a lane's plan, or with tiling the merged result, which has the same packed fields
-            ids = None
-            if track is not None:      # batches finish in order, so the frames reach the tracker in order
-                ids = track.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
-            if zones is not None:      # one more launch, right after the tracker's, on the same packed results
-                zv = zones.update(pl.det_labels, pl.det_boxes, pl.det_count, ids if zones.tracker is not None else None)
-                if dwell is not None:  # and the dwell times, from the masks the zones just wrote
-                    dwell.update(pl.det_count, ids, zv["det_inside"])
-            if heatmap is not None:    # this frame's anchors onto the grid; nothing comes back
-                heatmap.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
-            if traces is not None:     # the tail of every track, appended right after the tracker (and the zones)
-                traces.update(pl.det_labels, pl.det_boxes, pl.det_count, ids)
-            if classify is not None:   # select, crop, classify, attribute on the batch's own frames `fb`; nothing comes back yet
-                classify.update(pl, fb, ids, self.model_info.classes)
-            if not detections:         # analytics only: no detection objects, no ids on the host
-                out = [FocoosDetections(detections=[]) for _ in range(B)]
-            elif mask_family:
-                out = self.processor.pack_detections(pl, self.model_info.classes, mask_format=mask_format)
-            else:
-                out = self.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, self.model_info.classes)
-            if ids is not None and detections:
-                attach_ids(out, ids.cpu().tolist())
-            if zones is not None:
-                Z.attach(out, zones.fetch() if dwell is None else dwell.fetch(zones.fetch()))
-            if classify is not None:
-                CS.attach(out, classify.fetch(), classify.cascade)
-            if annotate:      # the lane's results stay valid until the lane is submitted to again, which happens after this returns
-                ovl = None if overlay is None else OverlayPass(overlay, ids, zones if overlay.zones else None, traces,
-                                                               heatmap if overlay.heat else None,
-                                                               track if overlay.redact is not None and overlay.redact.hold > 0 else None)
-                annotate_results(self, *drawn, pl, out, ovl)
-            return out
-
-        def prepare(inputs, B, device):      # the call's device state, created with the first batch, which fixes B
-            nonlocal track, zones, dwell, heatmap, traces, classify
-            if classify is not None:
-                CS.check_budget(classify, B, "infer_stream")      # before the tracker below loads the library
-            if track is not None:
-                track = for_batch(track, B, device)
-            if classify is not None:
-                classify = CS.for_batch(classify, B, track, device)
-            if zones is not None:
-                zones = Z.for_batch(zones, B, track, device)
-            if dwell is not None:
-                dwell = Z.dwell_for_batch(dwell, zones)      # created on the call's DeviceZones with the first batch
-            if heatmap is not None:
-                HM.check_sizes(heatmap, self.processor.get_image_sizes(inputs))
-                heatmap = HM.for_batch(heatmap, B, device)
-            if overlay is not None and overlay.traced and traces is None:
-                traces = traces_for_batch(overlay, track)      # created with the first batch, like the tracker it follows
-
-        if tiling is not None:      # the same tail (`analyse`) on the merged result of every frame batch (tiled.py)
-            yield from TL.infer_stream_tiled(self, batches, tiling, thr, depth, prepare, analyse, bool(annotate))
-            if track is not None and not isinstance(track, TrackerConfig):
-                warn_drops(track)
-            if classify is not None:
-                CS.warn_left(classify)
-            return
-        for inputs in batches:
-            if classify is not None:      # uint8 frames: the detector's preprocess and the crops read the same resident planes
-                inputs = CS.stream_frames(inputs, "infer_stream")
-                CS.check_budget(classify, len(inputs), "infer_stream")
-            else:
-                inputs = as_frame_batch(inputs) or inputs
-            if annotate:
-                check_inputs(inputs, "infer_stream")
-            images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
-            x = self.model._to_nhwc(images)
-            sizes = torch.tensor(self.processor.get_image_sizes(inputs), dtype=torch.int32, device=x.device)
-            B, H, W, _ = x.shape
-            prepare(inputs, B, x.device)
-            if pipe is None or (pipe.B, pipe.H, pipe.W) != (B, H, W):
-                while pending:
-                    yield finish()
-                eng = self.model.engine
-                pipe = (eng.pipeline(B, H, W, depth, x.dtype == torch.float32, 1, False) if mask_family
-                        else eng.pipeline(B, H, W, depth, x.dtype == torch.float32))
-            if len(pending) >= pipe.depth:      # the lane about to be reused still holds an unread result
-                yield finish()
-            pending.append(pipe.submit(x, sizes, thr))
-            if annotate:
-                frames[pending[-1]] = (drawable(inputs, x, x.device), x)      # the submitted batch stays referenced until it is drawn
-            if classify is not None:
-                held[pending[-1]] = inputs      # and so do the frames the crops are taken from, until the batch is analysed
-        while pending:
-            yield finish()
-        if track is not None and not isinstance(track, TrackerConfig):
-            warn_drops(track)
-        if classify is not None:
-            CS.warn_left(classify)
-
-    def _infer_stream_cls(self, batches, thr: float, depth: Optional[int], annotate: bool = False):
-        """infer_stream of the classifiers: a pipeline is reused only when (B, H, W, input dtype) all match - a uint8 batch and a resized
-        float32 batch of one shape run on different plans (the input buffer's dtype is part of the plan).  Each lane's logits are copied
-        into a pinned host buffer on the lane's stream; the sigmoid / threshold run on them on the host."""
-        from collections import deque
-
+        fam = self.model.family
+        # one record per ticket in flight: what the batch's tail reads stays referenced until the ticket is finished - the frames the
+        # crops are taken from (`classify`), what is drawn on (`annotate`), the pinned host buffer a classifier lane copies its logits into
         pipe, key, pending = None, None, deque()
 
-        from .annotate import annotate_results, check_inputs
-        from .frames import as_frame_batch, drawable
-
         def finish():
-            ticket, host, drawn = pending.popleft()
-            pipe.wait(ticket)
-            out = self.processor.pack_detections(host["logits"], self.model_info.classes, thr)
-            if drawn is not None:
-                annotate_results(self, *drawn, None, out)
+            t = pending.popleft()
+            pl = pipe.wait(t.ticket)
+            out = an.analyse(pl, pipe.B, t.frames, None if t.host is None else t.host["logits"])
+            if t.drawn is not None:
+                an.draw(t.drawn, pl, out)
             return out
 
         for inputs in batches:
-            inputs = as_frame_batch(inputs) or inputs
-            if annotate:
-                check_inputs(inputs, "infer_stream")
+            inputs = an.frames(inputs)
+            an.prepare(inputs, batch_size(inputs))
             images, _ = self.processor.preprocess(inputs, device=self.model.device, dtype=self.model.dtype)
             x = self.model._to_nhwc(images)
             B, H, W, _ = x.shape
-            k = (B, H, W, x.dtype)
-            if pipe is None or key != k:
+            if key != (B, H, W, x.dtype):      # the input buffer's dtype is part of a plan: uint8 and resized float32 batches never share one
                 while pending:
                     yield finish()
-                pipe, key = self.model.engine.pipeline(B, H, W, depth, x.dtype == torch.float32), k
+                eng, f32 = self.model.engine, x.dtype == torch.float32
+                pipe = eng.pipeline(B, H, W, depth, f32, 1, False) if fam in ("fai_mf", "bisenetformer") else eng.pipeline(B, H, W, depth, f32)
+                key = (B, H, W, x.dtype)
             if len(pending) >= pipe.depth:      # the lane about to be reused still holds an unread result
                 yield finish()
-            host = {"logits": torch.empty(B, self.model.num_classes, dtype=torch.float32, pin_memory=True)}
-            pending.append((pipe.submit(x, None, thr, host), host, (drawable(inputs, x, x.device), x) if annotate else None))
+            sizes = host = None
+            if fam == "fai_cls":      # the lane copies its logits into pinned host memory on its own stream; sigmoid / threshold run on the host
+                host = {"logits": torch.empty(B, self.model.num_classes, dtype=torch.float32, pin_memory=True)}
+            else:
+                sizes = torch.tensor(self.processor.get_image_sizes(inputs), dtype=torch.int32, device=x.device)
+            pending.append(SimpleNamespace(ticket=pipe.submit(x, sizes, an.thr, host), host=host, frames=inputs if classify is not None else None,
+                                           drawn=(drawable(inputs, x, x.device), x) if annotate else None))
         while pending:
             yield finish()
+        an.close()
 
     def __call__(self, inputs, **kwargs) -> FocoosDetections:
         from .frames import as_frame_batch

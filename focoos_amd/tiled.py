@@ -199,21 +199,9 @@ def check_tiling(fm, tiling, what: str) -> None:
 def stream_frames(inputs, what: str):
     """One batch of ``tiling=`` inputs as a FrameBatch of ONE (H, W): a FrameBatch, a Frame, or a list of Frames and / or uint8 RGB arrays
     or tensors [H, W, 3] (wrapped as RGB24 frames).  ValueError for anything else; host only."""
-    from .frames import Frame, FrameBatch, as_frame_batch
+    from .frames import wrap_frames
 
-    fb = as_frame_batch(inputs)
-    if fb is None:
-        if not isinstance(inputs, (list, tuple)) or not inputs:
-            raise ValueError(f"{what}(tiling=) takes a FrameBatch or a non-empty list of Frames / uint8 RGB arrays, got {type(inputs).__name__}")
-        frames = []
-        for i, im in enumerate(inputs):
-            if not isinstance(im, Frame):
-                dt = getattr(im, "dtype", None)
-                if dt not in (np.uint8, torch.uint8):
-                    raise ValueError(f"{what}(tiling=) takes uint8 frames: input {i} is {dt if dt is not None else type(im).__name__}")
-                im = Frame.from_rgb(im)
-            frames.append(im)
-        fb = FrameBatch(frames)
+    fb = wrap_frames(inputs, f"{what}(tiling=)")
     sizes = fb.sizes
     for i, s in enumerate(sizes):
         if s != sizes[0]:
@@ -363,14 +351,15 @@ def infer_batch_tiled(fm, fb, tiling: Tiling, thr: float):
     return tl.merge(detect_views(fm.model, views, tl.sizes, tl.bs, thr)), tl
 
 
-def infer_stream_tiled(fm, batches, tiling: Tiling, thr: float, depth: Optional[int], prepare, analyse, annotate):
+def infer_stream_tiled(fm, batches, tiling: Tiling, thr: float, depth: Optional[int], an):
     """The loop of ``infer_stream(tiling=)``.  Every chunk of every frame batch is one submit on ONE engine pipeline of (batch_size, th, tw);
     a lane's packed results are copied out device to device (after ``wait``, on the current stream, which the lane's next submit waits
     for) before that lane is submitted to again; a frame batch is finished - merged, then ``analyse``d like an engine plan's result - once
     the next one has been submitted, so its chunks run while this one is merged and packed.  Two view buffers alternate: the gather of
     frame batch i + 2 overwrites what the chunks of batch i read, and batch i has been finished (every chunk waited for) by then.
-    ``prepare(fb, S, device)`` creates the per-call analytics state (called before anything here loads the library),
-    ``analyse(result, S, drawn, fb)`` is infer_stream's own tail; ``fb`` are the batch's frames, which ``classify=`` crops from."""
+    ``an``: the call's ``analytics.StreamAnalytics`` - ``an.prepare(fb, S)`` checks the batch and creates the per-call state
+    (called before anything here loads the library), ``an.analyse(result, S, fb)`` and ``an.draw`` are the tail every entry point runs;
+    ``fb`` are the batch's frames, which ``classify=`` crops from."""
     from collections import deque
 
     tl, pipe, T = None, None, 0      # the tiler loads the library: created once the first batch has passed the host checks
@@ -388,13 +377,16 @@ def infer_stream_tiled(fm, batches, tiling: Tiling, thr: float, depth: Optional[
         while outstanding and outstanding[0][1] is rec:
             collect()
         res = tl.merge(rec["bufs"])
-        drawn = (rec["fb"], tl.rgb(rec["fb"])) if annotate else None
-        return analyse(res, tl.S, drawn, rec["fb"])
+        drawn = (rec["fb"], tl.rgb(rec["fb"])) if an.annotate else None
+        out = an.analyse(res, tl.S, rec["fb"])
+        if drawn is not None:
+            an.draw(drawn, res, out)
+        return out
 
     for inputs in batches:
-        fb = stream_frames(inputs, "infer_stream")
+        fb = an.frames(inputs)
         S, (H, W) = len(fb), fb.sizes[0]
-        prepare(fb, S, fm.model.device)
+        an.prepare(fb, S)
         if tl is None:
             tl = StreamTiler(fm, tiling, 2)
         if tl.changed(S, H, W):

@@ -155,12 +155,15 @@ class DeviceTracker:
         return {k: src[k].cpu().numpy().copy() for k in self.STATE}
 
 
-def resolve(track, family: str, device, what: str = "infer_stream"):
+def resolve(track, family: str, device, what: str = "infer_stream", device_only: bool = False):
     """What ``track=`` of infer_stream means: None / False -> no tracking; True / a TrackerConfig -> a tracker created with the first
-    batch (returned as the config until then); a DeviceTracker -> itself, its state outlives the call."""
+    batch (returned as the config until then); a DeviceTracker -> itself, its state outlives the call.  ``device_only``
+    (``tracker=`` of infer_batch, which sees one batch per call): a DeviceTracker or nothing."""
     if track is None or track is False:
         return None
     check_family(family, what)
+    if device_only and not isinstance(track, DeviceTracker):
+        raise TypeError(f"{what}: tracker must be a DeviceTracker, not {type(track).__name__}")
     if track is True:
         return TrackerConfig()
     if isinstance(track, (TrackerConfig, DeviceTracker)):
@@ -193,4 +196,4 @@ def warn_drops(tracker: Optional[DeviceTracker], what: str = "infer_stream") -> 
     st = tracker.status()
     if st.any():
         warnings.warn(f"{what}: {int(st.sum())} new tracks dropped on {int((st != 0).sum())} of {tracker.streams} streams: every one of "
-                      f"max_tracks = {tracker.config.max_tracks} slots was taken (raise TrackerConfig.max_tracks)", RuntimeWarning, stacklevel=3)
+                      f"max_tracks = {tracker.config.max_tracks} slots was taken (raise TrackerConfig.max_tracks)", RuntimeWarning, stacklevel=4)

@@ -475,9 +475,10 @@ class DeviceDwell:
         return {k: src[k].cpu().numpy().copy() for k in self.STATE}
 
 
-def resolve_dwell(dwell, zones, track, family: str, what: str = "infer_stream"):
+def resolve_dwell(dwell, zones, track, family: str, what: str = "infer_stream", device_only: bool = False):
     """What ``dwell=`` means, decided on the host before anything touches the GPU (after ``resolve``): None / False -> None; True, a list of
-    Zone names or a DeviceDwell need ``zones=`` and a tracker.  Returns None, the DeviceDwell, or (names, None) to build with the first batch."""
+    Zone names or a DeviceDwell need ``zones=`` and a tracker.  Returns None, the DeviceDwell, or (names, None) to build with the first batch.
+    ``device_only`` (infer_batch): a DeviceDwell or nothing."""
     if dwell is None or dwell is False:
         return None
     check_family(family, what)
@@ -487,17 +488,12 @@ def resolve_dwell(dwell, zones, track, family: str, what: str = "infer_stream"):
         if dwell.zones is not zones:
             raise ValueError(f"{what}: dwell: the DeviceDwell was built for another DeviceZones: pass that one as zones=")
         return dwell
-    if what == "infer_batch":
-        raise TypeError(f"infer_batch: dwell must be a DeviceDwell, not {type(dwell).__name__}")
+    if device_only:
+        raise TypeError(f"{what}: dwell must be a DeviceDwell, not {type(dwell).__name__}")
     if track is None or (isinstance(zones, DeviceZones) and zones.tracker is None):
         raise ValueError(f"{what}: dwell= needs track= (dwell times belong to tracks; a DeviceZones passed as zones= must be built on a tracker)")
     regions = zones.regions if isinstance(zones, DeviceZones) else zones
     return check_dwell_names(regions, None if dwell is True else dwell, f"{what}: dwell"), None
-
-
-def dwell_for_batch(dwell, zones: DeviceZones) -> DeviceDwell:
-    """The DeviceDwell of a call: created on the call's DeviceZones with the first batch from the validated names."""
-    return dwell if isinstance(dwell, DeviceDwell) else DeviceDwell(zones, dwell[0])
 
 
 def check_detections_flag(detections: bool, zones, annotate: bool, mask_format: str, what: str = "infer_stream") -> None:
@@ -512,13 +508,16 @@ def check_detections_flag(detections: bool, zones, annotate: bool, mask_format: 
         raise ValueError(f"{what}: detections=False cannot be combined with mask_format={mask_format!r} (no masks are returned)")
 
 
-def resolve(zones, track, family: str, what: str = "infer_stream"):
+def resolve(zones, track, family: str, what: str = "infer_stream", device_only: bool = False):
     """What ``zones=`` means, decided on the host before anything touches the GPU: returns (zones, track).  None -> no zones; a list of
     Zone / Line -> validated, the DeviceZones is created with the first batch (a Line without ``track`` is a ValueError); a DeviceZones ->
-    itself, and its tracker is the one that runs (``track`` must be None or that tracker)."""
+    itself, and its tracker is the one that runs (``track`` must be None or that tracker).  ``device_only`` (infer_batch): a DeviceZones
+    or nothing."""
     if zones is None:
         return None, track
     check_family(family, what)
+    if device_only and not isinstance(zones, DeviceZones):
+        raise TypeError(f"{what}: zones must be a DeviceZones, not {type(zones).__name__}")
     if isinstance(zones, DeviceZones):
         if zones.tracker is not None:
             if track is not None and track is not zones.tracker:

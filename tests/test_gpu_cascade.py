@@ -594,3 +594,45 @@ def test_the_budget_warning_is_issued_once_per_call(models):
     with pytest.warns(RuntimeWarning, match="max_objects") as rec:
         list(det.infer_stream(iter(batches), threshold=THR, classify=CS.Cascade(cls, max_objects=1, min_size=1)))
     assert len([w for w in rec if "max_objects" in str(w.message)]) == 1
+
+
+def test_infer_stream_and_infer_batch_run_one_analytics_tail(models):
+    """Everything at once (analytics.py): tracker, a zone and a line, dwell times, heat map, traces, cascade and an
+    overlay with redaction.  ``infer_stream`` on one set of device objects equals three ``infer_batch`` calls on a second, fresh set
+    exactly: both run the same kernels on the same inputs, so no margin is needed."""
+    from focoos_amd.annotate import DeviceTraces, Overlay, Redact
+    from focoos_amd.heat import DeviceHeatmap, Heatmap
+    from focoos_amd.tracking import DeviceTracker
+    from focoos_amd.zones import DeviceDwell, DeviceZones, Line, Zone
+
+    det, cls = models
+    batches, rgbs = _frame_batches()
+    regions = [Zone("yard", [(20, 20), (240, 20), (240, 180), (20, 180)]), Line("gate", (130, 0), (130, 199))]
+
+    def device_objects():
+        trk = DeviceTracker(2, _tracker_config(), DEV)
+        zon = DeviceZones(2, regions, trk, DEV)
+        ov = Overlay(traces=DeviceTraces(trk, 8), heat=True, redact=Redact(hold=1))
+        return trk, dict(zones=zon, dwell=DeviceDwell(zon), heatmap=DeviceHeatmap(2, Heatmap(EH, EW), DEV),
+                         classify=CS.DeviceCascade(_cascade(cls), 2, trk, DEV), annotate=ov)
+
+    def facts(results):
+        return [[(_dets(r), r.zones, _attrs(r)) for r in g] for g in results], [[r.image for r in g] for g in results]
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)      # the crop budget overflows on purpose
+        trk, kw = device_objects()
+        with pytest.warns(RuntimeWarning, match=r"infer_batch\(classify=\).*max_objects") as rec:      # close() warns from this entry point too
+            first = det.infer_batch(batches[0], threshold=THR, tracker=trk, **kw)
+        left = [w for w in rec if "max_objects" in str(w.message)]
+        assert len(left) == 1 and left[0].filename == __file__      # once per call, attributed to the caller of infer_batch
+        want, want_images = facts([first] + [det.infer_batch(inputs, threshold=THR, tracker=trk, **kw) for inputs in batches[1:]])
+        # the infer_batch side has work in it: identity carried across frames, a count, an attribute, pixels changed
+        assert any(d[4] is not None for g in want[1:] for dets, _, _ in g for d in dets)
+        assert any(z["count"] > 0 for g in want for _, zd, _ in g for z in zd.values())
+        assert any(a[0] is not None for g in want for _, _, attrs in g for a in attrs)
+        assert all(im.shape == (EH, EW, 3) and not np.array_equal(im, rgb) for g, r in zip(want_images, rgbs) for im, rgb in zip(g, r))
+        trk, kw = device_objects()
+        got, got_images = facts(list(det.infer_stream(iter(batches), threshold=THR, track=trk, **kw)))
+    assert got == want
+    assert all(np.array_equal(a, b) for g, w in zip(got_images, want_images) for a, b in zip(g, w)) and len(got_images) == 3
