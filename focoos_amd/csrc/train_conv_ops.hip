@@ -23,7 +23,10 @@ __global__ __launch_bounds__(256) void pack_conv_weights_kernel(const float* __r
     r /= KH;
     int c = (int)(r % C);
     int n = (int)(r / C);
-    const float v = w[i] * (scale ? scale[n] : 1.0f);
+    float v = w[i] * (scale ? scale[n] : 1.0f);
+    // the image holds the fp32 product rounded once to the element type, as the host packers and fx_publish_weights_f32 produce it: left to
+    // the compiler, the fp16 build fuses the multiply with the conversion (v_fma_mixlo_f16) and rounds the exact product instead
+    asm volatile("" : "+v"(v));
     const bf16_t b = f32_to_bf16(v);
     if (w_fwd) w_fwd[(((int64_t)n * KH + kh) * KW + kw) * C + c] = b;
     if (w_dgrad) w_dgrad[(((int64_t)c * KH + (KH - 1 - kh)) * KW + (KW - 1 - kw)) * N + n] = b;
@@ -152,7 +155,11 @@ __global__ __launch_bounds__(256) void pack_weights_many_kernel(const fx_pack_en
   for (int r = 0; r < nn; ++r) {
     const float sc = e.scale ? e.scale[n0 + r] : 1.0f;
     const float* __restrict__ src = e.w + ((int64_t)(n0 + r) * C + c0) * T;
-    for (int i = threadIdx.x; i < cw * T; i += 256) tile[r][i] = f32_to_bf16(src[i] * sc);
+    for (int i = threadIdx.x; i < cw * T; i += 256) {
+      float p = src[i] * sc;
+      asm volatile("" : "+v"(p));   // the fp32 product, then ONE rounding to the element type (see pack_conv_weights_kernel)
+      tile[r][i] = f32_to_bf16(p);
+    }
   }
   if (e.bias_out && c0 == 0 && (int)threadIdx.x < nn) e.bias_out[ng0 + threadIdx.x] = e.bias[n0 + threadIdx.x];
   __syncthreads();

@@ -1229,7 +1229,8 @@ int fx_conv2d_wgrad_bias_nhwc_bf16(const void* x, int ldx, const void* dz, int l
  * w_dgrad [Cpad][KH][KW][N] = flipped + transposed filter: for a stride-1 "same" conv, dX = fx_conv2d_nhwc_bf16(dZ, w_dgrad).
  * Either output may be NULL; padding rows are not touched (zero them once).  w_fwd_frag / w_dgrad_frag (optional; need the matching
  * image, N % 32 == 0 resp. C % 32 == 0): second copies in MFMA fragment order - fx_conv_desc.w_frag of the forward / input-gradient
- * convolution, which routes eligible layers to the halo / pointwise kernels of conv3x3_flat.hip. */
+ * convolution, which routes eligible layers to the halo / pointwise kernels of conv3x3_flat.hip.  An image element is the fp32
+ * product w * scale[n] rounded once (nearest-even) to the element type, in both libraries and in fx_pack_weights_many_f32 alike. */
 int fx_pack_conv_weights_f32(const float* w, const float* scale, void* w_fwd, void* w_dgrad, void* w_fwd_frag, void* w_dgrad_frag, int N, int C,
                              int KH, int KW, fx_stream_t stream);
 

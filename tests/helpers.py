@@ -159,6 +159,14 @@ def gemm_ref64(x, w, bias=None, act=None, residual=None):
     return act64(y, act), mag
 
 
+def frag_order(W2: torch.Tensor) -> torch.Tensor:
+    """[N,K] -> MFMA fragment order [N/32][K/16][64][8] (include/focoos_amd.h, fx_conv_desc.w_frag): lane l of fragment (nb, ks) holds
+    W2[nb*32 + l%32][ks*16 + (l/32)*8 .. +8].  Same dtype, contiguous."""
+    N, K = W2.shape
+    assert N % 32 == 0 and K % 16 == 0
+    return W2.reshape(N // 32, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous().reshape(N // 32, K // 16, 64, 8)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Guarded device buffers and the per-element gate of the kernels' direct tests (tests/test_gpu_train_token_ops.py,
 # tests/test_gpu_infer_token_ops.py, tests/test_gpu_train_matrix_ops.py, tests/test_gpu_seg_head_ops.py).  The element type is an

@@ -16,7 +16,7 @@ from focoos_amd import _lib  # noqa: E402
 from focoos_amd._lib import FX_ACT, FxConvDesc, check  # noqa: E402
 from oracle import detr_oracle as O  # noqa: E402
 from tests._cases import MSDA_SHAPES, msda_case_inputs  # noqa: E402
-from tests.helpers import assert_ulp_gate, conv_ref64, gemm_ref64, load_golden  # noqa: E402
+from tests.helpers import assert_ulp_gate, conv_ref64, frag_order, gemm_ref64, load_golden  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -501,9 +501,7 @@ def test_library_exports_and_device(lib):
 # fx_pw_chain_bf16: branch2c (+ shortcut conv as second K segment) + residual + ReLU -> next branch2a + ReLU in one launch
 def frag_pack(W2):
     """[N,K] -> MFMA fragment order [N/32][K/16][64][8] (include/focoos_amd.h, fx_pw_chain_desc)."""
-    N, K = W2.shape
-    w = W2.float().reshape(N // 32, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
-    return to_dev(w.reshape(N // 32, K // 16, 64, 8), torch.bfloat16)
+    return to_dev(frag_order(W2.float()), torch.bfloat16)
 
 
 PW_CHAIN_CASES = [
