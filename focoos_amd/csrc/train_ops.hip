@@ -433,7 +433,9 @@ extern "C" int fx_msda_train_bwd(const void* value, int value_bf16, int ldv, con
   FX_CHECK_ARG(value && spatial_shapes && level_start && loc && attn && grad_out && grad_value && grad_loc && grad_attn);
   FX_CHECK_ARG(B > 0 && S > 0 && Q > 0 && L > 0 && P > 0);
   if (M != 8) return FX_ERR_UNSUPPORTED;
-  FX_CHECK_ARG(ldv >= M * 32 && ldg >= M * 32 && (!zero_grad_value || ldg == M * 32));
+  // the value operand is the forward's: the same stride and alignment contract, although this kernel gathers single elements
+  FX_CHECK_ARG(ldv >= M * 32 && ldv % 4 == 0 && ((uintptr_t)value % (value_bf16 ? 8 : 16)) == 0);
+  FX_CHECK_ARG(ldg >= M * 32 && (!zero_grad_value || ldg == M * 32));
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (zero_grad_value && hipMemsetAsync(grad_value, 0, (size_t)B * S * M * 32 * sizeof(float), stream) != hipSuccess) return FX_ERR_RUNTIME;
   static const int split_on = fx_tune("FX_MSDA_BWD_LEVEL_SPLIT", 1);

@@ -1154,7 +1154,10 @@ int fx_msda_f32_bwd(const float* value, const int32_t* spatial_shapes, const int
 /* The same pair with a typed, strided value operand (the training graph: the six decoder layers share one value projection whose
  * bf16 output [B,S,6*M*32] each layer reads as a column slice - no fp32 copy - and whose fp32 gradient they accumulate into column
  * slices of one buffer): value fp32 or bf16 (value_bf16), row stride ldv elements; grad_value fp32, row stride ldg, zeroed by the call
- * only when zero_grad_value != 0 (then ldg must be M*32). */
+ * only when zero_grad_value != 0 (then ldg must be M*32); with zero_grad_value == 0 the gradient is ADDED to what the slice holds.
+ * M must be 8 (else FX_ERR_UNSUPPORTED).  ldv >= M*32 and ldv % 4 == 0, value 16-byte (fp32) / 8-byte (bf16) aligned - for the backward
+ * too, which reads the forward's operand - ldg >= M*32, no NULL pointer; otherwise FX_ERR_INVALID_ARGUMENT, nothing launched or written.
+ * Sampling follows grid_sample(bilinear, zeros padding, align_corners=False): ix = loc_x * W - 0.5, pixels outside the map count as 0. */
 int fx_msda_train_fwd(const void* value, int value_bf16, int ldv, const int32_t* spatial_shapes, const int32_t* level_start, int L, int P,
                       const float* loc, const float* attn, float* out, int B, int S, int Q, int M, fx_stream_t stream);
 int fx_msda_train_bwd(const void* value, int value_bf16, int ldv, const int32_t* spatial_shapes, const int32_t* level_start, int L, int P,
