@@ -1,5 +1,5 @@
 """What the device mask encoders share on the host (``mask_format="rle"``, mask_rle.py; ``mask_format="polygon"``,
-mask_polygon.py, section 19): the bit words of a mask as a bool array, and ``PooledMaskEncoder``, the buffers, checks and copy back of an
+mask_polygon.py, section 19; ``mask_format="png_device"``, mask_png.py, section 28): the bit words of a mask as a bool array, and ``PooledMaskEncoder``, the buffers, checks and copy back of an
 encoder that leaves per slot a stream of int32 in a pool per image.  What a stream means is the subclass's."""
 from __future__ import annotations
 
@@ -28,9 +28,10 @@ class PooledMaskEncoder:
     A subclass gives ``CALL`` (the library pair ``CALL_workspace_bytes(B, Q, H, W, *sizes[1:])`` / ``CALL_encode(words, det_count,
     det_boxes, B, Q, H, W, *sizes, len, off, pool, workspace, bytes, stream)``), ``SIZES`` (the names of what its constructor takes after
     ``device``; they become attributes), ``sizes`` (their values, defaults filled in), ``LIMITS`` (the kernel's shape limits, for the
-    error), ``_det_counts``, ``_decode`` (a stored stream), ``_encode_words`` (the host fallback) and ``_warning``."""
+    error), ``_det_counts``, ``_decode`` (a stored stream), ``_encode_words`` (the host fallback) and ``_warning``.  An encoder whose
+    streams depend on the slot's box sets ``FALLBACK_BOX`` and gives ``_encode_slot(words, box)`` instead of ``_encode_words``."""
 
-    CALL, SIZES, LIMITS = "", ("capacity",), ""
+    CALL, SIZES, LIMITS, FALLBACK_BOX = "", ("capacity",), "", False
 
     def __init__(self, B: int, Q: int, H: int, W: int, device, *sizes):
         import torch
@@ -106,14 +107,19 @@ class PooledMaskEncoder:
         for b in range(self.B):
             n = int(count[b])      # detections are the leading slots
             lost = np.flatnonzero(~stored[b, :n] & (ln[b, :n] != 0))      # did not fit (the pool, or length -1: the encoder's own workspace)
-            words = {}
+            words, boxes = {}, {}
             if len(lost):      # the same result from the slots' bit words, on the host (one copy per image)
-                w = self._res.mask_words[b, :n][torch.from_numpy(lost).to(self.device)].cpu().numpy()
+                at = torch.from_numpy(lost).to(self.device)
+                w = self._res.mask_words[b, :n][at].cpu().numpy()
                 self.last_d2h_bytes += w.nbytes
                 words = dict(zip(lost.tolist(), w))
+                if self.FALLBACK_BOX:
+                    bx = self._res.det_boxes[b, :n][at].cpu().numpy()
+                    self.last_d2h_bytes += bx.nbytes
+                    boxes = dict(zip(lost.tolist(), bx))
                 fell += len(lost)
             # a slot that is neither stored nor lost has length 0: the empty stream
-            out.append([self._encode_words(words[j]) if j in words else self._decode(pool[b, off[b, j]:off[b, j] + max(ln[b, j], 0)])
+            out.append([self._encode_slot(words[j], boxes.get(j)) if j in words else self._decode(pool[b, off[b, j]:off[b, j] + max(ln[b, j], 0)])
                         for j in range(n)])
         self.last_fallback = fell
         self.total_fallback += fell
@@ -121,6 +127,10 @@ class PooledMaskEncoder:
         if fell:
             warnings.warn(self._warning(fell, masks), RuntimeWarning, stacklevel=3)
         return out
+
+
+    def _encode_slot(self, words, box):
+        return self._encode_words(words)
 
 
 def encoder_for(cls, current, res, *sizes):

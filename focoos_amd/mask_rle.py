@@ -14,20 +14,22 @@ import numpy as np
 
 from .mask_pool import PooledMaskEncoder, unpack_words
 
-MASK_FORMATS = ("png", "rle", "polygon", "none")
+MASK_FORMATS = ("png", "rle", "polygon", "png_device", "none")
+DEVICE_MASK_FORMATS = ("rle", "polygon", "png_device")      # encoded from the mask families' packed device results
 MASK_FAMILIES = ("fai_mf", "bisenetformer")
 
 
 def check_mask_format(mask_format, family: Optional[str] = None, what: str = "infer") -> str:
     """The ``mask_format`` keyword of the inference surface: "png" (the reference's base64 PNG, the default), "rle" (``FocoosDet.rle``),
-    "polygon" (``FocoosDet.polygons``, mask_polygon.py) or "none" (boxes, scores and labels only).  ValueError for anything else, the
-    compressed "coco_string" by name; NotImplementedError, by name, for "rle" or "polygon" on a family without masks.  Host only: nothing is loaded or launched."""
+    "polygon" (``FocoosDet.polygons``, mask_polygon.py), "png_device" (the base64 PNG again, encoded on the device: mask_png.py) or "none"
+    (boxes, scores and labels only).  ValueError for anything else, the compressed "coco_string" by name; NotImplementedError, by name, for
+    "rle", "polygon" or "png_device" on a family without masks.  Host only: nothing is loaded or launched."""
     if mask_format == "coco_string":
         raise ValueError(f"{what}: mask_format='coco_string' (maskApi's compressed RLE string) is not built: its codec cannot be checked "
                          "against pycocotools here, which is why detection_eval does not decode it either; use 'rle' (uncompressed counts)")
     if not isinstance(mask_format, str) or mask_format not in MASK_FORMATS:
         raise ValueError(f"{what}: mask_format = {mask_format!r} must be one of {', '.join(repr(f) for f in MASK_FORMATS)}")
-    if mask_format in ("rle", "polygon") and family is not None and family not in MASK_FAMILIES:
+    if mask_format in DEVICE_MASK_FORMATS and family is not None and family not in MASK_FAMILIES:
         raise NotImplementedError(f"{what}: mask_format={mask_format!r} needs masks; model family {family!r} has none "
                                   f"(supported: {', '.join(MASK_FAMILIES)})")
     return mask_format

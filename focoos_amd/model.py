@@ -295,8 +295,10 @@ class FocoosModel:
         detections themselves are those of ``tracker=None``).  ``mask_format``: how the mask families hand out their masks - "png" (the
         reference's base64 PNG in ``FocoosDet.mask``, the default), "rle" (``FocoosDet.rle``: the full-frame uncompressed COCO RLE, encoded on
         the device, ``mask`` is None; mask_rle.py), "polygon" (``FocoosDet.polygons``: every ring of the mask's boundary, holes too,
-        traced on the device, ``mask`` and ``rle`` are None; mask_polygon.py) or "none" (boxes, scores and labels only); anything
-        else raises ValueError, "rle" or "polygon" on a family without masks NotImplementedError.  ``annotate`` and ``tracker`` read the
+        traced on the device, ``mask`` and ``rle`` are None; mask_polygon.py), "png_device" (``FocoosDet.mask`` again: a base64 PNG that
+        decodes to the same image as "png"'s, filtered, deflated, check-summed and base64-encoded on the device; mask_png.py) or "none"
+        (boxes, scores and labels only); anything else raises ValueError, "rle", "polygon" or "png_device" on a family without masks
+        NotImplementedError.  ``annotate`` and ``tracker`` read the
         packed device results, so they compose.  ``zones``: a ``zones.DeviceZones`` of ``len(inputs)`` streams, the counterpart of
         ``tracker`` for zone and line counting (zones.py): every result carries ``.zones``; a DeviceZones built on a tracker
         runs that tracker (``tracker`` must be None or that one).  ``dwell``: a ``zones.DeviceDwell`` built on that DeviceZones - the dicts
@@ -511,7 +513,7 @@ class FocoosModel:
         the frame goes up once, one packed result comes back.  Bad arguments raise ValueError; every family but fai_detr raises
         NotImplementedError before anything touches the GPU.  ``annotate``: ``.image`` is the frame with the merged detections drawn on
         it (the resident frame is drawn on the device and copied back beside the packed result; annotate.py).  ``mask_format``: tiled
-        inference has no masks to hand out - "rle" and "polygon" raise NotImplementedError, another unknown value ValueError."""
+        inference has no masks to hand out - "rle", "polygon" and "png_device" raise NotImplementedError, another unknown value ValueError."""
         from .frames import refuse_frames
         from .mask_rle import check_mask_format
 
@@ -522,7 +524,7 @@ class FocoosModel:
             refuse_overlay(annotate, "infer_tiled")
         from .tiled import infer_tiled as _infer_tiled
 
-        if check_mask_format(mask_format, None, "infer_tiled") in ("rle", "polygon"):
+        if check_mask_format(mask_format, None, "infer_tiled") in ("rle", "polygon", "png_device"):
             raise NotImplementedError(f"infer_tiled: mask_format={mask_format!r} is not built: tiled inference merges boxes only (model family "
                                       f"{self.model.family!r})")
 

@@ -331,6 +331,8 @@ class MaskFormerProcessor(DETRProcessor):
     polygon_capacity: Optional[int] = None   # words per image of the mask_format="polygon" pool; None = mask_polygon.default_capacity (Q (4 W + 1))
     polygon_max_edges: Optional[int] = None  # boundary edges per image of its edge workspace; None = mask_polygon.default_max_edges (Q 2 (H + W))
     _polygon_encoder = None                  # the MaskPolygonEncoder of the last "polygon" call, reused like _rle_encoder
+    png_capacity: Optional[int] = None   # base64 quads per image of the mask_format="png_device" pool; None = mask_png.default_capacity
+    _png_encoder = None                  # the MaskPngEncoder of the last "png_device" call, reused like _rle_encoder
 
     def __init__(self, config: dict, image_size=None):
         super().__init__(config, None)
@@ -487,21 +489,25 @@ class MaskFormerProcessor(DETRProcessor):
         masks as uncompressed COCO RLE on the device (mask_rle.py, DESIGN 18: ``FocoosDet.rle`` is set, ``mask`` is None, no dense mask is
         copied or unpacked unless a slot overflowed the pool of ``self.rle_capacity`` counts per image); "polygon" traces the masks' boundaries
         on the device (mask_polygon.py, DESIGN 19: ``FocoosDet.polygons`` is set, ``mask`` and ``rle`` are None; ``self.polygon_capacity`` words per
-        image); "none" is ``encode_masks=False``."""
+        image); "png_device" writes the base64 PNG of every trimmed mask on the device (mask_png.py, DESIGN 28: ``FocoosDet.mask`` decodes to the
+        image "png" gives; ``self.png_capacity`` base64 quads per image); "none" is ``encode_masks=False``."""
         from .mask_rle import check_mask_format
 
-        if check_mask_format(mask_format, what="pack_detections") in ("rle", "polygon"):
+        if check_mask_format(mask_format, what="pack_detections") in ("rle", "polygon", "png_device"):
+            from .mask_png import MaskPngEncoder
             from .mask_polygon import MaskPolygonEncoder
             from .mask_pool import encoder_for
             from .mask_rle import MaskRleEncoder
 
             if mask_format == "rle":
                 enc = self._rle_encoder = encoder_for(MaskRleEncoder, self._rle_encoder, res, self.rle_capacity)
+            elif mask_format == "png_device":
+                enc = self._png_encoder = encoder_for(MaskPngEncoder, self._png_encoder, res, self.png_capacity)
             else:
                 enc = self._polygon_encoder = encoder_for(MaskPolygonEncoder, self._polygon_encoder, res, self.polygon_capacity,
                                                           self.polygon_max_edges)
             enc.encode(res)      # on the current stream, before the copies below wait for it
-            items, field = enc.fetch(), "rle" if mask_format == "rle" else "polygons"      # the FocoosDet field an item goes to
+            items, field = enc.fetch(), {"rle": "rle", "polygon": "polygons", "png_device": "mask"}[mask_format]      # the FocoosDet field an item goes to
             s, l, b = res.det_scores.cpu().tolist(), res.det_labels.cpu().tolist(), res.det_boxes.cpu().tolist()
             return [FocoosDetections(detections=[
                 FocoosDet(bbox=b[i][j], conf=s[i][j], cls_id=l[i][j], label=class_names[l[i][j]] if class_names else None, **{field: r})

@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 27
+#define FX_ABI_VERSION 28
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -470,6 +470,39 @@ size_t fx_mask_polygon_workspace_bytes(int B, int Q, int H, int W, int max_edges
 int fx_mask_polygon_encode(const int32_t* mask_words, const int32_t* det_count, const int32_t* det_boxes, int B, int Q, int H, int W, int capacity,
                            int max_edges, int32_t* poly_len, int32_t* poly_off, int32_t* poly_pool, void* workspace, size_t workspace_bytes,
                            fx_stream_t stream);
+
+/* ---- Base64 PNG of the kept masks on the device (ABI 28; csrc/mask_png.hip):
+ * FocoosModel.infer(mask_format="png_device").  Input: exactly that of fx_mask_rle_encode (mask_words, det_count, det_boxes; the words and box
+ * of a slot >= clamp(det_count[b], 0, Q) are never read).
+ *
+ * Definition.  The crop of a slot with box (x1, y1, x2, y2) is mask[y1 : min(y2, H), x1 : min(x2, W)] (the inclusive box used as an
+ * exclusive end, as the reference's trim does): h = min(y2, H) - y1 rows of w = min(x2, W) - x1 pixels.  Its file is the PNG signature,
+ * IHDR(w, h, 8, 0, 0, 0, 0), ONE IDAT chunk and IEND, every chunk with its CRC-32.  The IDAT payload is a zlib stream: the header 0x78 0x01,
+ * one final deflate block, the Adler-32 of the raw scanlines, big-endian.  A raw scanline is the filter byte 0x01 (SUB) and then p[x] -
+ * p[x - 1] mod 256 over the row's pixels p in {0, 255}, p[-1] = 0: every byte is 0x00, 0x01 or 0xFF.  The deflate block is a
+ * dynamic-Huffman block (BTYPE = 10) whose code is fixed at build time (csrc/mask_png_table.h, written by scripts/gen_mask_png_table.py):
+ * three literals, end-of-block, the length codes and one distance code, so the same header bits open every stream.  Its tokens: every
+ * non-zero byte is a literal; a run of n zero bytes inside a scanline is one literal, then matches of distance 1 over the other n - 1 bytes
+ * - floor((n - 1) / 258) of length 258, then one for what is left when that is at least PNG_MIN_MATCH, else literals.  No match crosses a
+ * scanline.  The file's bytes go out as base64 (standard alphabet, '=' padding), four characters per int32, the first in the low byte.
+ *
+ * Output, all int32:
+ *  - png_len [B][Q]: the file's base64 quads, ceil(bytes / 3), of every detection, stored or not; 0 for a slot that is no detection; -1 for a
+ *    detection with x1 < 0, y1 < 0, h <= 0 or w <= 0 (nothing is encoded; the host's default path decides what such a mask gives);
+ *  - png_off [B][Q]: the exclusive prefix sum of max(png_len, 0) over the slots of the image, in slot order;
+ *  - png_pool [B][capacity]: the quads of slot j at [b][png_off .. png_off + png_len) iff png_len > 0 and png_off + png_len <= capacity.  A
+ *    slot that does not fit writes nothing (the slots before it stay stored), no other element is ever written, nothing is written at or
+ *    beyond capacity.
+ * Only the rows and words of the crop are read.  Two launches (measure: bits and Adler-32 sums per row, scan per slot; emit), one workgroup
+ * per slot; plain stores to global memory, no global atomics: the output is a pure function of the input.
+ * workspace: fx_mask_png_workspace_bytes(B, Q, H, W) bytes = 8 B Q (H + 1) + 4 B Q, 0 outside the limits; 8-byte aligned, contents
+ * irrelevant.
+ * Limits: 1 <= B, Q <= 65535, H, W >= 1, H W < 2^31, capacity >= 1, and Q times the quads of the longest file of the frame (H scanlines of
+ * W + 1 literals at the longest literal code) below 2^31: lengths and an image's offsets are int32.  Null or misaligned pointers, a short
+ * workspace or anything else outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched or written.  The same in both libraries. */
+size_t fx_mask_png_workspace_bytes(int B, int Q, int H, int W);
+int fx_mask_png_encode(const int32_t* mask_words, const int32_t* det_count, const int32_t* det_boxes, int B, int Q, int H, int W, int capacity,
+                       int32_t* png_len, int32_t* png_off, int32_t* png_pool, void* workspace, size_t workspace_bytes, fx_stream_t stream);
 
 /* ---- Zone and line counting on the device (ABI 21; csrc/zone_ops.hip): FocoosModel.infer_stream(zones=...).
  * Input: the packed results (det_labels i32 [B][T], det_boxes i32 xyxy [B][T][4], 16-byte aligned, det_count i32 [B]; slot j of stream b is a
