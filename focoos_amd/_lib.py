@@ -135,6 +135,9 @@ SIGNATURES = {
     "fx_merge_detections_workspace_bytes": [_i, _i],
     "fx_merge_detections_nms": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "fx_frames_tile_gather_f32": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp],
+    "fx_seg_merge_workspace_bytes": [_i, _i, _i, _i, _i, _i, _i, _i],
+    "fx_seg_merge_views": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                           _vp],
     "fx_roi_select": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp],
     "fx_frames_roi_gather_f32": [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp],
     "fx_roi_attributes": [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
@@ -340,7 +343,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 28  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 29  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:
@@ -375,6 +378,7 @@ def load(name: str = None) -> C.CDLL:
     lib.fx_mask_rle_workspace_bytes.restype = C.c_size_t
     lib.fx_mask_polygon_workspace_bytes.restype = C.c_size_t
     lib.fx_mask_png_workspace_bytes.restype = C.c_size_t
+    lib.fx_seg_merge_workspace_bytes.restype = C.c_size_t
     lib.fx_error_string.argtypes = [C.c_int]
     lib.fx_error_string.restype = C.c_char_p
     if lib.fx_abi_version() != FX_ABI_VERSION:

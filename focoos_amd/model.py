@@ -531,6 +531,33 @@ class FocoosModel:
         return _infer_tiled(self, image, tile, overlap, threshold, merge_threshold, merge_metric, include_full, batch_size, max_detections,
                             annotate)
 
+    def segment_tiled(self, image, tile: Optional[int] = None, overlap: float = 0.2, threshold: Optional[float] = None,
+                      batch_size: Optional[int] = None, max_classes: Optional[int] = None, mask_format: str = "png", annotate: bool = False,
+                      return_label_map: bool = False):
+        """Tiled semantic segmentation of ONE large picture (an engine-native mode like ``infer_tiled``; the reference has none): ``image``
+        (what ``infer_tiled`` takes) is cut into the overlapping windows of ``tiled.tile_grid`` for a square ``tile`` (a multiple of 32,
+        default ``model_info.im_size``) and ``overlap`` in [0, 0.5]; the views run through the engine in chunks of ``batch_size`` (default
+        min(views, 32)) and their low-resolution query maps are merged per class on the device (fx_seg_merge_views; tiled_seg.py, DESIGN
+        29): per pixel and class the best ``score x probability`` of a view's queries of that class, summed over the views that cover the
+        pixel; the pixel takes the class with the largest sum, its confidence is that sum over the number of covering views.  Returns one
+        ``FocoosDet`` per class present, in ascending class id: ``bbox`` the integer xyxy extent of its pixels in frame pixels, ``conf`` the
+        mean confidence of its pixels, the mask in ``mask_format`` (as in ``infer_batch``).  A class is kept when it has more than one
+        pixel and ``conf > threshold`` (default: the processor's; ``<= 0`` keeps all).  ``max_classes`` (default ``num_classes``) mask
+        planes of ``Hf * ceil(Wf / 32) * 4`` bytes each are allocated; kept classes beyond them, in ascending class id, are dropped with
+        a warning.  ``return_label_map``: the result is the pair ``(detections, label_map)``, ``label_map`` the uint8 [Hf, Wf] numpy array of class ids.  ``annotate``: ``.image`` is the frame
+        with the classes drawn on it.  bisenetformer with ``predict_all_pixels`` only: every other family or configuration raises
+        NotImplementedError before anything touches the GPU, bad arguments and frames ValueError."""
+        from .frames import refuse_frames
+
+        refuse_frames(image, "segment_tiled")      # before anything loads the library
+        if annotate:
+            from .annotate import refuse_overlay
+
+            refuse_overlay(annotate, "segment_tiled")
+        from .tiled_seg import segment_tiled as _segment_tiled
+
+        return _segment_tiled(self, image, tile, overlap, threshold, batch_size, max_classes, mask_format, annotate, return_label_map)
+
     def train(self, args, data_train, data_val=None, hub=None):
         """focoos_model.py:221-274: fine-tune on ``data_train`` (indexable, entries = ports.DatasetEntry) with ``args`` (ports.TrainerArgs):
         one process per GPU, TrainStep on every rank, artifacts in ``args.output_dir/args.run_name``, weights reloaded into the engine."""

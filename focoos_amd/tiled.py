@@ -85,8 +85,8 @@ def check_arguments(tile, overlap, merge_threshold, merge_metric, batch_size, ma
     return th, tw
 
 
-def frame_tensor(image) -> torch.Tensor:
-    """One picture (path, PIL image, HWC uint8 ndarray, HWC / CHW uint8 tensor) as a contiguous uint8 [H, W, 3] tensor (where it lives)."""
+def frame_tensor(image, what: str = "infer_tiled") -> torch.Tensor:
+    """One picture (path, PIL image, HWC uint8 ndarray, HWC / CHW uint8 tensor) as a contiguous uint8 [H, W, 3] tensor (where it lives); ``what`` names the caller in the errors."""
     if isinstance(image, (str, os.PathLike)):
         from PIL import Image
 
@@ -98,11 +98,11 @@ def frame_tensor(image) -> torch.Tensor:
     if image.dim() == 4 and image.shape[0] == 1:
         image = image[0]
     if image.dim() != 3:
-        raise ValueError("infer_tiled takes one picture: [H, W, 3] or [3, H, W] uint8")
+        raise ValueError(f"{what} takes one picture: [H, W, 3] or [3, H, W] uint8")
     if image.shape[0] == 3 and image.shape[-1] != 3:   # CHW -> HWC
         image = image.permute(1, 2, 0)
     if image.shape[-1] != 3 or image.dtype != torch.uint8:
-        raise ValueError(f"infer_tiled takes a uint8 RGB picture, got {tuple(image.shape)} {image.dtype}")
+        raise ValueError(f"{what} takes a uint8 RGB picture, got {tuple(image.shape)} {image.dtype}")
     return image.contiguous()
 
 

@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 28
+#define FX_ABI_VERSION 29
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -318,6 +318,42 @@ int fx_merge_detections_nms_batched(const float* det_scores, const int32_t* det_
                                     const int32_t* windows, int S, int V, int T, int frame_h, int frame_w, float merge_threshold, int metric,
                                     int max_detections, float* out_scores, int32_t* out_labels, int32_t* out_boxes, int32_t* out_count,
                                     int32_t* status, void* workspace, size_t workspace_bytes, fx_stream_t stream);
+
+/* ---- Tiled semantic segmentation of one large frame (ABI 29; csrc/seg_merge.hip): FocoosModel.segment_tiled's merge.
+ * Input: N views of one frame [Hf][Wf] as the BiSeNetFormer plan leaves them - mask_probs f32 [N][Q][h][w] (the low-resolution sigmoid maps),
+ * score f32 [N][Q] and label i32 [N][Q] (the per-query class score and class, label in [0, K); a label outside takes part in nothing) - and
+ * the views' windows, int32 [N][4] (x0, y0, ww, wh): `windows` a DEVICE array, 16-byte aligned, `windows_host` the same values in host memory.
+ *
+ * Definition.  For a frame pixel (Y, X) inside window n: P(n, q) = up(p[n][q])[Y - y0][X - x0], up = the bilinear align_corners = False resize
+ * of [h][w] to the WINDOW's extent [wh][ww] in ATen's tap arithmetic (src = scale (dst + 0.5) - 0.5 clamped at 0, scale = (float)h / (float)wh;
+ * along x first, then y, fp32, no contraction).  S(n, c) = max over the queries q of view n with label c of score[n][q] P(n, q), 0 when view
+ * n has none.  A(c) = the sum of S(n, c) over the views that cover the pixel, in ascending n; cover = their number.
+ *  - label_map u8 [Hf][Wf] = argmax_c A(c), the lowest c among equal maxima; conf f32 [Hf][Wf] (optional, may be NULL) = A(label) / cover;
+ *  - per class c: area = its pixels, box = their inclusive extent (x0, y0, x1, y1), score = the mean of conf over them.  The sum is an
+ *    integer one: a pixel enters as (uint64)(clamp(conf, 0, 255) 2^24 + 0.5) evaluated in fp32 (within one unit of 2^-24 of conf: at
+ *    2^23 units and above the addition itself rounds to even) into a 64-bit sum, so it is exact in any order and score =
+ *    (float)(sum / (area 2^24));
+ *  - a class is kept when area > 1 and (threshold <= 0 or score > threshold).  The kept classes take the slots in ascending class id; the
+ *    first max_classes of them are stored, the number of the others is WRITTEN to status[0];
+ *  - the packed result has the layout of fx_seg_postprocess with B = 1 and max_classes slots: det_count i32 [1], det_label i32
+ *    [max_classes], det_score f32, det_box i32 [max_classes][4], det_area i32, mask_words u32 [max_classes][Hf][ceil(Wf / 32)] (optional, may
+ *    be NULL; bit x % 32 of word x / 32, bits at x >= Wf zero).  Slots from det_count on are zeroed in det_*; their planes are not written.
+ * Five launches (prepare, merge, reduce, select, pack), plain stores, no global atomics: the outputs are a pure function of the inputs.
+ * Limits: 1 <= N <= 65535, 1 <= Q <= 128, 1 <= K <= 255, 1 <= max_classes <= 255, 1 <= h, w, Hf, Wf <= 16384; every window has non-zero
+ * extent and lies inside the frame; the union of the windows is the frame; at most FX_SEG_MERGE_MAX_COVER views cover one pixel; the window
+ * edges cut the frame into at most 2^22 rectangles.  FX_SEG_MERGE_MAX_COVER = 9: tiled.tile_grid with overlap <= 0.5 and a tile that is a
+ * multiple of 2 has a stride of at least half a tile, so at most 2 of an axis's regular windows hold a coordinate, the window snapped to
+ * the border is a third, and 3 x 3 = 9.  The host copy of the windows is validated before anything is launched.
+ * workspace: fx_seg_merge_workspace_bytes(...) bytes (0 outside the limits), 16-byte aligned, contents irrelevant: 896 N bytes of sorted
+ * queries and 24 K G bytes of per-workgroup statistics, G = (ceil(Wf / 128) + min(2 N + 1, Wf)) (ceil(Hf / 64) + min(2 N + 1, Hf)) bounding
+ * the workgroups of any window set.  Null (but for conf and mask_words) or misaligned pointers, a short workspace, anything outside the
+ * contract: FX_ERR_INVALID_ARGUMENT, nothing launched, nothing written.  The same in both libraries. */
+#define FX_SEG_MERGE_MAX_COVER 9
+size_t fx_seg_merge_workspace_bytes(int N, int Q, int h, int w, int Hf, int Wf, int K, int max_classes);
+int fx_seg_merge_views(const float* mask_probs, const float* score, const int32_t* label, const int32_t* windows, const int32_t* windows_host,
+                       int N, int Q, int h, int w, int Hf, int Wf, int K, float threshold, int max_classes, void* workspace,
+                       size_t workspace_bytes, uint8_t* label_map, float* conf, int32_t* det_count, int32_t* det_label, float* det_score,
+                       int32_t* det_box, int32_t* det_area, uint32_t* mask_words, int32_t* status, fx_stream_t stream);
 
 /* ---- Drawing the detections on uint8 frames on the device (ABI 17; csrc/annotate.hip): FocoosModel.infer(annotate=True).
  * A label record is the filled rectangle (x0, y0, w, h) of one text line in frame pixels, its colour (R | G << 8 | B << 16) and nchar glyph
