@@ -22,13 +22,14 @@ class StreamAnalytics:
     """The analytics state of one call.  ``track`` / ``zones`` / ``dwell`` / ``heatmap`` / ``classify`` hold what ``resolve`` made of the
     arguments - None, a validated config, or a device object - and, from the first ``prepare`` on, device objects only."""
 
-    def __init__(self, fm, what: str, annotate, detections: bool, tiling, mask_format: str, threshold):
+    def __init__(self, fm, what: str, annotate, detections: bool, tiling, mask_format: str, threshold, polygon_tolerance=None):
         self.fm = fm                      # the FocoosModel
         self.what = what                  # "infer_batch" / "infer_stream": the prefix of the messages
         self.annotate = annotate          # the argument: False, True or an Overlay
         self.detections = detections
         self.tiling = tiling
         self.mask_format = mask_format
+        self.polygon_tolerance = polygon_tolerance      # the argument: None leaves the processor's field in charge
         self.threshold = threshold        # the argument; ``thr`` is the value that runs
         self.track = None                 # TrackerConfig, then DeviceTracker
         self.zones = None                 # list of Zone / Line, then DeviceZones
@@ -41,13 +42,17 @@ class StreamAnalytics:
 
     @classmethod
     def resolve(cls, fm, what: str, *, device_only: bool, track, zones, dwell, heatmap, annotate, classify, tiling, detections: bool,
-                mask_format: str, threshold=None) -> "StreamAnalytics":
+                mask_format: str, threshold=None, polygon_tolerance=None) -> "StreamAnalytics":
         """Every argument check of the entry points, in one order, on the host: nothing is loaded or launched.  ``device_only``
         (``infer_batch``, which sees one batch per call): only a DeviceTracker, DeviceZones, DeviceDwell, DeviceHeatmap, DeviceCascade and
         DeviceTraces are taken, whose state outlives the call.  ``what`` is the prefix of the messages."""
         fam = fm.model.family
         Z.check_detections_flag(detections, zones, annotate, mask_format, what)
         check_mask_format(mask_format, fam, what)
+        if polygon_tolerance is not None:
+            from .mask_polygon import check_polygon_tolerance
+
+            check_polygon_tolerance(polygon_tolerance, mask_format, what)
         if tiling is not None:
             from . import tiled as TL
 
@@ -69,7 +74,7 @@ class StreamAnalytics:
             from . import heat as HM
 
             heatmap = HM.resolve(heatmap, track is not None, fam, what, device_only)
-        an = cls(fm, what, annotate, detections, tiling, mask_format, threshold)
+        an = cls(fm, what, annotate, detections, tiling, mask_format, threshold, polygon_tolerance)
         an.track, an.zones, an.dwell, an.heatmap, an.classify = track, zones, dwell, heatmap, classify
         if annotate:
             an.overlay = check_overlay(annotate, track is not None, zones is not None, fam, what, heatmap is not None, fm, device_only)
@@ -161,7 +166,7 @@ class StreamAnalytics:
         elif fam == "fai_cls":     # the one D2H copy of the batch's logits, unless the lane made it already
             out = fm.processor.pack_detections(logits if logits is not None else pl.logits.cpu(), names, self.thr)
         elif fam in MASK_FAMILIES:
-            out = fm.processor.pack_detections(pl, names, mask_format=self.mask_format)
+            out = fm.processor.pack_detections(pl, names, mask_format=self.mask_format, polygon_tolerance=self.polygon_tolerance)
         else:
             out = fm.processor.pack_detections(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count, names)
         if ids is not None and self.detections:

@@ -14,6 +14,9 @@
 //            place in the stream and the slot its length
 //     emit   poly_off = sum of the earlier slots' lengths; a slot that fits writes every word of its range exactly once
 //
+//   fx_mask_polygon_simplify_workspace_bytes / fx_mask_polygon_simplify: the second section of this file (Douglas-Peucker on the stored streams,
+//   DESIGN.md section 30); fx_mask_polygon_encode and its three kernels do not know of it
+//
 // Every loop has a trip count fixed before it starts (a wrong successor gives a wrong ring, never a walk without end), no workgroup waits
 // for another, nothing is read back between the launches.  The detection count, the box clamped to the frame, the block-wide exclusive scan
 // (groups, leaders) and the block-wide sum (poly_off) are det_common.h's, shared with mask_rle.hip.  Plain vector stores, no atomics;
@@ -336,5 +339,287 @@ extern "C" int fx_mask_polygon_encode(const int32_t* mask_words, const int32_t* 
   const int chunks = (int)((((int64_t)max_edges + POLY_THREADS - 1) / POLY_THREADS) < 16 ? (((int64_t)max_edges + POLY_THREADS - 1) / POLY_THREADS) : 16);
   hipLaunchKernelGGL(mask_polygon_emit_kernel, dim3(chunks, Q, B), dim3(POLY_THREADS), 0, stream, det_count, Q, capacity, max_edges, slot_edges,
                      edges, poly_len, poly_off, poly_pool);
+  return fx_launch_status();
+}
+
+// ---- Vertex simplification of the stored streams (FocoosModel.infer(mask_format="polygon", polygon_tolerance=...), DESIGN.md section 30;
+// the definition - anchors, chains, the exact integer threshold, the three-vertex rule, the hole bit - is in include/focoos_amd.h).
+//
+//   simplify  one workgroup of 1024 threads per slot, one thread per word of the slot's stream (strided above 1024 words), all rings at once:
+//     headers   pointer doubling over the header chain (word w -> w + 1 + V) marks the ring headers in ceil(log2(n / 5 + 1)) rounds; a max-scan
+//               gives every word its ring; the same scan checks that the rings tile the stream exactly (else the slot is refused with -1)
+//     anchors   a 64-bit max per ring of |p_k - p_0|^2 << 32 | ~k: the farthest vertex b, lowest index on ties; 0 and b are kept and every
+//               other vertex gets its chain (L, R) as word indices - the chain (b, V) simply names p_0's word as its R
+//     rounds    level-synchronous: every open vertex adds c_k << 32 | ~k to the 64-bit max of its chain (kept at the chain's left end), then
+//               reads the winner back, applies the threshold ITSELF (no owner step, no extra barrier) and either closes (chain finished),
+//               becomes kept, or re-points L or R to the winner.  Two key arrays alternate so that a round is two barriers; the second one
+//               is __syncthreads_or of "a vertex was kept", which ends the loop early; its trip count is fixed at the slot's largest V
+//     rule      the ring's header thread looks at the two first-round winners: when neither passed, the better one is kept after the loop
+//     tally     one block scan of (kept or header, shoelace term of the ORIGINAL ring): a kept vertex is written to its rank in the
+//               slot's range of the staging pool, a header gets V' | hole << 31
+//   place     out_off = sum of the earlier slots' out_len (as mask_polygon_emit_kernel does); the staged stream is copied to out_pool, every
+//             word of the slot's range exactly once
+//
+// A slot's state is xy, L, R (int32) and two keys (uint64): 28 bytes per word.  Up to POLY_SIMP_LDS_WORDS words it lives in 140 KB of the
+// CU's 160 KB of LDS; above, the same code runs on the slot's range of the workspace in global memory (keys at agent scope there).
+#define POLY_SIMP_THREADS 1024
+#define POLY_SIMP_LDS_WORDS 5120
+#define POLY_SIMP_WORD_BYTES 28
+#define POLY_HEADER (-2)
+#define POLY_KEPT (-1)
+#define POLY_CLOSED (-3)
+
+// What the tally scans: kept vertices and headers before a word, and the shoelace terms before it.
+struct PolyTally {
+  int cnt;
+  long long area;
+};
+__device__ __forceinline__ PolyTally fx_scan_join(PolyTally a, PolyTally b) { return PolyTally{a.cnt + b.cnt, a.area + b.area}; }
+__device__ __forceinline__ PolyTally fx_scan_up(PolyTally v, int o) { return PolyTally{__shfl_up(v.cnt, o, 64), __shfl_up(v.area, o, 64)}; }
+
+__device__ __forceinline__ int64_t poly_vx(int32_t v) { return v & 0xffff; }
+__device__ __forceinline__ int64_t poly_vy(int32_t v) { return (int64_t)((uint32_t)v >> 16); }
+__device__ __forceinline__ int64_t poly_cross(int32_t p, int32_t q) { return poly_vx(p) * poly_vy(q) - poly_vx(q) * poly_vy(p); }
+__device__ __forceinline__ uint64_t poly_key(uint64_t c, int k) { return (c << 32) | (uint64_t)(~(uint32_t)k); }
+__device__ __forceinline__ int poly_key_index(uint64_t key) { return (int)(~(uint32_t)key); }
+
+// c_k of the definition for p in the chain (pi, pj): |cross(pj - pi, p - pi)|, or |p - pi|^2 when the chain's ends are one point.
+__device__ __forceinline__ uint64_t poly_deviation(int32_t pi, int32_t pj, int32_t p) {
+  const int64_t ax = poly_vx(pj) - poly_vx(pi), ay = poly_vy(pj) - poly_vy(pi), bx = poly_vx(p) - poly_vx(pi), by = poly_vy(p) - poly_vy(pi);
+  if (pi == pj) return (uint64_t)(bx * bx + by * by);
+  const int64_t c = ax * by - ay * bx;
+  return (uint64_t)(c < 0 ? -c : c);
+}
+
+// The threshold on the winner's c, T2 = tol16^2: c^2 > floor(T2 |pj - pi|^2 / 256), or 256 c > T2 for a chain whose ends are one point.
+__device__ __forceinline__ bool poly_keeps(int32_t pi, int32_t pj, uint64_t c, uint64_t T2) {
+  if (pi == pj) return 256ull * c > T2;
+  const int64_t ax = poly_vx(pj) - poly_vx(pi), ay = poly_vy(pj) - poly_vy(pi);
+  return c * c > ((T2 * (uint64_t)(ax * ax + ay * ay)) >> 8);
+}
+
+// The keys: LDS operations at workgroup scope, or global ones at agent scope (performed in L2, loads past the CU's L1).
+template <bool LDS>
+__device__ __forceinline__ void poly_key_max(uint64_t* p, uint64_t v) {
+  if (LDS) __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  else __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <bool LDS>
+__device__ __forceinline__ uint64_t poly_key_ld(const uint64_t* p) {
+  return LDS ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <bool LDS>
+__device__ __forceinline__ void poly_key_st(uint64_t* p, uint64_t v) {
+  if (LDS) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One slot, by its whole workgroup: xy = the n words of its stream, L / R / K0 / K1 = n elements of state each (contents irrelevant), stage =
+// n words that take the simplified stream.  Returns its length, -1 for a stream that is no sequence of rings of >= 4 vertices (nothing
+// staged then).  Every index that is formed is one of the slot's own words: a header's V was checked against n, b and the winners are
+// indices that vertices of the ring wrote into a key.
+template <bool LDS>
+__device__ __forceinline__ int poly_simplify_slot(const int32_t* xy, int32_t* L, int32_t* R, uint64_t* K0, uint64_t* K1, int n, uint64_t T2,
+                                                  int32_t* __restrict__ stage) {
+  __shared__ int s_maxv;
+  const int tid = threadIdx.x;
+  int32_t* mark = reinterpret_cast<int32_t*>(K0);   // the first half of K0, until the keys need it
+
+  // headers: pointer doubling over w -> w + 1 + V from word 0; every word jumps, only the ones reached from 0 are headers
+  for (int w = tid; w < n; w += POLY_SIMP_THREADS) {
+    const int64_t v = xy[w];
+    L[w] = (v >= 4 && (int64_t)w + 1 + v <= (int64_t)n) ? (int)(w + 1 + v) : n;
+    mark[w] = w == 0;
+    poly_key_st<LDS>(&K1[w], 0ull);
+  }
+  if (tid == 0) s_maxv = 0;
+  __syncthreads();
+  {
+    int32_t *js = L, *jd = R;
+    const int RH = poly_rounds(n / 5 + 1);   // at most n / 5 headers: after round r every header within 2^(r + 1) jumps of word 0 is marked
+    for (int r = 0; r < RH; ++r) {
+      for (int w = tid; w < n; w += POLY_SIMP_THREADS) {
+        const int j = js[w];
+        jd[w] = j < n ? js[j] : n;
+        if (j < n && mark[w]) mark[j] = 1;   // a mark that lands during the round marks a true header too
+      }
+      __syncthreads();
+      int32_t* t = js;
+      js = jd, jd = t;
+    }
+  }
+  // L <- the header of every word's ring (the last header at or before it); the rings must tile the stream; the largest V
+  int run_mx = 0, run_sum = 0;
+  for (int base = 0; base < n; base += POLY_SIMP_THREADS) {   // block-uniform
+    const int w = base + tid;
+    const bool h = w < n && mark[w] != 0;
+    const int v = h ? xy[w] : 0;
+    const bool ok = h && v >= 4 && (int64_t)w + 1 + v <= (int64_t)n;
+    FxSumMax total;
+    const FxSumMax ex = fx_block_exscan<POLY_SIMP_THREADS>(FxSumMax{ok ? 1 + v : 0, h ? w + 1 : 0}, total);
+    if (w < n) L[w] = max(run_mx, max(ex.mx, h ? w + 1 : 0)) - 1;
+    if (ok) atomicMax(&s_maxv, v);
+    run_mx = max(run_mx, total.mx), run_sum += total.sum;
+  }
+  __syncthreads();
+  if (run_sum != n) return -1;   // block-uniform
+  const int maxV = s_maxv;
+
+  // anchors: b = the vertex farthest from p_0, per ring, in the header's key
+  for (int w = tid; w < n; w += POLY_SIMP_THREADS) {
+    const int hd = L[w];
+    if (hd == w) continue;
+    const int32_t p0 = xy[hd + 1], p = xy[w];
+    const int64_t dx = poly_vx(p) - poly_vx(p0), dy = poly_vy(p) - poly_vy(p0);
+    poly_key_max<LDS>(&K1[hd], poly_key((uint64_t)(dx * dx + dy * dy), w));
+  }
+  __syncthreads();
+  for (int w = tid; w < n; w += POLY_SIMP_THREADS) {
+    const int hd = L[w];
+    const int b = poly_key_index(poly_key_ld<LDS>(&K1[hd]));
+    if (hd == w) {
+      L[w] = POLY_HEADER, R[w] = b;
+    } else {
+      const int a = hd + 1;
+      if (w == a || w == b) L[w] = POLY_KEPT;
+      else if (w < b) L[w] = a, R[w] = b;
+      else L[w] = b, R[w] = a;   // the chain (b, V): its right end is p_0 again
+    }
+    poly_key_st<LDS>(&K0[w], 0ull);
+  }
+  __syncthreads();
+
+  // rounds: every chain finds its winner and either splits at it or is finished
+  for (int r = 0; r < maxV; ++r) {
+    uint64_t *cur = (r & 1) ? K1 : K0, *nxt = (r & 1) ? K0 : K1;
+    for (int w = tid; w < n; w += POLY_SIMP_THREADS) {
+      poly_key_st<LDS>(&nxt[w], 0ull);
+      const int l = L[w];
+      if (l >= 0) poly_key_max<LDS>(&cur[l], poly_key(poly_deviation(xy[l], xy[R[w]], xy[w]), w));
+    }
+    __syncthreads();
+    int split = 0;
+    for (int w = tid; w < n; w += POLY_SIMP_THREADS) {
+      const int l = L[w];
+      if (l >= 0) {
+        const uint64_t key = poly_key_ld<LDS>(&cur[l]);
+        const int ks = poly_key_index(key);
+        if (!poly_keeps(xy[l], xy[R[w]], key >> 32, T2)) L[w] = POLY_CLOSED;
+        else if (w == ks) L[w] = POLY_KEPT, split = 1;
+        else if (w < ks) R[w] = ks;
+        else L[w] = ks;
+      } else if (r == 0 && l == POLY_HEADER) {
+        // the three-vertex rule: when neither first-round winner passes, the ring ends with its two anchors, and the better winner joins them
+        const int a = w + 1, b = R[w];
+        const uint64_t ka = poly_key_ld<LDS>(&cur[a]), kb = poly_key_ld<LDS>(&cur[b]);
+        const bool any = (ka != 0 && poly_keeps(xy[a], xy[b], ka >> 32, T2)) || (kb != 0 && poly_keeps(xy[b], xy[a], kb >> 32, T2));
+        const uint64_t best = ka > kb ? ka : kb;   // the larger c, the lower index on ties
+        R[w] = (!any && best != 0) ? poly_key_index(best) : -1;
+      }
+    }
+    if (!__syncthreads_or(split)) break;
+  }
+  for (int w = tid; w < n; w += POLY_SIMP_THREADS)
+    if (L[w] == POLY_HEADER && R[w] >= 0) L[R[w]] = POLY_KEPT;
+  __syncthreads();
+
+  // tally: ranks of the kept vertices and headers, shoelace sums of the original rings (the closing term is the header's)
+  PolyTally run{0, 0};
+  for (int base = 0; base < n; base += POLY_SIMP_THREADS) {   // block-uniform
+    const int w = base + tid;
+    const int l = w < n ? L[w] : POLY_CLOSED;
+    const bool header = l == POLY_HEADER, kept = l == POLY_KEPT;
+    long long term = 0;
+    if (w < n && !header && w + 1 < n && L[w + 1] != POLY_HEADER) term = poly_cross(xy[w], xy[w + 1]);
+    PolyTally total;
+    const PolyTally ex = fx_scan_join(run, fx_block_exscan<POLY_SIMP_THREADS>(PolyTally{(header || kept) ? 1 : 0, term}, total));
+    if (header) R[w] = ex.cnt, poly_key_st<LDS>(&K0[w], (uint64_t)ex.area);
+    else if (kept) stage[ex.cnt] = xy[w];
+    run = fx_scan_join(run, total);
+  }
+  __syncthreads();
+  for (int w = tid; w < n; w += POLY_SIMP_THREADS) {
+    if (L[w] != POLY_HEADER) continue;
+    const int V = xy[w], nh = w + 1 + V, at = R[w];
+    const int cnt = nh < n ? R[nh] : run.cnt;
+    const long long upto = nh < n ? (long long)poly_key_ld<LDS>(&K0[nh]) : run.area;
+    const long long area2 = upto - (long long)poly_key_ld<LDS>(&K0[w]) + poly_cross(xy[w + V], xy[w + 1]);
+    stage[at] = (cnt - at - 1) | (area2 < 0 ? (int32_t)0x80000000 : 0);
+  }
+  return run.cnt;
+}
+
+__global__ __launch_bounds__(POLY_SIMP_THREADS) void mask_polygon_simplify_kernel(const int32_t* __restrict__ poly_len, const int32_t* __restrict__ poly_off,
+                                                                                   const int32_t* __restrict__ poly_pool, const int32_t* __restrict__ det_count,
+                                                                                   int Q, int capacity, uint32_t T2, int32_t* gL, int32_t* gR, uint64_t* gK0,
+                                                                                   uint64_t* gK1, int32_t* __restrict__ stage, int32_t* __restrict__ out_len) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char poly_smem[];
+  const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int64_t slot = (int64_t)b * Q + j;
+  const int n = poly_len[slot], off = poly_off[slot];
+  const bool stored = j < fx_det_count(det_count, b, Q) && n > 0 && off >= 0 && (int64_t)off + n <= (int64_t)capacity;
+  if (!stored) {   // block-uniform
+    if (tid == 0) out_len[slot] = (n == 0 && j < fx_det_count(det_count, b, Q)) ? 0 : -1;
+    return;
+  }
+  const int64_t at = (int64_t)b * capacity + off;
+  int len;
+  if (n <= POLY_SIMP_LDS_WORDS) {
+    uint64_t *K0 = reinterpret_cast<uint64_t*>(poly_smem), *K1 = K0 + POLY_SIMP_LDS_WORDS;
+    int32_t *xy = reinterpret_cast<int32_t*>(K1 + POLY_SIMP_LDS_WORDS), *L = xy + POLY_SIMP_LDS_WORDS, *R = L + POLY_SIMP_LDS_WORDS;
+    for (int w = tid; w < n; w += POLY_SIMP_THREADS) xy[w] = poly_pool[at + w];
+    __syncthreads();
+    len = poly_simplify_slot<true>(xy, L, R, K0, K1, n, (uint64_t)T2, stage + at);
+  } else {
+    len = poly_simplify_slot<false>(poly_pool + at, gL + at, gR + at, gK0 + at, gK1 + at, n, (uint64_t)T2, stage + at);
+  }
+  if (tid == 0) out_len[slot] = len;
+}
+
+__global__ __launch_bounds__(POLY_THREADS) void mask_polygon_place_kernel(const int32_t* __restrict__ poly_off, const int32_t* __restrict__ out_len, int Q,
+                                                                           int capacity, const int32_t* __restrict__ stage, int32_t* __restrict__ out_off,
+                                                                           int32_t* __restrict__ out_pool) {
+  const int j = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+  const int64_t slot = (int64_t)b * Q + j;
+  int part = 0;
+  for (int i = tid; i < j; i += POLY_THREADS) part += max(out_len[(int64_t)b * Q + i], 0);
+  const int off = fx_block_sum<POLY_THREADS>(part);
+  const int len = out_len[slot], src = poly_off[slot];
+  if (blockIdx.x == 0 && tid == 0) out_off[slot] = off;
+  // a simplified stream is no longer than its input and starts no later: what was stored fits; the checks keep every index in the pools
+  if (len <= 0 || src < 0 || (int64_t)src + len > (int64_t)capacity || (int64_t)off + len > (int64_t)capacity) return;
+  const int32_t* from = stage + (int64_t)b * capacity + src;
+  int32_t* to = out_pool + (int64_t)b * capacity + off;
+  for (int w = blockIdx.x * POLY_THREADS + tid; w < len; w += gridDim.x * POLY_THREADS) to[w] = from[w];
+}
+
+// The staging pool and the state of the slots that do not fit LDS: L, R (int32) and two keys (uint64, on an 8-byte boundary: 8 bytes of slack)
+// per word of every image's pool.
+extern "C" size_t fx_mask_polygon_simplify_workspace_bytes(int B, int Q, int capacity) {
+  if (!(B >= 1 && B <= 65535 && Q >= 1 && Q <= 65535 && capacity >= 1)) return 0;
+  return (size_t)B * capacity * POLY_SIMP_WORD_BYTES + 8;
+}
+
+extern "C" int fx_mask_polygon_simplify(const int32_t* poly_len, const int32_t* poly_off, const int32_t* poly_pool, const int32_t* det_count, int B, int Q,
+                                        int capacity, int tol16, int32_t* out_len, int32_t* out_off, int32_t* out_pool, void* workspace,
+                                        size_t workspace_bytes, fx_stream_t stream_) {
+  FX_CHECK_ARG(poly_len && poly_off && poly_pool && det_count && out_len && out_off && out_pool && workspace);
+  FX_CHECK_ARG((((uintptr_t)poly_len | (uintptr_t)poly_off | (uintptr_t)poly_pool | (uintptr_t)det_count | (uintptr_t)out_len | (uintptr_t)out_off |
+                 (uintptr_t)out_pool | (uintptr_t)workspace) & 3) == 0);
+  FX_CHECK_ARG(B >= 1 && B <= 65535 && Q >= 1 && Q <= 65535 && capacity >= 1 && tol16 >= 1 && tol16 <= 1024);
+  FX_CHECK_ARG(out_pool != poly_pool && workspace_bytes >= fx_mask_polygon_simplify_workspace_bytes(B, Q, capacity));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  const size_t words = (size_t)B * capacity;
+  uint64_t* gK0 = reinterpret_cast<uint64_t*>(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  uint64_t* gK1 = gK0 + words;
+  int32_t* stage = reinterpret_cast<int32_t*>(gK1 + words);
+  int32_t *gL = stage + words, *gR = gL + words;
+  static int granted = 0;
+  const int smem = POLY_SIMP_LDS_WORDS * POLY_SIMP_WORD_BYTES;
+  if (!fx_ensure_dyn_smem(reinterpret_cast<const void*>(mask_polygon_simplify_kernel), smem, granted)) return FX_ERR_RUNTIME;
+  hipLaunchKernelGGL(mask_polygon_simplify_kernel, dim3(Q, B), dim3(POLY_SIMP_THREADS), smem, stream, poly_len, poly_off, poly_pool, det_count, Q, capacity,
+                     (uint32_t)(tol16 * tol16), gL, gR, gK0, gK1, stage, out_len);
+  const int chunks = (int)((((int64_t)capacity + POLY_THREADS - 1) / POLY_THREADS) < 16 ? (((int64_t)capacity + POLY_THREADS - 1) / POLY_THREADS) : 16);
+  hipLaunchKernelGGL(mask_polygon_place_kernel, dim3(chunks, Q, B), dim3(POLY_THREADS), 0, stream, poly_off, out_len, Q, capacity, stage, out_off, out_pool);
   return fx_launch_status();
 }

@@ -7,9 +7,11 @@ the image's edge workspace, or whose stream did not fit the pool, is traced on t
 warning per call, so the result is always complete.
 
 A ring is a flat list ``[x0, y0, x1, y1, ...]`` of lattice points in frame pixels (pixel (x, y) is the square [x, x + 1] x [y, y + 1]); the
-rings of a mask come in the canonical order of the definition, holes included: a hole has a negative shoelace sum (``is_hole``).  Vertex
-simplification and cv2's pixel-centre contours are out of scope.  What this encoder shares with mask_rle.py's (buffers, checks, copy
-back, fallback, ``encoder_for``) is mask_pool.py."""
+rings of a mask come in the canonical order of the definition, holes included: a hole has a negative shoelace sum (``is_hole``).  With a
+tolerance (``polygon_tolerance=``) the rings are simplified on the device as well (Douglas-Peucker in exact integers,
+``fx_mask_polygon_simplify``; ``simplify_ring`` is the same definition on the host) and only the simplified streams are copied back; a
+simplified ring can lose its orientation, so its hole flag travels beside it.  cv2's pixel-centre contours are out of scope.  What this
+encoder shares with mask_rle.py's (buffers, checks, copy back, fallback, ``encoder_for``) is mask_pool.py."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -93,6 +95,88 @@ def decode_stream(stream) -> List[List[int]]:
     return rings
 
 
+def decode_simplified_stream(stream):
+    """A slot's stream of the device simplifier (per ring: v | hole << 31, then v >= 3 vertices) -> (rings, holes)."""
+    s = np.asarray(stream, np.int64).reshape(-1) & 0xffffffff
+    rings, holes, i = [], [], 0
+    while i < len(s):
+        v, hole = int(s[i]) & 0x7fffffff, bool(int(s[i]) >> 31)
+        if v < 3 or i + 1 + v > len(s):
+            raise ValueError(f"decode_simplified_stream: a ring of {v} vertices at word {i} of a stream of {len(s)}")
+        xy = s[i + 1:i + 1 + v]
+        rings.append(np.stack([xy & 0xffff, xy >> 16], axis=1).reshape(-1).tolist())
+        holes.append(hole)
+        i += 1 + v
+    return rings, holes
+
+
+def tolerance_units(tolerance, what: str = "polygon_tolerance") -> int:
+    """A tolerance in pixels -> T sixteenths of a pixel, 1 .. 1024; ValueError for anything that is no number in (0, 64] or rounds to 0."""
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float, np.integer, np.floating)) or not 0 < float(tolerance) <= 64:
+        raise ValueError(f"{what} = {tolerance!r} must be a number of pixels in (0, 64]")
+    T = int(round(16 * float(tolerance)))
+    if T < 1:
+        raise ValueError(f"{what} = {tolerance!r} rounds to 0 sixteenths of a pixel: the smallest tolerance is 1 / 16")
+    return T
+
+
+def check_polygon_tolerance(tolerance, mask_format, what: str = "infer") -> Optional[int]:
+    """The ``polygon_tolerance`` keyword of the inference surface: None, or T sixteenths.  ValueError with another ``mask_format`` than
+    "polygon" or for a value ``tolerance_units`` refuses.  Host only: nothing is loaded or launched."""
+    if tolerance is None:
+        return None
+    if mask_format != "polygon":
+        raise ValueError(f"{what}: polygon_tolerance = {tolerance!r} needs mask_format='polygon', got mask_format={mask_format!r}")
+    return tolerance_units(tolerance, f"{what}: polygon_tolerance")
+
+
+def _simplify(ring, T: int) -> List[int]:
+    """The definition of include/focoos_amd.h in Python integers, T in sixteenths: the chains on a stack, depth is no concern."""
+    pts = [(int(ring[i]), int(ring[i + 1])) for i in range(0, len(ring), 2)]
+    V, T2 = len(pts), T * T
+    if V < 4:
+        raise ValueError(f"simplify_ring: a traced ring has at least 4 vertices, got {V}")
+    x0, y0 = pts[0]
+    b = max(range(V), key=lambda k: ((pts[k][0] - x0) ** 2 + (pts[k][1] - y0) ** 2, -k))
+
+    def winner(i, j):      # (c, -k*, kept) of the chain (i, j), None without an interior
+        (xi, yi), (xj, yj) = pts[i], pts[j % V]
+        ax, ay = xj - xi, yj - yi
+        if j - i < 2:
+            return None
+        if (ax, ay) == (0, 0):
+            c, k = max(((pts[k][0] - xi) ** 2 + (pts[k][1] - yi) ** 2, -k) for k in range(i + 1, j))
+            return c, k, 256 * c > T2
+        c, k = max((abs(ax * (pts[k][1] - yi) - ay * (pts[k][0] - xi)), -k) for k in range(i + 1, j))
+        return c, k, c * c > T2 * (ax * ax + ay * ay) // 256
+
+    keep, first, stack = {0, b}, [], [(0, b), (b, V)]
+    while stack:
+        i, j = stack.pop()
+        w = winner(i, j)
+        if (i, j) in ((0, b), (b, V)) and w is not None:
+            first.append(w)
+        if w is not None and w[2]:
+            keep.add(-w[1])
+            stack += [(i, -w[1]), (-w[1], j)]
+    if len(keep) == 2 and first:      # never fewer than three vertices: the better first-round candidate
+        keep.add(-max(first)[1])
+    return [v for k in sorted(keep) for v in pts[k]]
+
+
+def simplify_ring(ring, tolerance) -> List[int]:
+    """A traced ring (flat [x0, y0, ...], at least 4 vertices) simplified with ``tolerance`` pixels: a subsequence that keeps the first
+    vertex and has at least 3 (the definition of include/focoos_amd.h, which the device kernel computes bit for bit)."""
+    return _simplify(ring, tolerance_units(tolerance, "simplify_ring: tolerance"))
+
+
+def simplify_rings(rings, tolerance):
+    """The rings of a mask -> (the simplified rings, their hole flags).  A hole is decided on the ORIGINAL ring: a simplified ring's own
+    area can flip sign or vanish."""
+    T = tolerance_units(tolerance, "simplify_rings: tolerance")
+    return [_simplify(r, T) for r in rings], [is_hole(r) for r in rings]
+
+
 def ring_area2(ring) -> int:
     """The shoelace sum of a ring, twice its signed area: positive for an outer ring, negative for a hole."""
     r = np.asarray(ring, np.int64).reshape(-1, 2)
@@ -156,6 +240,35 @@ class MaskPolygonEncoder(PooledMaskEncoder):
     def __init__(self, B: int, Q: int, H: int, W: int, device, capacity: Optional[int] = None, max_edges: Optional[int] = None):
         super().__init__(B, Q, H, W, device, capacity, max_edges)
         self.poly_len, self.poly_off, self.poly_pool = self.meta[0], self.meta[1], self.pool
+        self.tol16 = None          # of the last encode: None, or T sixteenths of a pixel
+        self.out_meta = self.out_pool = self.simplify_workspace = None      # made with the first encode that has a tolerance
+
+    def encode(self, res, tolerance: Optional[float] = None) -> None:
+        """``tolerance`` (pixels; not part of the encoder's key): the streams are also simplified on the device, behind the trace on the
+        same stream, and ``fetch()`` copies back and decodes the simplified ones: per detection ``(rings, holes)``."""
+        import torch
+
+        from ._lib import check
+
+        T = None if tolerance is None else tolerance_units(tolerance, "MaskPolygonEncoder.encode: tolerance")
+        super().encode(res)
+        self.tol16 = T
+        if T is None:
+            return
+        if self.out_pool is None:
+            nb = int(self.lib.fx_mask_polygon_simplify_workspace_bytes(self.B, self.Q, self.capacity))
+            if nb == 0:
+                raise ValueError(f"MaskPolygonEncoder: B = {self.B}, Q = {self.Q}, capacity = {self.capacity} is outside the simplifier's limits")
+            self.out_meta = torch.zeros_like(self.meta)
+            self.out_pool = torch.zeros_like(self.pool)
+            self.simplify_workspace = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.fx_mask_polygon_simplify(
+            self.meta[0].data_ptr(), self.meta[1].data_ptr(), self.pool.data_ptr(), res.det_count.data_ptr(), self.B, self.Q, self.capacity, T,
+            self.out_meta[0].data_ptr(), self.out_meta[1].data_ptr(), self.out_pool.data_ptr(), self.simplify_workspace.data_ptr(),
+            self.simplify_workspace.numel(), torch.cuda.current_stream(self.device).cuda_stream), "fx_mask_polygon_simplify")
+
+    def _outputs(self):
+        return (self.meta, self.pool) if self.tol16 is None else (self.out_meta, self.out_pool)
 
     @staticmethod
     def sizes(Q, H, W, capacity=None, max_edges=None):
@@ -167,10 +280,11 @@ class MaskPolygonEncoder(PooledMaskEncoder):
         return count, count.size * 4
 
     def _decode(self, stream):
-        return decode_stream(stream)
+        return decode_stream(stream) if self.tol16 is None else decode_simplified_stream(stream)
 
     def _encode_words(self, words):
-        return trace_words_numpy(words, self.W)
+        rings = trace_words_numpy(words, self.W)
+        return rings if self.tol16 is None else ([_simplify(r, self.tol16) for r in rings], [is_hole(r) for r in rings])
 
     def _warning(self, fell, masks):
         return (f"mask_format='polygon': {fell} of {masks} masks did not fit the pool of {self.capacity} words or the workspace of "

@@ -90,7 +90,8 @@ class PooledMaskEncoder:
 
         if self._res is None:
             raise RuntimeError(f"{type(self).__name__}.fetch: nothing was encoded")
-        meta = self.meta.cpu().numpy().astype(np.int64)      # synchronises the stream
+        meta_d, pool_d = self._outputs()
+        meta = meta_d.cpu().numpy().astype(np.int64)      # synchronises the stream
         ln, off = meta[0], meta[1]
         count, count_bytes = self._det_counts(ln)
         stored = (ln > 0) & (off + ln <= self.capacity)
@@ -99,7 +100,7 @@ class PooledMaskEncoder:
             self._host = torch.empty(self.B, self.capacity, dtype=torch.int32, pin_memory=True)
         for b in range(self.B):
             if used[b]:
-                self._host[b, :used[b]].copy_(self.pool[b, :used[b]], non_blocking=True)
+                self._host[b, :used[b]].copy_(pool_d[b, :used[b]], non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         pool = self._host.numpy()
         self.last_d2h_bytes = int(meta.size * 4 + count_bytes + used.sum() * 4)
@@ -128,6 +129,10 @@ class PooledMaskEncoder:
             warnings.warn(self._warning(fell, masks), RuntimeWarning, stacklevel=3)
         return out
 
+
+    def _outputs(self):
+        """(meta, pool) that ``fetch`` copies back: the encoder's own, unless a subclass ran another call behind it."""
+        return self.meta, self.pool
 
     def _encode_slot(self, words, box):
         return self._encode_words(words)

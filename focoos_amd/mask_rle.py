@@ -76,7 +76,8 @@ def rle_area(rle: dict) -> int:
 def to_coco_results(detections, image_id, category_ids: Optional[Sequence[int]] = None) -> List[dict]:
     """The entries of a COCO results file for one image: ``detections`` (a FocoosDetections or a list of FocoosDet) -> [{"image_id",
     "category_id", "bbox" (x, y, w, h), "score", "segmentation" (the uncompressed RLE dict when the detection has one; else, when it has polygons, its outer rings as COCO's list of
-    flat [x0, y0, x1, y1, ...]: a COCO polygon cannot carry a hole, so the hole rings are left out and the holes read as filled)}].
+    flat [x0, y0, x1, y1, ...]: a COCO polygon cannot carry a hole, so the hole rings are left out and the holes read as filled; the rings
+    with a false ``polygon_holes`` flag when the detection has those, by ``is_hole`` otherwise)}].
     ``category_ids[cls_id]`` maps the model's class index to the dataset's category id (identity when None).  The box of a detection with
     an RLE or polygons is the inclusive extent of its pixels, so its width is x1 - x0 + 1."""
     out = []
@@ -91,7 +92,8 @@ def to_coco_results(detections, image_id, category_ids: Optional[Sequence[int]] 
         elif polygons is not None:
             from .mask_polygon import outer_rings
 
-            e["segmentation"] = outer_rings(polygons)
+            holes = getattr(d, "polygon_holes", None)      # simplified rings carry their hole flags: their own area no longer tells
+            e["segmentation"] = outer_rings(polygons) if holes is None else [list(r) for r, h in zip(polygons, holes) if not h]
         out.append(e)
     return out
 

@@ -283,7 +283,8 @@ class FocoosModel:
         return self.model.device
 
     def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate=False, tracker=None,
-                    mask_format: str = "png", zones=None, dwell=None, heatmap=None, tiling=None, classify=None) -> List[FocoosDetections]:
+                    mask_format: str = "png", zones=None, dwell=None, heatmap=None, tiling=None, classify=None,
+                    polygon_tolerance: Optional[float] = None) -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
         reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``inputs`` may also be a
         ``frames.FrameBatch`` of NV12 / I420 / BGR / RGB video frames, host or device: the results are those of the same frames passed as
@@ -314,13 +315,17 @@ class FocoosModel:
         runs that tracker (``tracker`` must be None or that one) and remembers the attribute per track.  The inputs are uint8 frames (a
         list of RGB arrays is wrapped into one ``FrameBatch``; sizes may differ without ``tiling``); everything else is that of
         ``classify=None``.  A family without boxes raises NotImplementedError, anything but a DeviceCascade TypeError, a classifier on
-        another device or non-uint8 inputs ValueError, all before anything touches the GPU."""
+        another device or non-uint8 inputs ValueError, all before anything touches the GPU.
+        ``polygon_tolerance`` (pixels, in (0, 64]; overrides ``processor.polygon_tolerance`` for this call): with ``mask_format="polygon"``
+        the traced rings are simplified on the device (Douglas-Peucker in exact integers; mask_polygon.py), only the simplified
+        streams come back, and every detection also carries ``polygon_holes``; with another format, or a value outside the range or
+        below 1 / 32, ValueError before anything touches the GPU."""
         from .analytics import StreamAnalytics, batch_size
         from .frames import drawable
 
         an = StreamAnalytics.resolve(self, "infer_batch", device_only=True, track=tracker, zones=zones, dwell=dwell, heatmap=heatmap,
                                      annotate=annotate, classify=classify, tiling=tiling, detections=True, mask_format=mask_format,
-                                     threshold=threshold)
+                                     threshold=threshold, polygon_tolerance=polygon_tolerance)
         inputs = an.frames(inputs)      # a FrameBatch (or one Frame) goes where a list of images goes (frames.py, DESIGN 21)
         an.prepare(inputs, batch_size(inputs))
         t0 = perf_counter()
@@ -351,7 +356,8 @@ class FocoosModel:
         return out
 
     def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate=False, track=None,
-                     mask_format: str = "png", zones=None, detections: bool = True, dwell=None, heatmap=None, tiling=None, classify=None):
+                     mask_format: str = "png", zones=None, detections: bool = True, dwell=None, heatmap=None, tiling=None, classify=None,
+                     polygon_tolerance: Optional[float] = None):
         """Throughput inference (round 6): iterate over ``batches`` (each a list of images of ONE common shape after preprocessing and one
         batch size) and yield each batch's ``List[FocoosDetections]`` in order, with up to ``depth`` batches in flight on the engine's
         pipeline (engine.pipeline(): batch i+1's backbone runs beside batch i's decoder tail; default depth 3).  Same results as
@@ -412,7 +418,8 @@ class FocoosModel:
         ids, zone dicts and drawn images are those of ``classify=None``.  A family without boxes raises NotImplementedError; anything but
         a Cascade / DeviceCascade TypeError; a classifier on another device, non-uint8 inputs, ``detections=False``, ``interval > 1`` or
         ``hold="best"`` without ``track``, or more than 65535 crops per batch ValueError - all before anything touches the GPU; eligible
-        objects left out for want of crop budget warn once per call.  With ``None`` nothing changes."""
+        objects left out for want of crop budget warn once per call.  With ``None`` nothing changes.
+        ``polygon_tolerance``: as in ``infer_batch``; the simplify call follows each batch's trace on the current stream."""
         from collections import deque
         from types import SimpleNamespace
 
@@ -421,7 +428,7 @@ class FocoosModel:
 
         an = StreamAnalytics.resolve(self, "infer_stream", device_only=False, track=track, zones=zones, dwell=dwell, heatmap=heatmap,
                                      annotate=annotate, classify=classify, tiling=tiling, detections=detections, mask_format=mask_format,
-                                     threshold=threshold)
+                                     threshold=threshold, polygon_tolerance=polygon_tolerance)
         if tiling is not None:      # the same tail on the merged result of every frame batch, in the tiler's own loop (tiled.py)
             from . import tiled as TL
 
@@ -470,12 +477,14 @@ class FocoosModel:
         from .frames import as_frame_batch
 
         lst = as_frame_batch(inputs) or (inputs if isinstance(inputs, list) else [inputs])
-        return self.infer_batch(lst, threshold=kwargs.get("threshold"), mask_format=kwargs.get("mask_format", "png"))[0]
+        return self.infer_batch(lst, threshold=kwargs.get("threshold"), mask_format=kwargs.get("mask_format", "png"),
+                                polygon_tolerance=kwargs.get("polygon_tolerance"))[0]
 
-    def infer(self, image, threshold: Optional[float] = None, annotate: bool = False, mask_format: str = "png") -> FocoosDetections:
+    def infer(self, image, threshold: Optional[float] = None, annotate: bool = False, mask_format: str = "png",
+              polygon_tolerance: Optional[float] = None) -> FocoosDetections:
         """focoos_model.py:370-416: one picture (path, PIL image, array, tensor) -> FocoosDetections.  ``annotate``: ``.image`` is the
         picture (np.uint8 [H, W, 3] RGB, original size) with the detections drawn on it on the device (annotate.py; the input itself
-        when nothing was detected) and ``.latency.annotate`` / ``.latency.imload`` are set.  ``mask_format``: as in ``infer_batch``.
+        when nothing was detected) and ``.latency.annotate`` / ``.latency.imload`` are set.  ``mask_format`` and ``polygon_tolerance``: as in ``infer_batch``.
         ``image`` may also be a ``frames.Frame`` (NV12, I420, BGR or RGB video frame, host or device)."""
         from .frames import Frame, FrameBatch
         from .mask_rle import check_mask_format
@@ -485,16 +494,20 @@ class FocoosModel:
 
             refuse_overlay(annotate, "infer")
         check_mask_format(mask_format, self.model.family, "infer")
+        if polygon_tolerance is not None:
+            from .mask_polygon import check_polygon_tolerance
+
+            check_polygon_tolerance(polygon_tolerance, mask_format, "infer")
         t0 = perf_counter()
         if isinstance(image, (str, os.PathLike)):
             from PIL import Image
 
             image = np.array(Image.open(image).convert("RGB"))
         if not annotate:
-            return self(image, threshold=threshold, mask_format=mask_format)
+            return self(image, threshold=threshold, mask_format=mask_format, polygon_tolerance=polygon_tolerance)
         imload = perf_counter() - t0
         res = self.infer_batch(image if isinstance(image, (Frame, FrameBatch)) else [image], threshold=threshold, annotate=True,
-                               mask_format=mask_format)[0]
+                               mask_format=mask_format, polygon_tolerance=polygon_tolerance)[0]
         res.latency.imload = round(imload, 3)
         return res
 

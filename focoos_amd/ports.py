@@ -77,6 +77,9 @@ class FocoosDet:
     attr_id: Optional[int] = field(default=None, kw_only=True)
     attr_label: Optional[str] = field(default=None, kw_only=True)
     attr_conf: Optional[float] = field(default=None, kw_only=True)
+    # set by mask_format="polygon" with a polygon_tolerance, aligned with ``polygons``: a simplified ring can lose its orientation, so whether
+    # it is a hole was decided on the traced ring.  Keyword-only, for the same reason
+    polygon_holes: Optional[List[bool]] = field(default=None, kw_only=True)
     keypoints: Optional[List[Tuple[int, int, float]]] = None
     # set by mask_format="polygon" (mask_polygon.py): every ring of the mask's boundary as a flat [x0, y0, x1, y1, ...] in frame pixels, holes too
     polygons: Optional[List[List[int]]] = None

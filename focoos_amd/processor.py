@@ -330,6 +330,7 @@ class MaskFormerProcessor(DETRProcessor):
     _rle_encoder = None                  # the MaskRleEncoder of the last "rle" call, reused while shape, device and capacity stay
     polygon_capacity: Optional[int] = None   # words per image of the mask_format="polygon" pool; None = mask_polygon.default_capacity (Q (4 W + 1))
     polygon_max_edges: Optional[int] = None  # boundary edges per image of its edge workspace; None = mask_polygon.default_max_edges (Q 2 (H + W))
+    polygon_tolerance: Optional[float] = None  # pixels; with it "polygon" also simplifies the rings on the device; None = every vertex
     _polygon_encoder = None                  # the MaskPolygonEncoder of the last "polygon" call, reused like _rle_encoder
     png_capacity: Optional[int] = None   # base64 quads per image of the mask_format="png_device" pool; None = mask_png.default_capacity
     _png_encoder = None                  # the MaskPngEncoder of the last "png_device" call, reused like _rle_encoder
@@ -483,17 +484,22 @@ class MaskFormerProcessor(DETRProcessor):
         return unpack_words(words.cpu().numpy()[..., :(W + 31) // 32], W).reshape(words.shape[0], H, W)      # rows may be padded with words
 
     def pack_detections(self, res, class_names: Sequence[str] = (), encode_masks: bool = True,
-                        mask_format: str = "png") -> List[FocoosDetections]:
+                        mask_format: str = "png", polygon_tolerance: Optional[float] = None) -> List[FocoosDetections]:
         """D2H of the packed device results (counts, scores, labels, boxes, bit-packed masks of the kept detections only),
         then the host tail of processor.py:270-303: trim to the box, PNG + base64.  ``mask_format``: "png" is that path; "rle" encodes the
         masks as uncompressed COCO RLE on the device (mask_rle.py, DESIGN 18: ``FocoosDet.rle`` is set, ``mask`` is None, no dense mask is
         copied or unpacked unless a slot overflowed the pool of ``self.rle_capacity`` counts per image); "polygon" traces the masks' boundaries
         on the device (mask_polygon.py, DESIGN 19: ``FocoosDet.polygons`` is set, ``mask`` and ``rle`` are None; ``self.polygon_capacity`` words per
         image); "png_device" writes the base64 PNG of every trimmed mask on the device (mask_png.py, DESIGN 28: ``FocoosDet.mask`` decodes to the
-        image "png" gives; ``self.png_capacity`` base64 quads per image); "none" is ``encode_masks=False``."""
+        image "png" gives; ``self.png_capacity`` base64 quads per image); "none" is ``encode_masks=False``.  ``polygon_tolerance`` (pixels;
+        None = ``self.polygon_tolerance``, which only "polygon" reads): the rings are simplified on the device behind the trace and
+        ``FocoosDet.polygon_holes`` is set beside ``polygons``; given with another format it raises ValueError."""
+        from .mask_polygon import check_polygon_tolerance
         from .mask_rle import check_mask_format
 
-        if check_mask_format(mask_format, what="pack_detections") in ("rle", "polygon", "png_device"):
+        check_mask_format(mask_format, what="pack_detections")
+        check_polygon_tolerance(polygon_tolerance, mask_format, "pack_detections")
+        if mask_format in ("rle", "polygon", "png_device"):
             from .mask_png import MaskPngEncoder
             from .mask_polygon import MaskPolygonEncoder
             from .mask_pool import encoder_for
@@ -506,11 +512,16 @@ class MaskFormerProcessor(DETRProcessor):
             else:
                 enc = self._polygon_encoder = encoder_for(MaskPolygonEncoder, self._polygon_encoder, res, self.polygon_capacity,
                                                           self.polygon_max_edges)
-            enc.encode(res)      # on the current stream, before the copies below wait for it
+            tol = (self.polygon_tolerance if polygon_tolerance is None else polygon_tolerance) if mask_format == "polygon" else None
+            if tol is None:
+                enc.encode(res)      # on the current stream, before the copies below wait for it
+            else:
+                enc.encode(res, tol)
             items, field = enc.fetch(), {"rle": "rle", "polygon": "polygons", "png_device": "mask"}[mask_format]      # the FocoosDet field an item goes to
+            fields = (lambda r: {field: r}) if tol is None else (lambda r: {"polygons": r[0], "polygon_holes": r[1]})
             s, l, b = res.det_scores.cpu().tolist(), res.det_labels.cpu().tolist(), res.det_boxes.cpu().tolist()
             return [FocoosDetections(detections=[
-                FocoosDet(bbox=b[i][j], conf=s[i][j], cls_id=l[i][j], label=class_names[l[i][j]] if class_names else None, **{field: r})
+                FocoosDet(bbox=b[i][j], conf=s[i][j], cls_id=l[i][j], label=class_names[l[i][j]] if class_names else None, **fields(r))
                 for j, r in enumerate(ri)]) for i, ri in enumerate(items)]
         encode_masks = encode_masks and mask_format != "none"
         n = res.det_count.cpu().tolist()

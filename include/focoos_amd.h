@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 29
+#define FX_ABI_VERSION 30
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -506,6 +506,46 @@ size_t fx_mask_polygon_workspace_bytes(int B, int Q, int H, int W, int max_edges
 int fx_mask_polygon_encode(const int32_t* mask_words, const int32_t* det_count, const int32_t* det_boxes, int B, int Q, int H, int W, int capacity,
                            int max_edges, int32_t* poly_len, int32_t* poly_off, int32_t* poly_pool, void* workspace, size_t workspace_bytes,
                            fx_stream_t stream);
+
+/* ---- Vertex simplification of the traced polygons on the device (ABI 30; csrc/mask_polygon.hip):
+ * FocoosModel.infer(mask_format="polygon", polygon_tolerance=...).  Input: poly_len, poly_off and poly_pool as fx_mask_polygon_encode left
+ * them, and det_count.
+ *
+ * Definition (Douglas-Peucker with two anchors; integers only, so the result is unique).  A ring has V >= 4 lattice vertices p_0 .. p_(V-1)
+ * in the tracer's order (p_0 is the leader's tail).  The tolerance is T = tol16 sixteenths of a pixel, 1 <= T <= 1024 (1/16 to 64 pixels).
+ *  - Anchors: a = 0 and b = the index that maximises |p_k - p_0|^2, the lowest on ties.  Both are kept; the ring is cut into the chains
+ *    (0, b) and (b, V), where index V means p_0 again.
+ *  - A chain (i, j) with interior i < k < j: if p_i != p_j, c_k = |cross(p_j - p_i, p_k - p_i)|, k* = the k with the largest c_k (the lowest
+ *    on ties), and k* is kept exactly when c_k*^2 > floor(T^2 |p_j - p_i|^2 / 256).  With H, W <= 32767: c < 2^32, c^2 < 2^63 and the right
+ *    side is below 2^52, so 64-bit integers hold everything.  If p_i == p_j (a traced ring can pass through one lattice point twice),
+ *    c_k = |p_k - p_i|^2 and k* is kept exactly when 256 c_k* > T^2.  A kept k* splits the chain into (i, k*) and (k*, j); a chain with no
+ *    interior, or whose k* is not kept, is finished.
+ *  - Never fewer than three vertices: if only a and b are kept when every chain is finished, the better of the two first-round candidates
+ *    k* of (0, b) and (b, V) is kept as well: the larger c, the lower index on ties (a rectilinear ring of positive area has one with c > 0).
+ *  - The result is the kept vertices in their original order: a slot keeps the number and order of its rings, every ring keeps p_0 first,
+ *    has at least 3 vertices, and its vertices are a subsequence of the original's.
+ *  - The hole bit is decided on the ORIGINAL ring (shoelace sum < 0, in int64): a simplified ring's own area can flip sign or vanish.
+ *
+ * Output, all int32.  A slot's stream is, for each ring in order, V' | hole << 31 and then the V' kept vertices x | y << 16.
+ *  - out_len [B][Q]: the simplified stream's length; 0 for an empty slot (poly_len = 0 below det_count); -1 for a slot whose input stream was
+ *    not stored (poly_len < 0, poly_off + poly_len > capacity, a slot >= clamp(det_count[b], 0, Q)) or is no sequence of rings of >= 4
+ *    vertices;
+ *  - out_off [B][Q]: the exclusive prefix sum of max(out_len, 0) over the slots of the image;
+ *  - out_pool [B][capacity] (not poly_pool): the stream of slot j at [b][out_off .. out_off + out_len) iff out_len > 0 - it always fits, a
+ *    simplified stream being no longer than its input; no other element is ever written.
+ * Two launches.  simplify: one workgroup per slot works on all its rings at once - pointer doubling over the header chain finds the rings,
+ * a 64-bit max per ring the anchor b, then level-synchronous rounds: every open vertex adds c_k << 32 | ~k to the 64-bit max of its chain,
+ * reads the winner, applies the threshold and re-points its chain; the loop ends when a round keeps nothing, its trip count is fixed at the
+ * slot's largest V.  A block scan ranks the kept vertices and sums the shoelace terms; the stream goes to a staging pool.  The state (28
+ * bytes per word) is held in LDS for a stream of up to 5120 words and in the workspace above that.  place: out_off, and the copy from the
+ * staging pool.  The keys are integer maxima, everything else plain stores: the output is a pure function of the input.
+ * workspace: fx_mask_polygon_simplify_workspace_bytes(B, Q, capacity) = 28 B capacity + 8 bytes, 0 outside the limits; 4-byte aligned,
+ * contents irrelevant.  Limits: 1 <= B, Q <= 65535, capacity >= 1, 1 <= tol16 <= 1024.  Null or misaligned pointers, a short workspace or
+ * anything else outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched, nothing written.  The same in both libraries. */
+size_t fx_mask_polygon_simplify_workspace_bytes(int B, int Q, int capacity);
+int fx_mask_polygon_simplify(const int32_t* poly_len, const int32_t* poly_off, const int32_t* poly_pool, const int32_t* det_count, int B, int Q,
+                             int capacity, int tol16, int32_t* out_len, int32_t* out_off, int32_t* out_pool, void* workspace, size_t workspace_bytes,
+                             fx_stream_t stream);
 
 /* ---- Base64 PNG of the kept masks on the device (ABI 28; csrc/mask_png.hip):
  * FocoosModel.infer(mask_format="png_device").  Input: exactly that of fx_mask_rle_encode (mask_words, det_count, det_boxes; the words and box

@@ -9,6 +9,9 @@ Reports, as one JSON line:
   * device-to-host bytes per batch of pack_detections for "polygon", "rle" and the host path (computed from what each path copies);
   * host wall time per batch, the three alternating in one process (median, min and max over --reps): pack_detections with "polygon", with
     "rle", and the host path a user had before - the bit planes copied back, unpack_masks and trace_mask_numpy per detection.
+With --tolerance PIXELS the line also carries "simplify": the vertices before and after, last_d2h_bytes before and
+after, fx_mask_polygon_simplify by HIP events next to the encode's, and the wall time per batch of infer_stream's tail (pack_detections
+with "polygon") with and without the tolerance.
 One run, no gate: nothing depends on these figures."""
 from __future__ import annotations
 
@@ -47,6 +50,44 @@ def bench_kernel(res, reps, dev):
     return stats([e0.elapsed_time(e1) for e0, e1 in ev], 4), enc, polys, {
         "masks": len(verts), "vertices_per_mask_mean": round(float(np.mean(verts)), 1), "vertices_per_mask_max": int(max(verts)),
         "rings_per_mask_max": int(max(rings)), "fell_back": enc.last_fallback}
+
+
+def bench_simplify(res, tol, reps, wall_reps, dev):
+    """the simplify call alone by HIP events (the encode before it outside the interval), the bytes copied back, and pack_detections' wall"""
+    from focoos_amd.processor import MaskFormerProcessor
+    from focoos_amd.registry import ModelRegistry
+
+    enc = MaskPolygonEncoder(B, Q, H, W, dev)
+    enc.encode(res)
+    plain = enc.fetch()
+    before = enc.last_d2h_bytes
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps + 5)]
+    for e0, e1 in ev:      # encode + simplify; the first five warm up
+        enc.encode(res, tol)
+    torch.cuda.synchronize()
+    for e0, e1 in ev:
+        e0.record()
+        enc.lib.fx_mask_polygon_simplify(enc.meta[0].data_ptr(), enc.meta[1].data_ptr(), enc.pool.data_ptr(), res.det_count.data_ptr(), B, Q,
+                                         enc.capacity, enc.tol16, enc.out_meta[0].data_ptr(), enc.out_meta[1].data_ptr(), enc.out_pool.data_ptr(),
+                                         enc.simplify_workspace.data_ptr(), enc.simplify_workspace.numel(),
+                                         torch.cuda.current_stream(dev).cuda_stream)
+        e1.record()
+    torch.cuda.synchronize()
+    simple = enc.fetch()
+    proc = MaskFormerProcessor(ModelRegistry.get_model_info("fai-mf-l-coco-ins")["config"])
+    names = [str(i) for i in range(80)]
+    wall = {"polygon": [], "polygon_tolerance": []}
+    for rep in range(wall_reps + 1):
+        for k in wall:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            proc.pack_detections(res, names, mask_format="polygon", polygon_tolerance=tol if k == "polygon_tolerance" else None)
+            if rep:
+                wall[k].append((time.perf_counter() - t0) * 1e3)
+    count = lambda polys: sum(len(r) // 2 for img in polys for p in img for r in (p[0] if isinstance(p, tuple) else p))      # noqa: E731
+    return {"tolerance": tol, "vertices_before": count(plain), "vertices_after": count(simple), "d2h_bytes_before": before,
+            "d2h_bytes_after": enc.last_d2h_bytes, "fell_back": enc.last_fallback,
+            "simplify_ms_per_batch_hip_events": stats([e0.elapsed_time(e1) for e0, e1 in ev[5:]], 4), "pack_ms_per_batch": {k: stats(v) for k, v in wall.items()}}
 
 
 def host_path(proc, res):
@@ -90,6 +131,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--kernel-reps", type=int, default=50)
     ap.add_argument("--kernels-only", type=int, default=0)
+    ap.add_argument("--tolerance", type=float, default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_mask_polygon needs a GPU (no CPU fallback, no figure without one)")
@@ -108,6 +150,8 @@ def main():
     out = {"bench": "mask_polygon", "scene": f"{B} images {H} x {W}, {OBJECTS} filled ellipses each (semi-axes 30..150), Q = {Q} slots, tight boxes",
            "capacity_per_image": enc.capacity, "max_edges_per_image": enc.max_edges, "workspace_bytes": int(enc.workspace.numel()), **shape,
            "encode_ms_per_batch_hip_events": kern, "d2h_bytes_per_batch": d2h, "ms_per_batch": wall}
+    if a.tolerance is not None:
+        out["simplify"] = bench_simplify(res, a.tolerance, a.kernel_reps, a.reps, dev)
     print(json.dumps(out))
 
 
