@@ -168,6 +168,8 @@ SIGNATURES = {
     "fx_mask_polygon_encode": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "fx_mask_polygon_simplify_workspace_bytes": [_i, _i, _i],
     "fx_mask_polygon_simplify": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
+    "fx_mask_components_workspace_bytes": [_i, _i, _i, _i, _i, _i],
+    "fx_mask_components": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, C.c_size_t, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fx_mask_png_workspace_bytes": [_i, _i, _i, _i],
     "fx_mask_png_encode": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
     "fx_maxpool3x3s2_nhwc_bf16": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
@@ -345,7 +347,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 30  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 31  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:
@@ -380,6 +382,7 @@ def load(name: str = None) -> C.CDLL:
     lib.fx_mask_rle_workspace_bytes.restype = C.c_size_t
     lib.fx_mask_polygon_workspace_bytes.restype = C.c_size_t
     lib.fx_mask_polygon_simplify_workspace_bytes.restype = C.c_size_t
+    lib.fx_mask_components_workspace_bytes.restype = C.c_size_t
     lib.fx_mask_png_workspace_bytes.restype = C.c_size_t
     lib.fx_seg_merge_workspace_bytes.restype = C.c_size_t
     lib.fx_error_string.argtypes = [C.c_int]

@@ -22,7 +22,8 @@ class StreamAnalytics:
     """The analytics state of one call.  ``track`` / ``zones`` / ``dwell`` / ``heatmap`` / ``classify`` hold what ``resolve`` made of the
     arguments - None, a validated config, or a device object - and, from the first ``prepare`` on, device objects only."""
 
-    def __init__(self, fm, what: str, annotate, detections: bool, tiling, mask_format: str, threshold, polygon_tolerance=None):
+    def __init__(self, fm, what: str, annotate, detections: bool, tiling, mask_format: str, threshold, polygon_tolerance=None,
+                 components=None):
         self.fm = fm                      # the FocoosModel
         self.what = what                  # "infer_batch" / "infer_stream": the prefix of the messages
         self.annotate = annotate          # the argument: False, True or an Overlay
@@ -39,10 +40,12 @@ class StreamAnalytics:
         self.overlay = None               # the Overlay of ``annotate``, None for True / False
         self.traces = None                # the overlay's DeviceTraces
         self.ids = None                   # the track ids of the batch ``analyse`` saw last, which ``draw`` reads
+        self.components = components      # the validated Components, or None
+        self.split = None                 # the split result of the batch ``analyse`` saw last, which ``draw`` reads in the plan's place
 
     @classmethod
     def resolve(cls, fm, what: str, *, device_only: bool, track, zones, dwell, heatmap, annotate, classify, tiling, detections: bool,
-                mask_format: str, threshold=None, polygon_tolerance=None) -> "StreamAnalytics":
+                mask_format: str, threshold=None, polygon_tolerance=None, components=None) -> "StreamAnalytics":
         """Every argument check of the entry points, in one order, on the host: nothing is loaded or launched.  ``device_only``
         (``infer_batch``, which sees one batch per call): only a DeviceTracker, DeviceZones, DeviceDwell, DeviceHeatmap, DeviceCascade and
         DeviceTraces are taken, whose state outlives the call.  ``what`` is the prefix of the messages."""
@@ -53,6 +56,11 @@ class StreamAnalytics:
             from .mask_polygon import check_polygon_tolerance
 
             check_polygon_tolerance(polygon_tolerance, mask_format, what)
+        if components is not None:
+            from . import components as CC
+
+            consumed = bool(annotate) or any(a is not None for a in (track, zones, dwell, heatmap, classify))
+            components = CC.check(components, fam, fm.model_info.classes, mask_format, detections, consumed, what)
         if tiling is not None:
             from . import tiled as TL
 
@@ -74,7 +82,7 @@ class StreamAnalytics:
             from . import heat as HM
 
             heatmap = HM.resolve(heatmap, track is not None, fam, what, device_only)
-        an = cls(fm, what, annotate, detections, tiling, mask_format, threshold, polygon_tolerance)
+        an = cls(fm, what, annotate, detections, tiling, mask_format, threshold, polygon_tolerance, components)
         an.track, an.zones, an.dwell, an.heatmap, an.classify = track, zones, dwell, heatmap, classify
         if annotate:
             an.overlay = check_overlay(annotate, track is not None, zones is not None, fam, what, heatmap is not None, fm, device_only)
@@ -149,6 +157,13 @@ class StreamAnalytics:
         fm, fam = self.fm, self.fm.model.family
         track, zones, dwell, classify, names = self.track, self.zones, self.dwell, self.classify, fm.model_info.classes
         ids = None
+        if self.components is not None:      # first of all: everything below then reads one slot per connected component
+            from . import components as CC
+
+            proc = fm.processor
+            proc._components = CC.splitter_for(proc._components, pl, self.components,
+                                               CC.split_table(self.components.classes, names, self.what), proc.components_run_capacity)
+            pl = self.split = proc._components.split(pl)
         if track is not None:      # one launch on the packed device results; the ids come back beside the packed copy
             ids = track.update(pl.det_scores, pl.det_labels, pl.det_boxes, pl.det_count)
         if zones is not None:      # one more launch, right after the tracker's, on the same packed results
@@ -186,7 +201,7 @@ class StreamAnalytics:
         ov = self.overlay
         ovl = None if ov is None else OverlayPass(ov, self.ids, self.zones if ov.zones else None, self.traces, self.heatmap if ov.heat else None,
                                                   self.track if ov.redact is not None and ov.redact.hold > 0 else None)
-        annotate_results(self.fm, *drawn, pl, out, ovl)
+        annotate_results(self.fm, *drawn, pl if self.split is None else self.split, out, ovl)
 
     def close(self) -> None:
         """The once-per-call warnings: births dropped for want of a free slot, eligible objects left out for want of crop budget."""

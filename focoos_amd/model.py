@@ -284,7 +284,7 @@ class FocoosModel:
 
     def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate=False, tracker=None,
                     mask_format: str = "png", zones=None, dwell=None, heatmap=None, tiling=None, classify=None,
-                    polygon_tolerance: Optional[float] = None) -> List[FocoosDetections]:
+                    polygon_tolerance: Optional[float] = None, components=None) -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
         reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``inputs`` may also be a
         ``frames.FrameBatch`` of NV12 / I420 / BGR / RGB video frames, host or device: the results are those of the same frames passed as
@@ -319,13 +319,22 @@ class FocoosModel:
         ``polygon_tolerance`` (pixels, in (0, 64]; overrides ``processor.polygon_tolerance`` for this call): with ``mask_format="polygon"``
         the traced rings are simplified on the device (Douglas-Peucker in exact integers; mask_polygon.py), only the simplified
         streams come back, and every detection also carries ``polygon_holes``; with another format, or a value outside the range or
-        below 1 / 32, ValueError before anything touches the GPU."""
+        below 1 / 32, ValueError before anything touches the GPU.
+        ``components``: None, True (the defaults) or a ``components.Components(connectivity, min_area, max_components, classes)`` - the
+        masks of the packed result are split into their connected components on the device before anything else reads it
+        (fx_mask_components; components.py): every ``FocoosDet`` is one component - ``bbox`` its tight box, ``conf`` and
+        ``cls_id`` those of the mask it came from, the mask its own pixels - ordered by source mask, then by first pixel; the tracker, the
+        zones, the dwell times, the heat map, the cascade, the overlay and redaction and every ``mask_format`` see components.  Masks of
+        classes outside ``Components.classes`` pass through whole; components below ``min_area`` pixels are dropped silently, those
+        beyond ``max_components`` per image with a warning.  Mask families only (NotImplementedError otherwise); anything but None, True
+        or a Components TypeError; a value outside the contract, an unknown class, or ``mask_format="none"`` with nothing that reads the
+        components ValueError - all before anything touches the GPU.  With None nothing changes."""
         from .analytics import StreamAnalytics, batch_size
         from .frames import drawable
 
         an = StreamAnalytics.resolve(self, "infer_batch", device_only=True, track=tracker, zones=zones, dwell=dwell, heatmap=heatmap,
                                      annotate=annotate, classify=classify, tiling=tiling, detections=True, mask_format=mask_format,
-                                     threshold=threshold, polygon_tolerance=polygon_tolerance)
+                                     threshold=threshold, polygon_tolerance=polygon_tolerance, components=components)
         inputs = an.frames(inputs)      # a FrameBatch (or one Frame) goes where a list of images goes (frames.py, DESIGN 21)
         an.prepare(inputs, batch_size(inputs))
         t0 = perf_counter()
@@ -357,7 +366,7 @@ class FocoosModel:
 
     def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate=False, track=None,
                      mask_format: str = "png", zones=None, detections: bool = True, dwell=None, heatmap=None, tiling=None, classify=None,
-                     polygon_tolerance: Optional[float] = None):
+                     polygon_tolerance: Optional[float] = None, components=None):
         """Throughput inference (round 6): iterate over ``batches`` (each a list of images of ONE common shape after preprocessing and one
         batch size) and yield each batch's ``List[FocoosDetections]`` in order, with up to ``depth`` batches in flight on the engine's
         pipeline (engine.pipeline(): batch i+1's backbone runs beside batch i's decoder tail; default depth 3).  Same results as
@@ -419,7 +428,9 @@ class FocoosModel:
         a Cascade / DeviceCascade TypeError; a classifier on another device, non-uint8 inputs, ``detections=False``, ``interval > 1`` or
         ``hold="best"`` without ``track``, or more than 65535 crops per batch ValueError - all before anything touches the GPU; eligible
         objects left out for want of crop budget warn once per call.  With ``None`` nothing changes.
-        ``polygon_tolerance``: as in ``infer_batch``; the simplify call follows each batch's trace on the current stream."""
+        ``polygon_tolerance``: as in ``infer_batch``; the simplify call follows each batch's trace on the current stream.
+        ``components``: as in ``infer_batch``; each batch is split after its lane finished, in front of the tracker, and one splitter
+        serves every lane (batches finish in order on the current stream)."""
         from collections import deque
         from types import SimpleNamespace
 
@@ -428,7 +439,7 @@ class FocoosModel:
 
         an = StreamAnalytics.resolve(self, "infer_stream", device_only=False, track=track, zones=zones, dwell=dwell, heatmap=heatmap,
                                      annotate=annotate, classify=classify, tiling=tiling, detections=detections, mask_format=mask_format,
-                                     threshold=threshold, polygon_tolerance=polygon_tolerance)
+                                     threshold=threshold, polygon_tolerance=polygon_tolerance, components=components)
         if tiling is not None:      # the same tail on the merged result of every frame batch, in the tiler's own loop (tiled.py)
             from . import tiled as TL
 
@@ -478,13 +489,13 @@ class FocoosModel:
 
         lst = as_frame_batch(inputs) or (inputs if isinstance(inputs, list) else [inputs])
         return self.infer_batch(lst, threshold=kwargs.get("threshold"), mask_format=kwargs.get("mask_format", "png"),
-                                polygon_tolerance=kwargs.get("polygon_tolerance"))[0]
+                                polygon_tolerance=kwargs.get("polygon_tolerance"), components=kwargs.get("components"))[0]
 
     def infer(self, image, threshold: Optional[float] = None, annotate: bool = False, mask_format: str = "png",
-              polygon_tolerance: Optional[float] = None) -> FocoosDetections:
+              polygon_tolerance: Optional[float] = None, components=None) -> FocoosDetections:
         """focoos_model.py:370-416: one picture (path, PIL image, array, tensor) -> FocoosDetections.  ``annotate``: ``.image`` is the
         picture (np.uint8 [H, W, 3] RGB, original size) with the detections drawn on it on the device (annotate.py; the input itself
-        when nothing was detected) and ``.latency.annotate`` / ``.latency.imload`` are set.  ``mask_format`` and ``polygon_tolerance``: as in ``infer_batch``.
+        when nothing was detected) and ``.latency.annotate`` / ``.latency.imload`` are set.  ``mask_format``, ``polygon_tolerance`` and ``components``: as in ``infer_batch``.
         ``image`` may also be a ``frames.Frame`` (NV12, I420, BGR or RGB video frame, host or device)."""
         from .frames import Frame, FrameBatch
         from .mask_rle import check_mask_format
@@ -498,16 +509,20 @@ class FocoosModel:
             from .mask_polygon import check_polygon_tolerance
 
             check_polygon_tolerance(polygon_tolerance, mask_format, "infer")
+        if components is not None:
+            from .components import check as check_components
+
+            check_components(components, self.model.family, self.model_info.classes, mask_format, True, bool(annotate), "infer")
         t0 = perf_counter()
         if isinstance(image, (str, os.PathLike)):
             from PIL import Image
 
             image = np.array(Image.open(image).convert("RGB"))
         if not annotate:
-            return self(image, threshold=threshold, mask_format=mask_format, polygon_tolerance=polygon_tolerance)
+            return self(image, threshold=threshold, mask_format=mask_format, polygon_tolerance=polygon_tolerance, components=components)
         imload = perf_counter() - t0
         res = self.infer_batch(image if isinstance(image, (Frame, FrameBatch)) else [image], threshold=threshold, annotate=True,
-                               mask_format=mask_format, polygon_tolerance=polygon_tolerance)[0]
+                               mask_format=mask_format, polygon_tolerance=polygon_tolerance, components=components)[0]
         res.latency.imload = round(imload, 3)
         return res
 
@@ -546,7 +561,7 @@ class FocoosModel:
 
     def segment_tiled(self, image, tile: Optional[int] = None, overlap: float = 0.2, threshold: Optional[float] = None,
                       batch_size: Optional[int] = None, max_classes: Optional[int] = None, mask_format: str = "png", annotate: bool = False,
-                      return_label_map: bool = False):
+                      return_label_map: bool = False, components=None):
         """Tiled semantic segmentation of ONE large picture (an engine-native mode like ``infer_tiled``; the reference has none): ``image``
         (what ``infer_tiled`` takes) is cut into the overlapping windows of ``tiled.tile_grid`` for a square ``tile`` (a multiple of 32,
         default ``model_info.im_size``) and ``overlap`` in [0, 0.5]; the views run through the engine in chunks of ``batch_size`` (default
@@ -558,7 +573,8 @@ class FocoosModel:
         pixel and ``conf > threshold`` (default: the processor's; ``<= 0`` keeps all).  ``max_classes`` (default ``num_classes``) mask
         planes of ``Hf * ceil(Wf / 32) * 4`` bytes each are allocated; kept classes beyond them, in ascending class id, are dropped with
         a warning.  ``return_label_map``: the result is the pair ``(detections, label_map)``, ``label_map`` the uint8 [Hf, Wf] numpy array of class ids.  ``annotate``: ``.image`` is the frame
-        with the classes drawn on it.  bisenetformer with ``predict_all_pixels`` only: every other family or configuration raises
+        with the classes drawn on it.  ``components``: as in ``infer_batch`` - the merged class masks are split into their connected components
+        behind the merge, and the detections, the encoders and the drawing see one ``FocoosDet`` per component.  bisenetformer with ``predict_all_pixels`` only: every other family or configuration raises
         NotImplementedError before anything touches the GPU, bad arguments and frames ValueError."""
         from .frames import refuse_frames
 
@@ -569,7 +585,7 @@ class FocoosModel:
             refuse_overlay(annotate, "segment_tiled")
         from .tiled_seg import segment_tiled as _segment_tiled
 
-        return _segment_tiled(self, image, tile, overlap, threshold, batch_size, max_classes, mask_format, annotate, return_label_map)
+        return _segment_tiled(self, image, tile, overlap, threshold, batch_size, max_classes, mask_format, annotate, return_label_map, components)
 
     def train(self, args, data_train, data_val=None, hub=None):
         """focoos_model.py:221-274: fine-tune on ``data_train`` (indexable, entries = ports.DatasetEntry) with ``args`` (ports.TrainerArgs):

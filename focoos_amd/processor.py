@@ -334,6 +334,8 @@ class MaskFormerProcessor(DETRProcessor):
     _polygon_encoder = None                  # the MaskPolygonEncoder of the last "polygon" call, reused like _rle_encoder
     png_capacity: Optional[int] = None   # base64 quads per image of the mask_format="png_device" pool; None = mask_png.default_capacity
     _png_encoder = None                  # the MaskPngEncoder of the last "png_device" call, reused like _rle_encoder
+    components_run_capacity: Optional[int] = None   # runs per image of the components= run pool; None = components.default_run_capacity (64 H)
+    _components = None                   # the DeviceComponents of the last components= call, reused while shape, device and configuration stay
 
     def __init__(self, config: dict, image_size=None):
         super().__init__(config, None)

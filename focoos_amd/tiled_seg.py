@@ -99,7 +99,7 @@ def merge_views(lib, mask_probs: torch.Tensor, score: torch.Tensor, label: torch
 
 def segment_tiled(fm, image, tile: Optional[int] = None, overlap: float = 0.2, threshold: Optional[float] = None,
                   batch_size: Optional[int] = None, max_classes: Optional[int] = None, mask_format: str = "png", annotate: bool = False,
-                  return_label_map: bool = False):
+                  return_label_map: bool = False, components=None):
     """FocoosModel.segment_tiled (see there)."""
     from ._lib import load
     from .mask_rle import check_mask_format
@@ -107,6 +107,10 @@ def segment_tiled(fm, image, tile: Optional[int] = None, overlap: float = 0.2, t
 
     check_supported(fm)
     check_mask_format(mask_format, fm.model.family, "segment_tiled")
+    if components is not None:
+        from . import components as CC
+
+        components = CC.check(components, fm.model.family, fm.model_info.classes, mask_format, True, bool(annotate), "segment_tiled")
     K = int(fm.model_info.config["num_classes"])
     t, M = check_arguments(tile, overlap, batch_size, max_classes, fm.model_info.im_size, K)
     t0 = perf_counter()
@@ -127,7 +131,12 @@ def segment_tiled(fm, image, tile: Optional[int] = None, overlap: float = 0.2, t
     gather_views(lib, frame_d, wins_h, wins_d, views)
     t1 = perf_counter()
     probs, score, label = segment_views(fm.model, views, bs)
-    res = merge_views(lib, probs, score, label, wins_h, wins_d, (H, W), K, thr, M)
+    res = merged = merge_views(lib, probs, score, label, wins_h, wins_d, (H, W), K, thr, M)
+    if components is not None:      # behind the merge: one slot per connected component of every class mask; cached like the encoders below
+        fm._tiled_seg_components = CC.splitter_for(getattr(fm, "_tiled_seg_components", None), res, components,
+                                                   CC.split_table(components.classes, fm.model_info.classes, "segment_tiled"),
+                                                   fm.processor.components_run_capacity)
+        res = fm._tiled_seg_components.split(res)
     torch.cuda.current_stream(dev).synchronize()
     t2 = perf_counter()
     # the device mask encoders are cached per shape on the processor: the frame-shaped ones live on the model, so that a caller who
@@ -142,11 +151,11 @@ def segment_tiled(fm, image, tile: Optional[int] = None, overlap: float = 0.2, t
         fm._tiled_seg_encoders = [getattr(proc, n) for n in names]
         for n, enc in zip(names, theirs):
             setattr(proc, n, enc)
-    dropped = int(res.status.item())
+    dropped = int(merged.status.item())
     if dropped:
         warnings.warn(f"segment_tiled: {dropped} classes present in the frame found no mask plane (max_classes = {M}; classes take the "
                       "planes in ascending class id): raise max_classes")
-    label_map = res.label_map.cpu().numpy() if return_label_map else None
+    label_map = merged.label_map.cpu().numpy() if return_label_map else None
     t3 = perf_counter()
     if annotate:       # the frame is resident: draw the merged classes on it (a caller's own device tensor stays untouched)
         from .annotate import annotate_results

@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 30
+#define FX_ABI_VERSION 31
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -546,6 +546,53 @@ size_t fx_mask_polygon_simplify_workspace_bytes(int B, int Q, int capacity);
 int fx_mask_polygon_simplify(const int32_t* poly_len, const int32_t* poly_off, const int32_t* poly_pool, const int32_t* det_count, int B, int Q,
                              int capacity, int tol16, int32_t* out_len, int32_t* out_off, int32_t* out_pool, void* workspace, size_t workspace_bytes,
                              fx_stream_t stream);
+
+/* ---- Connected components of the kept masks on the device (ABI 31; csrc/mask_components.hip):
+ * FocoosModel.infer(components=...).  Input: the packed results as fx_mask_rle_encode reads them (mask_words, det_count, det_boxes; the
+ * words and box of a slot >= clamp(det_count[b], 0, Q) are never read, bits at x >= W are zero) and, of the same slots, det_scores f32
+ * [B][Q] and det_labels i32 [B][Q].  The box only bounds the work: rows y0 .. y1 (clamped to the frame) are read and every other row counts
+ * as unset, so a tight box and the full frame give the same result for a mask that lies inside its box.
+ *
+ * Definition.  A component of slot j is a maximal set of set pixels of its mask that is connected under `connectivity`: 4 (a pixel touches
+ * the pixels left, right, above and below it) or 8 (the diagonal ones too).  With split_class (u8 [K], or null: every class is split) a slot
+ * whose label l has 0 <= l < K and split_class[l] == 0 is ONE component - all its pixels - provided it has any; a label outside 0 .. K - 1 is
+ * split.  The components of an image are ordered by source slot ascending, then by the raster index y W + x of their first pixel
+ * ascending (scipy.ndimage.label's order within a mask).  A component with fewer than min_area pixels takes no slot and is counted
+ * nowhere; of the rest, `total` per image, the first M take the output slots 0 .. M - 1.
+ *
+ * Output (the packed layout again, M slots per image):
+ *  - out_count i32 [B] = min(total, M); status i32 [B][2]: status[b][0] = total - out_count[b], status[b][1] = 1 when the run pool
+ *    overflowed (below), else 0;
+ *  - per output slot k < out_count[b]: out_area i32 [B][M] = the component's pixels; out_boxes i32 [B][M][4] = their inclusive extent (x0,
+ *    y0, x1, y1); out_scores f32 [B][M] and out_labels i32 [B][M] = those of the source slot, bit for bit; out_source i32 [B][M] = j.  The
+ *    records at or beyond out_count[b] are not written;
+ *  - out_mask_words u32 [B][M][H][ceil(W / 32)]: plane k < out_count[b] holds exactly the component's pixels, every other plane is zero.
+ * Run pool.  A run is a maximal horizontal stretch of set pixels of one row of one slot; an image's runs are numbered by (slot, row, x).
+ * An image with more than run_capacity runs gets status[b][1] = 1 and out_count[b] = 0, its planes are zero and nothing else of it is
+ * defined; the other images are not affected.
+ * Six launches.  clear: the planes.  count: a group of lanes per (slot, row), a lane per word - the run starts of a word are
+ * w & ~(w << 1 | carry), a scan inside the group gives the starts before each word.  scan: one workgroup per image - the exclusive scan of
+ * the row counts over (slot, row), the slots' first runs and totals, the overflow flag.  label: one workgroup per slot - writes the runs
+ * (x0 | x1 << 16), links every run to the runs of the row above that it touches (binary search, then a walk) in a lock-free union-find
+ * (find with path halving, union by atomicMin of the larger root under the smaller: the final root is the component's first run whatever the
+ * order), flattens, and collects area and box per root with integer atomics; the state lives in LDS for a slot of up to 5120 runs (140 KB)
+ * and in the workspace above that (FX_COMPONENTS_LDS_RUNS = 0 .. 5120 lowers the threshold: a test's knob).  select: one workgroup per
+ * image - flags the roots with area >= min_area, scans them in run order (the order defined above), writes the records, out_count, status
+ * and the table run -> output slot.  emit: the tiling of count again - a lane walks the segments of its word, maps each to run, root and
+ * output slot and stores whole words; only lane (j, y, word) writes word (y, word) of a plane whose source is j.  No locks, no waiting
+ * between workgroups, every loop is bounded (parents only decrease); integer atomics are exact in any order: the output is a pure function of
+ * the input.
+ * workspace: fx_mask_components_workspace_bytes(B, Q, H, W, M, run_capacity) = 4 (B Q H + 2 B Q + 2 B + 8 B run_capacity) bytes, 0 outside
+ * the limits; 4-byte aligned, contents irrelevant.
+ * Limits: 1 <= B, Q <= 65535, H, W >= 1, H W < 2^31, W <= 65535, 1 <= M <= 4096, 1 <= run_capacity <= 2^27, connectivity 4 or 8, min_area
+ * >= 1, K >= 0 (K >= 1 with split_class).  Null or misaligned pointers (split_class is a byte array and may be null), a short workspace or
+ * anything else outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched or written.  The same in both libraries. */
+size_t fx_mask_components_workspace_bytes(int B, int Q, int H, int W, int M, int run_capacity);
+int fx_mask_components(const int32_t* mask_words, const int32_t* det_count, const float* det_scores, const int32_t* det_labels,
+                       const int32_t* det_boxes, int B, int Q, int H, int W, int connectivity, int min_area, const uint8_t* split_class, int K,
+                       int M, int run_capacity, void* workspace, size_t workspace_bytes, int32_t* out_count, float* out_scores,
+                       int32_t* out_labels, int32_t* out_boxes, int32_t* out_area, int32_t* out_source, uint32_t* out_mask_words, int32_t* status,
+                       fx_stream_t stream);
 
 /* ---- Base64 PNG of the kept masks on the device (ABI 28; csrc/mask_png.hip):
  * FocoosModel.infer(mask_format="png_device").  Input: exactly that of fx_mask_rle_encode (mask_words, det_count, det_boxes; the words and box
