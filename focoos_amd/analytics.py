@@ -42,14 +42,18 @@ class StreamAnalytics:
         self.ids = None                   # the track ids of the batch ``analyse`` saw last, which ``draw`` reads
         self.components = components      # the validated Components, or None
         self.split = None                 # the split result of the batch ``analyse`` saw last, which ``draw`` reads in the plan's place
+        self.image_format = None          # what ``.image`` becomes: None (the array) or (Jpeg, base64?) of jpeg.check_image_format
 
     @classmethod
     def resolve(cls, fm, what: str, *, device_only: bool, track, zones, dwell, heatmap, annotate, classify, tiling, detections: bool,
-                mask_format: str, threshold=None, polygon_tolerance=None, components=None) -> "StreamAnalytics":
+                mask_format: str, threshold=None, polygon_tolerance=None, components=None, image_format="array") -> "StreamAnalytics":
         """Every argument check of the entry points, in one order, on the host: nothing is loaded or launched.  ``device_only``
         (``infer_batch``, which sees one batch per call): only a DeviceTracker, DeviceZones, DeviceDwell, DeviceHeatmap, DeviceCascade and
         DeviceTraces are taken, whose state outlives the call.  ``what`` is the prefix of the messages."""
+        from .jpeg import check_image_format
+
         fam = fm.model.family
+        image_format = check_image_format(image_format, annotate, what)
         Z.check_detections_flag(detections, zones, annotate, mask_format, what)
         check_mask_format(mask_format, fam, what)
         if polygon_tolerance is not None:
@@ -84,6 +88,7 @@ class StreamAnalytics:
             heatmap = HM.resolve(heatmap, track is not None, fam, what, device_only)
         an = cls(fm, what, annotate, detections, tiling, mask_format, threshold, polygon_tolerance, components)
         an.track, an.zones, an.dwell, an.heatmap, an.classify = track, zones, dwell, heatmap, classify
+        an.image_format = image_format
         if annotate:
             an.overlay = check_overlay(annotate, track is not None, zones is not None, fam, what, heatmap is not None, fm, device_only)
         if an.overlay is not None and isinstance(an.overlay.traces, DeviceTraces):
@@ -201,7 +206,7 @@ class StreamAnalytics:
         ov = self.overlay
         ovl = None if ov is None else OverlayPass(ov, self.ids, self.zones if ov.zones else None, self.traces, self.heatmap if ov.heat else None,
                                                   self.track if ov.redact is not None and ov.redact.hold > 0 else None)
-        annotate_results(self.fm, *drawn, pl if self.split is None else self.split, out, ovl)
+        annotate_results(self.fm, *drawn, pl if self.split is None else self.split, out, ovl, self.image_format)
 
     def close(self) -> None:
         """The once-per-call warnings: births dropped for want of a free slot, eligible objects left out for want of crop budget."""

@@ -649,12 +649,23 @@ def to_host(frames: torch.Tensor) -> np.ndarray:
     return host.numpy().copy()
 
 
-def annotate_results(fm, inputs, images: torch.Tensor, results, out: list, overlay: Optional[OverlayPass] = None) -> None:
+def images_to_host(frames: torch.Tensor, image_format=None) -> Sequence:
+    """What ``.image`` holds for each of the drawn device frames: the rows of ``to_host`` (``image_format`` None, "array"), or the JPEG
+    files the device encodes (``image_format`` = what ``jpeg.check_image_format`` returned; jpeg.py)."""
+    if image_format is None:
+        return to_host(frames)
+    from .jpeg import images_to_host as jpeg_to_host
+
+    return jpeg_to_host(frames, image_format)
+
+
+def annotate_results(fm, inputs, images: torch.Tensor, results, out: list, overlay: Optional[OverlayPass] = None, image_format=None) -> None:
     """Set ``out[i].image`` (np.uint8 [H, W, 3] at the ORIGINAL size of input i) for one batch: ``images`` is what preprocess returned,
     ``results`` the plan holding the packed device results (ignored for classification, drawn from ``out``'s detections).  When
     preprocess took the uint8 same-size fast path the batch itself is drawn on; otherwise every original goes up once (the boxes are in
     original pixels already) and each run of equal-size images is one kernel call with its ``b0``.  One pinned copy back per call.
-    ``overlay``: the layers of an ``Overlay`` as well (``annotate_overlay``); None draws exactly what ``annotate=True`` always drew."""
+    ``overlay``: the layers of an ``Overlay`` as well (``annotate_overlay``); None draws exactly what ``annotate=True`` always drew.
+    ``image_format``: None, or what ``jpeg.check_image_format`` returned - ``.image`` is then the frame's JPEG file, encoded on the device."""
     ann = annotator_of(fm)
     lst = inputs if isinstance(inputs, list) else [inputs]
     cls = fm.model.family == "fai_cls"
@@ -677,6 +688,6 @@ def annotate_results(fm, inputs, images: torch.Tensor, results, out: list, overl
             drawn = ann.annotate_classification(fr, out[b0:b0 + n])
         else:
             drawn = ann.annotate(fr, results, b0) if overlay is None else ann.annotate_overlay(fr, results, b0, overlay)
-        host = to_host(drawn)
+        host = images_to_host(drawn, image_format)
         for k in range(n):
             out[b0 + k].image = host[k]

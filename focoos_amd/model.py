@@ -284,7 +284,7 @@ class FocoosModel:
 
     def infer_batch(self, inputs: list, threshold: Optional[float] = None, annotate=False, tracker=None,
                     mask_format: str = "png", zones=None, dwell=None, heatmap=None, tiling=None, classify=None,
-                    polygon_tolerance: Optional[float] = None, components=None) -> List[FocoosDetections]:
+                    polygon_tolerance: Optional[float] = None, components=None, image_format="array") -> List[FocoosDetections]:
         """Batched inference: list of images in, list of FocoosDetections out (per-image result == the
         reference at B=1; the reference's own __call__ drops all but image 0 — focoos_model.py:615-621).  ``inputs`` may also be a
         ``frames.FrameBatch`` of NV12 / I420 / BGR / RGB video frames, host or device: the results are those of the same frames passed as
@@ -328,13 +328,19 @@ class FocoosModel:
         classes outside ``Components.classes`` pass through whole; components below ``min_area`` pixels are dropped silently, those
         beyond ``max_components`` per image with a warning.  Mask families only (NotImplementedError otherwise); anything but None, True
         or a Components TypeError; a value outside the contract, an unknown class, or ``mask_format="none"`` with nothing that reads the
-        components ValueError - all before anything touches the GPU.  With None nothing changes."""
+        components ValueError - all before anything touches the GPU.  With None nothing changes.
+        ``image_format``: what ``.image`` holds when ``annotate`` draws - "array" (the default: np.uint8 [H, W, 3]), "jpeg" (``bytes``: a
+        complete baseline JFIF file of the drawn frame at its original size, encoded on the device so that only the file crosses the bus;
+        jpeg.py), a ``jpeg.Jpeg(quality=85, subsampling="420", restart_mcus=32)`` for other settings, or "jpeg_base64" (the
+        same file as base64 ``str``, the reference's form).  Anything else, or anything but "array" with a falsy ``annotate``, raises
+        ValueError before anything touches the GPU."""
         from .analytics import StreamAnalytics, batch_size
         from .frames import drawable
 
         an = StreamAnalytics.resolve(self, "infer_batch", device_only=True, track=tracker, zones=zones, dwell=dwell, heatmap=heatmap,
                                      annotate=annotate, classify=classify, tiling=tiling, detections=True, mask_format=mask_format,
-                                     threshold=threshold, polygon_tolerance=polygon_tolerance, components=components)
+                                     threshold=threshold, polygon_tolerance=polygon_tolerance, components=components,
+                                     image_format=image_format)
         inputs = an.frames(inputs)      # a FrameBatch (or one Frame) goes where a list of images goes (frames.py, DESIGN 21)
         an.prepare(inputs, batch_size(inputs))
         t0 = perf_counter()
@@ -366,7 +372,7 @@ class FocoosModel:
 
     def infer_stream(self, batches, threshold: Optional[float] = None, depth: Optional[int] = None, annotate=False, track=None,
                      mask_format: str = "png", zones=None, detections: bool = True, dwell=None, heatmap=None, tiling=None, classify=None,
-                     polygon_tolerance: Optional[float] = None, components=None):
+                     polygon_tolerance: Optional[float] = None, components=None, image_format="array"):
         """Throughput inference (round 6): iterate over ``batches`` (each a list of images of ONE common shape after preprocessing and one
         batch size) and yield each batch's ``List[FocoosDetections]`` in order, with up to ``depth`` batches in flight on the engine's
         pipeline (engine.pipeline(): batch i+1's backbone runs beside batch i's decoder tail; default depth 3).  Same results as
@@ -430,7 +436,8 @@ class FocoosModel:
         objects left out for want of crop budget warn once per call.  With ``None`` nothing changes.
         ``polygon_tolerance``: as in ``infer_batch``; the simplify call follows each batch's trace on the current stream.
         ``components``: as in ``infer_batch``; each batch is split after its lane finished, in front of the tracker, and one splitter
-        serves every lane (batches finish in order on the current stream)."""
+        serves every lane (batches finish in order on the current stream).
+        ``image_format``: as in ``infer_batch``; each batch's drawn frames are encoded right after they are drawn."""
         from collections import deque
         from types import SimpleNamespace
 
@@ -439,7 +446,8 @@ class FocoosModel:
 
         an = StreamAnalytics.resolve(self, "infer_stream", device_only=False, track=track, zones=zones, dwell=dwell, heatmap=heatmap,
                                      annotate=annotate, classify=classify, tiling=tiling, detections=detections, mask_format=mask_format,
-                                     threshold=threshold, polygon_tolerance=polygon_tolerance, components=components)
+                                     threshold=threshold, polygon_tolerance=polygon_tolerance, components=components,
+                                     image_format=image_format)
         if tiling is not None:      # the same tail on the merged result of every frame batch, in the tiler's own loop (tiled.py)
             from . import tiled as TL
 
@@ -492,14 +500,17 @@ class FocoosModel:
                                 polygon_tolerance=kwargs.get("polygon_tolerance"), components=kwargs.get("components"))[0]
 
     def infer(self, image, threshold: Optional[float] = None, annotate: bool = False, mask_format: str = "png",
-              polygon_tolerance: Optional[float] = None, components=None) -> FocoosDetections:
+              polygon_tolerance: Optional[float] = None, components=None, image_format="array") -> FocoosDetections:
         """focoos_model.py:370-416: one picture (path, PIL image, array, tensor) -> FocoosDetections.  ``annotate``: ``.image`` is the
         picture (np.uint8 [H, W, 3] RGB, original size) with the detections drawn on it on the device (annotate.py; the input itself
-        when nothing was detected) and ``.latency.annotate`` / ``.latency.imload`` are set.  ``mask_format``, ``polygon_tolerance`` and ``components``: as in ``infer_batch``.
+        when nothing was detected) and ``.latency.annotate`` / ``.latency.imload`` are set.  ``mask_format``, ``polygon_tolerance``,
+        ``components`` and ``image_format``: as in ``infer_batch``.
         ``image`` may also be a ``frames.Frame`` (NV12, I420, BGR or RGB video frame, host or device)."""
         from .frames import Frame, FrameBatch
+        from .jpeg import check_image_format
         from .mask_rle import check_mask_format
 
+        check_image_format(image_format, annotate, "infer")
         if annotate:
             from .annotate import refuse_overlay
 
@@ -522,13 +533,14 @@ class FocoosModel:
             return self(image, threshold=threshold, mask_format=mask_format, polygon_tolerance=polygon_tolerance, components=components)
         imload = perf_counter() - t0
         res = self.infer_batch(image if isinstance(image, (Frame, FrameBatch)) else [image], threshold=threshold, annotate=True,
-                               mask_format=mask_format, polygon_tolerance=polygon_tolerance, components=components)[0]
+                               mask_format=mask_format, polygon_tolerance=polygon_tolerance, components=components,
+                               image_format=image_format)[0]
         res.latency.imload = round(imload, 3)
         return res
 
     def infer_tiled(self, image, tile: Union[None, int, Tuple[int, int]] = None, overlap: float = 0.2, threshold: Optional[float] = None,
                     merge_threshold: float = 0.5, merge_metric: str = "iou", include_full: bool = True, batch_size: Optional[int] = None,
-                    max_detections: int = 300, annotate: bool = False, mask_format: str = "png") -> FocoosDetections:
+                    max_detections: int = 300, annotate: bool = False, mask_format: str = "png", image_format="array") -> FocoosDetections:
         """Tiled RT-DETR inference of ONE large picture (an engine-native mode like ``infer_stream``; the reference has none): ``image`` (what
         ``infer`` takes) is cut into overlapping windows of ``tile`` (int or (h, w), default ``model_info.im_size``; both the window cut from
         the frame and the size the model runs at) that share at least ``overlap`` in [0, 1) of a tile with their neighbours
@@ -541,11 +553,14 @@ class FocoosModel:
         the frame goes up once, one packed result comes back.  Bad arguments raise ValueError; every family but fai_detr raises
         NotImplementedError before anything touches the GPU.  ``annotate``: ``.image`` is the frame with the merged detections drawn on
         it (the resident frame is drawn on the device and copied back beside the packed result; annotate.py).  ``mask_format``: tiled
-        inference has no masks to hand out - "rle", "polygon" and "png_device" raise NotImplementedError, another unknown value ValueError."""
+        inference has no masks to hand out - "rle", "polygon" and "png_device" raise NotImplementedError, another unknown value ValueError.
+        ``image_format``: as in ``infer_batch``."""
         from .frames import refuse_frames
+        from .jpeg import check_image_format
         from .mask_rle import check_mask_format
 
         refuse_frames(image, "infer_tiled")      # before anything loads the library
+        image_format = check_image_format(image_format, annotate, "infer_tiled")
         if annotate:
             from .annotate import refuse_overlay
 
@@ -557,11 +572,11 @@ class FocoosModel:
                                       f"{self.model.family!r})")
 
         return _infer_tiled(self, image, tile, overlap, threshold, merge_threshold, merge_metric, include_full, batch_size, max_detections,
-                            annotate)
+                            annotate, image_format)
 
     def segment_tiled(self, image, tile: Optional[int] = None, overlap: float = 0.2, threshold: Optional[float] = None,
                       batch_size: Optional[int] = None, max_classes: Optional[int] = None, mask_format: str = "png", annotate: bool = False,
-                      return_label_map: bool = False, components=None):
+                      return_label_map: bool = False, components=None, image_format="array"):
         """Tiled semantic segmentation of ONE large picture (an engine-native mode like ``infer_tiled``; the reference has none): ``image``
         (what ``infer_tiled`` takes) is cut into the overlapping windows of ``tiled.tile_grid`` for a square ``tile`` (a multiple of 32,
         default ``model_info.im_size``) and ``overlap`` in [0, 0.5]; the views run through the engine in chunks of ``batch_size`` (default
@@ -575,17 +590,20 @@ class FocoosModel:
         a warning.  ``return_label_map``: the result is the pair ``(detections, label_map)``, ``label_map`` the uint8 [Hf, Wf] numpy array of class ids.  ``annotate``: ``.image`` is the frame
         with the classes drawn on it.  ``components``: as in ``infer_batch`` - the merged class masks are split into their connected components
         behind the merge, and the detections, the encoders and the drawing see one ``FocoosDet`` per component.  bisenetformer with ``predict_all_pixels`` only: every other family or configuration raises
-        NotImplementedError before anything touches the GPU, bad arguments and frames ValueError."""
+        NotImplementedError before anything touches the GPU, bad arguments and frames ValueError.  ``image_format``: as in ``infer_batch``."""
         from .frames import refuse_frames
+        from .jpeg import check_image_format
 
         refuse_frames(image, "segment_tiled")      # before anything loads the library
+        image_format = check_image_format(image_format, annotate, "segment_tiled")
         if annotate:
             from .annotate import refuse_overlay
 
             refuse_overlay(annotate, "segment_tiled")
         from .tiled_seg import segment_tiled as _segment_tiled
 
-        return _segment_tiled(self, image, tile, overlap, threshold, batch_size, max_classes, mask_format, annotate, return_label_map, components)
+        return _segment_tiled(self, image, tile, overlap, threshold, batch_size, max_classes, mask_format, annotate, return_label_map, components,
+                              image_format)
 
     def train(self, args, data_train, data_val=None, hub=None):
         """focoos_model.py:221-274: fine-tune on ``data_train`` (indexable, entries = ports.DatasetEntry) with ``args`` (ports.TrainerArgs):

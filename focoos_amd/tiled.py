@@ -413,8 +413,8 @@ def infer_stream_tiled(fm, batches, tiling: Tiling, thr: float, depth: Optional[
 
 def infer_tiled(fm, image, tile: Union[None, int, Tuple[int, int]] = None, overlap: float = 0.2, threshold: Optional[float] = None,
                 merge_threshold: float = 0.5, merge_metric: str = "iou", include_full: bool = True, batch_size: Optional[int] = None,
-                max_detections: int = 300, annotate: bool = False):
-    """FocoosModel.infer_tiled (see there)."""
+                max_detections: int = 300, annotate: bool = False, image_format=None):
+    """FocoosModel.infer_tiled (see there).  ``image_format``: None, or what ``jpeg.check_image_format`` returned."""
     from ._lib import load
     from .ports import InferLatency
 
@@ -456,11 +456,11 @@ def infer_tiled(fm, image, tile: Union[None, int, Tuple[int, int]] = None, overl
     if annotate:       # the frame is resident: draw the merged, frame-pixel detections on it (a caller's own device tensor stays untouched)
         from types import SimpleNamespace
 
-        from .annotate import annotator_of, to_host
+        from .annotate import annotator_of, images_to_host
 
         res = SimpleNamespace(det_scores=o_s, det_labels=o_l, det_boxes=o_b, det_count=cs[:1])
         drawn = annotator_of(fm).annotate(frame_d[None], res, 0, out=torch.empty_like(frame_d[None]) if frame.is_cuda else None)
-        out.image = to_host(drawn)[0]
+        out.image = images_to_host(drawn, image_format)[0]
     t4 = perf_counter()
     # host wall clock: the gather is enqueued in `preprocess`, the device drains it, the engine and the merge in `inference`
     out.latency = InferLatency(preprocess=round(t1 - t0, 3), inference=round(t2 - t1, 3), postprocess=round(t3 - t2, 3),

@@ -99,8 +99,8 @@ def merge_views(lib, mask_probs: torch.Tensor, score: torch.Tensor, label: torch
 
 def segment_tiled(fm, image, tile: Optional[int] = None, overlap: float = 0.2, threshold: Optional[float] = None,
                   batch_size: Optional[int] = None, max_classes: Optional[int] = None, mask_format: str = "png", annotate: bool = False,
-                  return_label_map: bool = False, components=None):
-    """FocoosModel.segment_tiled (see there)."""
+                  return_label_map: bool = False, components=None, image_format=None):
+    """FocoosModel.segment_tiled (see there).  ``image_format``: None, or what ``jpeg.check_image_format`` returned."""
     from ._lib import load
     from .mask_rle import check_mask_format
     from .ports import InferLatency
@@ -160,7 +160,7 @@ def segment_tiled(fm, image, tile: Optional[int] = None, overlap: float = 0.2, t
     if annotate:       # the frame is resident: draw the merged classes on it (a caller's own device tensor stays untouched)
         from .annotate import annotate_results
 
-        annotate_results(fm, [frame], frame_d.clone()[None] if frame.is_cuda else frame_d[None], res, [out])
+        annotate_results(fm, [frame], frame_d.clone()[None] if frame.is_cuda else frame_d[None], res, [out], None, image_format)
     t4 = perf_counter()
     out.latency = InferLatency(preprocess=round(t1 - t0, 3), inference=round(t2 - t1, 3), postprocess=round(t3 - t2, 3),
                                annotate=round(t4 - t3, 3) if annotate else None)

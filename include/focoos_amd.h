@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 31
+#define FX_ABI_VERSION 32
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -626,6 +626,49 @@ int fx_mask_components(const int32_t* mask_words, const int32_t* det_count, cons
 size_t fx_mask_png_workspace_bytes(int B, int Q, int H, int W);
 int fx_mask_png_encode(const int32_t* mask_words, const int32_t* det_count, const int32_t* det_boxes, int B, int Q, int H, int W, int capacity,
                        int32_t* png_len, int32_t* png_off, int32_t* png_pool, void* workspace, size_t workspace_bytes, fx_stream_t stream);
+
+/* ---- Baseline JPEG of drawn frames on the device (ABI 32; csrc/jpeg.hip): image_format="jpeg" wherever annotate=
+ * exists.  Input: frames uint8 [B][H][W][3] RGB; frames b0 .. b0 + count - 1 are encoded, each into one complete JFIF file.
+ *
+ * The file: `header` (built by the host, focoos_amd/jpeg.py: SOI, JFIF APP0, two DQT, SOF0, four DHT, DRI, SOS), one interleaved scan, EOI.
+ * subsampling 0 = 4:4:4 (MCU 8 x 8: blocks Y Cb Cr), 1 = 4:2:0 (MCU 16 x 16: Y0 Y1 Y2 Y3 Cb Cr, Y in raster order).  MCUs in raster order,
+ * ceil(W / mcu) x ceil(H / mcu) of them; pixel (x, y) outside the frame is pixel (min(x, W - 1), min(y, H - 1)).  A restart interval is
+ * restart_mcus consecutive MCUs (the last may be short); interval i < n - 1 is followed by the marker FF D0+(i mod 8), the last by FF D9.
+ * All arithmetic is integer, >> is the arithmetic shift:
+ *  - colour per pixel: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16,
+ *    Cr = (32768 R - 27439 G - 5329 B + 8421375) >> 16 (8421375 = 128 * 65536 + 32767);
+ *  - 4:2:0 chroma sample = (a + b + c + d + 2) >> 2 over the Cb (Cr) of the 2 x 2 pixels;
+ *  - forward DCT of s[y][x] = sample - 128 with A[u][x] = round(2^13 c(u) cos((2 x + 1) u pi / 16)), c(0) = 1 / sqrt 2, else 1:
+ *    rows t[y][u] = (sum_x A[u][x] s[y][x] + 1024) >> 11, then columns F[v][u] = (sum_y A[v][y] t[y][u] + 65536) >> 17;
+ *  - quantisation by q = the DQT entry of (v, u): sign(F) * ((|F| + (q >> 1)) / q) with / the floor division; AC clamped to +-1023 (DC lies
+ *    in -1024 .. 1016, so a DC difference in +-2040, category <= 11);
+ *  - entropy coding as ITU-T T.81 F.1.2 with the tables the host passes: the DC difference against the previous block of the same component,
+ *    0 for the first of an interval; (run, size) symbols over the zigzag order with ZRL (0xF0) per 16 zeros and EOB (0x00) unless
+ *    coefficient 63 is nonzero; a negative value v of category s is sent as the low s bits of v - 1; the interval is padded with 1-bits to a
+ *    byte and every byte FF of it is followed by 00.
+ * tables int32 [FX_JPEG_TABLE_WORDS]: [0, 128) the two quantisers (luminance, chrominance), 64 entries each in NATURAL order (v * 8 + u),
+ * 1 .. 255; [128, 160) the DC codes, 16 per class, indexed by category; [160, 672) the AC codes, 256 per class, indexed by the symbol.  A code
+ * entry is code << 5 | length (length 1 .. 16; 0: not in the table - never looked up for a valid table).
+ *
+ * fx_jpeg_intervals: n, the restart intervals of one frame; 0 outside the limits below.
+ * fx_jpeg_scan_sizes (launch A and the scan): sizes [count][n] int32 = the bytes of every interval after stuffing; interval_off [count][n]
+ *   int64 = where its first byte goes in the flat output; frame_off [count + 1] int64 = where every file starts (frame_off[count] = the
+ *   bytes of all of them; a file is header_bytes + sum(sizes) + 2 n bytes).
+ * fx_jpeg_encode (launch B): out[0 .. out_bytes) = the files, back to back, from the offsets of fx_jpeg_scan_sizes on the same arguments; one
+ *   workgroup per interval recomputes it and stores it, its marker and (interval 0) the header.  Nothing at or beyond out_bytes is written.
+ *   Plain stores, no global atomics: the output is a pure function of the input.
+ * Limits: 1 <= count, 0 <= b0, b0 + count <= B <= 65535; 1 <= H, W <= 65535, H W <= 2^26; subsampling 0 or 1; restart_mcus >= 1 with
+ * restart_mcus * (blocks of an MCU: 3 or 6) <= FX_JPEG_MAX_BLOCKS (an interval is assembled in LDS); 1 <= header_bytes <= 4096; out_bytes >= 1.
+ * A null pointer, interval_off / frame_off not 8-byte or sizes / tables not 4-byte aligned, or anything else outside the contract:
+ * FX_ERR_INVALID_ARGUMENT, nothing launched or written.  The same in both libraries. */
+#define FX_JPEG_TABLE_WORDS 672
+#define FX_JPEG_MAX_BLOCKS 192
+int fx_jpeg_intervals(int H, int W, int subsampling, int restart_mcus);
+int fx_jpeg_scan_sizes(const uint8_t* frames, int B, int H, int W, int b0, int count, int subsampling, int restart_mcus, const int32_t* tables,
+                       int header_bytes, int32_t* sizes, int64_t* interval_off, int64_t* frame_off, fx_stream_t stream);
+int fx_jpeg_encode(const uint8_t* frames, int B, int H, int W, int b0, int count, int subsampling, int restart_mcus, const int32_t* tables,
+                   const uint8_t* header, int header_bytes, const int64_t* interval_off, const int64_t* frame_off, uint8_t* out, int64_t out_bytes,
+                   fx_stream_t stream);
 
 /* ---- Zone and line counting on the device (ABI 21; csrc/zone_ops.hip): FocoosModel.infer_stream(zones=...).
  * Input: the packed results (det_labels i32 [B][T], det_boxes i32 xyxy [B][T][4], 16-byte aligned, det_count i32 [B]; slot j of stream b is a
