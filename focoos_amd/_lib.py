@@ -99,6 +99,15 @@ class FxFrameDesc(C.Structure):
     ]
 
 
+class FxJpegFile(C.Structure):
+    """include/focoos_amd.h fx_jpeg_file (128 bytes)"""
+    _fields_ = [
+        ("height", C.c_int32), ("width", C.c_int32), ("subsampling", C.c_int32), ("restart", C.c_int32), ("scan_off", C.c_int32),
+        ("scan_len", C.c_int32), ("tab_off", C.c_int32), ("selectors", C.c_int32), ("sub_first", C.c_int32), ("n_sub", C.c_int32),
+        ("blk_first", C.c_int32), ("n_blk", C.c_int32), ("out_off", C.c_int32 * 3), ("pitch", C.c_int32 * 3), ("reserved", C.c_int32 * 14),
+    ]
+
+
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 
 # name -> argtypes (every function returns int unless noted); mirrors include/focoos_amd.h
@@ -175,6 +184,8 @@ SIGNATURES = {
     "fx_jpeg_intervals": [_i, _i, _i, _i],
     "fx_jpeg_scan_sizes": [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "fx_jpeg_encode": [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, C.c_int64, _vp],
+    "fx_jpeg_decode_workspace_bytes": [C.c_int64, C.c_int64],
+    "fx_jpeg_decode": [_vp, _vp, _i, _vp, C.c_int64, _vp, C.c_size_t, _vp, C.c_int64, _vp, _vp],
     "fx_maxpool3x3s2_nhwc_bf16": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "fx_stem_conv12_u8_bf16": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "fx_stem_conv_pool_supported": [_i, _i, _i, _i],
@@ -350,7 +361,7 @@ def lib_path(name: str = None) -> str:
     return os.environ.get("FOCOOS_AMD_LIB", LIB_PATH)
 
 
-FX_ABI_VERSION = 32  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
+FX_ABI_VERSION = 33  # = include/focoos_amd.h (tests/test_host_cpu.py compares the two)
 
 
 def load(name: str = None) -> C.CDLL:
@@ -388,6 +399,7 @@ def load(name: str = None) -> C.CDLL:
     lib.fx_mask_components_workspace_bytes.restype = C.c_size_t
     lib.fx_mask_png_workspace_bytes.restype = C.c_size_t
     lib.fx_seg_merge_workspace_bytes.restype = C.c_size_t
+    lib.fx_jpeg_decode_workspace_bytes.restype = C.c_size_t
     lib.fx_error_string.argtypes = [C.c_int]
     lib.fx_error_string.restype = C.c_char_p
     if lib.fx_abi_version() != FX_ABI_VERSION:

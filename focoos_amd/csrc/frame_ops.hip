@@ -25,34 +25,6 @@
 #define FI_BY 4    // rows per workgroup
 #define FI_PX 16   // pixels of one thread on the uint8 path
 
-// (cy, crv, cgu, cgv, cbu, luma offset) of matrix 0..3: the standard matrices times 256, rounded
-struct FiCoef {
-  int cy, crv, cgu, cgv, cbu, yoff;
-};
-
-__device__ __forceinline__ FiCoef fi_coef(int matrix) {
-  switch (matrix) {
-    case FX_FRAME_BT601_FULL: return FiCoef{256, 359, 88, 183, 454, 0};
-    case FX_FRAME_BT709_LIMITED: return FiCoef{298, 459, 55, 136, 541, 16};
-    case FX_FRAME_BT709_FULL: return FiCoef{256, 403, 48, 120, 475, 0};
-    default: return FiCoef{298, 409, 100, 208, 516, 16};
-  }
-}
-
-// clip(v >> 8) to 0..255, written as clamp-then-shift: v < 0 gives 0 either way, v >= 65536 gives 255 either way, and in between the
-// shift is the same.  The shift-then-clamp spelling is what hipcc (ROCm 7.2) turns into v_ashr_pk_u8_i32 where two results end up in one
-// word, and on the MI355X that form left the upper half of its destination register as it was while the code around it assumed zeros
-// there: tests/test_gpu_frames.py saw 255s in the bytes packed beside a negative value.  This spelling compiles to max, min and a shift.
-__device__ __forceinline__ int fi_clip_shr8(int v) { return (v < 0 ? 0 : (v > 65535 ? 65535 : v)) >> 8; }
-
-// |cy C| <= 298 * 255, |c E| <= 541 * 128: every sum stays far inside int32
-__device__ __forceinline__ void fi_yuv_to_rgb(int Y, int U, int V, const FiCoef& k, int& R, int& G, int& B) {
-  const int c = k.cy * (Y - k.yoff), d = U - 128, e = V - 128;
-  R = fi_clip_shr8(c + k.crv * e + 128);
-  G = fi_clip_shr8(c - k.cgu * d - k.cgv * e + 128);
-  B = fi_clip_shr8(c + k.cbu * d + 128);
-}
-
 // The workgroup's frame: 16 threads copy one dword each of the 64-byte record into LDS.
 __device__ __forceinline__ void fi_load_desc(fx_frame_desc* s_d, const fx_frame_desc* __restrict__ descs, int b) {
   const int t = threadIdx.y * FI_BX + threadIdx.x;

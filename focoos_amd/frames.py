@@ -8,7 +8,8 @@ BGR, or NV12 / I420 with a row pitch, on the host or already on the device), ``F
 
 The result is defined to be, bit for bit, what ``processor.preprocess`` returns for the same frames converted to RGB arrays by the integer
 conversion of include/focoos_amd.h (tests/frames_ref.py restates it), so everything downstream can be compared by equality.
-Construction validates on the host and never touches the GPU."""
+Construction validates on the host and never touches the GPU.  Cameras and uploads that send JPEG files instead go through
+``FrameBatch.from_jpeg``: baseline files are decoded on the device into such planes (focoos_amd/jpeg.py)."""
 from __future__ import annotations
 
 import ctypes
@@ -217,6 +218,18 @@ class FrameBatch:
     @property
     def sizes(self) -> List[Tuple[int, int]]:
         return [f.size for f in self.frames]
+
+    @classmethod
+    def from_jpeg(cls, files, device="cuda", check: bool = True) -> "FrameBatch":
+        """Baseline JPEG files (a sequence of bytes / bytearray / memoryview / 1-D uint8 arrays; sizes, subsampling, tables and restart
+        intervals may differ) decoded on ``device`` (csrc/jpeg_decode.hip): a 4:2:0 file becomes a full-range BT.601
+        I420 frame, a 4:4:4 file an RGB frame, all planes views into one device allocation.  The host only walks the markers: ValueError
+        naming the file for what is outside the accepted class (progressive, grey, CMYK, 4:2:2, 12 bit, ...), nothing falls back to a host
+        decoder.  ``check=True`` copies the per-file status words and raises ValueError for the first file whose entropy-coded data was
+        invalid; ``check=False`` does not synchronise and leaves them on ``jpeg.decoder_for(device).status``."""
+        from .jpeg import decoder_for
+
+        return decoder_for(device).decode(files, check=check)
 
     # ---- device side
     def _descriptors(self, device):

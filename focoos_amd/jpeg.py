@@ -5,7 +5,13 @@ Everything that ends in ``.image`` is drawn on the device; with ``image_format="
 builds the ~620 header bytes, the quantisers and the Huffman code tables once per (H, W, ``Jpeg``) and uploads them once, launch A sizes
 every restart interval, one small copy tells the host how many bytes there are, launch B stores the files into one flat buffer of exactly
 that size and one pinned copy brings them back.  ``"jpeg_base64"`` is ``base64.b64encode`` over those bytes on the host.  Progressive or
-optimised-Huffman files, 4:2:2, grey-scale, EXIF, frames that were not drawn and decoding are out of scope."""
+optimised-Huffman files, 4:2:2, grey-scale, EXIF and frames that were not drawn are out of scope of the encoder.
+
+The other direction (``FrameBatch.from_jpeg``): ``parse_jpeg`` walks the markers of a baseline file on the host and
+builds the table block the kernels read, ``DeviceJpegDecoder`` packs the scans of a call into one staging buffer, uploads it once and
+runs fx_jpeg_decode (csrc/jpeg_decode.hip): self-synchronising parallel Huffman decoding, a DC scan, the integer IDCT and the stores, into
+device planes that every entry point reads in place.  Optimised-Huffman files and files without restart markers are in scope there;
+progressive, arithmetic, 12-bit, grey-scale, CMYK and 4:2:2 files are refused on the host."""
 from __future__ import annotations
 
 import struct
@@ -214,3 +220,248 @@ def images_to_host(frames, fmt: Tuple[Jpeg, bool]) -> list:
 
         return [base64.b64encode(f).decode("ascii") for f in files]
     return files
+
+
+# ---------------------------------------------------------------- decoding
+SUBSEQ_BYTES = 128            # FX_JPEG_SUBSEQ_BYTES: scan bytes of one thread
+SEQ_SUBSEQS = 256             # FX_JPEG_SEQ_SUBSEQS: threads of one workgroup
+DHT_BYTES = 1416              # FX_JPEG_DHT_BYTES
+TABLE_BLOCK_BYTES = 384 + 4 * DHT_BYTES
+MAX_SCAN_BYTES = 1 << 27
+STATUS_BITS = {1: "a marker other than RSTn / EOI inside the scan", 2: "an invalid Huffman code or a run past coefficient 63",
+               4: "the scan ends before (or runs past) the last MCU"}
+_NATURAL = np.array(ZIGZAG)
+_DHT_CACHE: dict = {}
+
+
+@dataclass
+class JpegInfo:
+    """What ``parse_jpeg`` found: the frame, the scan bytes (from behind the SOS segment to the end of EOI, or of the file) and the file's
+    table block as fx_jpeg_decode reads it (include/focoos_amd.h)."""
+    height: int
+    width: int
+    subsampling: str          # "444" / "420"
+    restart: int              # MCUs per restart interval, 0 without DRI
+    selectors: int            # bit 2c: DC table of component c, bit 2c + 1: its AC table
+    scan: np.ndarray          # uint8, a view into the file
+    tables: np.ndarray        # uint8 [TABLE_BLOCK_BYTES]
+
+
+def huffman_decode_table(bits, values) -> np.ndarray:
+    """uint8 [DHT_BYTES] of one DHT table: look[512] over the next 9 bits (length << 8 | symbol, 0: longer), then T.81 F.2.2.3's maxcode
+    (-1: no code of that length) and valptr - mincode per length, then huffval."""
+    key = (bytes(bits), bytes(values))
+    if key not in _DHT_CACHE:
+        look, maxcode, valoff = np.zeros(512, np.uint16), np.full(17, -1, np.int32), np.zeros(17, np.int32)
+        huffval = np.zeros(256, np.uint8)
+        huffval[:len(values)] = list(values)
+        code, k = 0, 0
+        for length in range(1, 17):
+            valoff[length] = k - code
+            for _ in range(bits[length - 1]):
+                if length <= 9:
+                    look[code << (9 - length):(code + 1) << (9 - length)] = length << 8 | values[k]
+                code, k = code + 1, k + 1
+            if bits[length - 1]:
+                maxcode[length] = code - 1
+            code <<= 1
+        _DHT_CACHE[key] = np.concatenate([look.view(np.uint8), maxcode.view(np.uint8), valoff.view(np.uint8), huffval])
+    return _DHT_CACHE[key]
+
+
+def parse_jpeg(file, index: int = 0) -> JpegInfo:
+    """Walks the markers of one baseline JFIF / JPEG file (bytes, bytearray, memoryview or a 1-D uint8 array) up to its scan.  ValueError
+    naming ``index`` and the reason for everything outside the accepted class (section 33).  Host only: the library is not loaded."""
+    def refuse(why: str):
+        raise ValueError(f"from_jpeg: file {index}: {why}")
+
+    if isinstance(file, np.ndarray):
+        if file.dtype != np.uint8 or file.ndim != 1:
+            refuse(f"an array must be 1-D uint8, got {file.dtype} {file.shape}")
+        data = np.ascontiguousarray(file)
+    elif isinstance(file, (bytes, bytearray, memoryview)):
+        data = np.frombuffer(file, np.uint8)
+    else:
+        refuse(f"must be bytes, bytearray, memoryview or a 1-D uint8 array, not {type(file).__name__}")
+    raw = data.tobytes() if not isinstance(file, bytes) else file
+    if raw[:2] != b"\xff\xd8":
+        refuse("no SOI marker: not a JPEG file")
+    quant, dht, frame, restart, at = {}, {}, None, 0, 2
+    while True:
+        if at + 4 > len(raw) or raw[at] != 0xFF:
+            refuse("truncated header: no SOS" if at + 4 > len(raw) else f"no marker at byte {at}")
+        marker, n = raw[at + 1], int.from_bytes(raw[at + 2:at + 4], "big")
+        if marker == 0xD9:
+            refuse("no SOS before EOI")
+        body = raw[at + 4:at + 2 + n]
+        if n < 2 or at + 2 + n > len(raw):
+            refuse("truncated header")
+        if marker == 0xDB:
+            k = 0
+            while k < len(body):
+                if body[k] >> 4:
+                    refuse("a DQT with 16-bit entries")
+                if (body[k] & 15) > 3 or k + 65 > len(body):
+                    refuse("a malformed DQT")
+                q = np.zeros(64, np.uint16)
+                q[_NATURAL] = list(body[k + 1:k + 65])
+                quant[body[k] & 15], k = q, k + 65
+        elif marker == 0xC4:
+            k = 0
+            while k < len(body):
+                bits = body[k + 1:k + 17]
+                cnt = sum(bits)
+                if (body[k] >> 4) > 1 or (body[k] & 15) > 1 or len(bits) < 16 or cnt > 256 or k + 17 + cnt > len(body):
+                    refuse("a malformed DHT (classes 0 / 1, ids 0 / 1)")
+                code = 0
+                for length in range(16):          # Kraft: the codes of every length must fit
+                    code += bits[length]
+                    if code > (2 << length):
+                        refuse("a DHT whose code lengths fit no prefix code")
+                    code <<= 1
+                dht[body[k]], k = huffman_decode_table(bits, body[k + 17:k + 17 + cnt]), k + 17 + cnt
+        elif marker == 0xC0:
+            if frame is not None:
+                refuse("two SOF segments")
+            frame = body
+        elif marker in (0xC1, 0xC2, 0xC3) or 0xC5 <= marker <= 0xCF and marker != 0xC8:
+            refuse({0xC1: "SOF1 (extended sequential)", 0xC2: "SOF2 (progressive)"}.get(marker, f"SOF{marker - 0xC0} (lossless / arithmetic)"))
+        elif marker == 0xDD:
+            restart = int.from_bytes(body[:2], "big")
+        elif marker == 0xEE and body[:5] == b"Adobe" and len(body) >= 12 and body[11] == 0:
+            refuse("Adobe APP14 with transform 0: RGB-coded")
+        elif marker == 0xDA:
+            break
+        at += 2 + n
+    if frame is None or len(frame) < 6:
+        refuse("SOS without SOF0")
+    if frame[0] != 8:
+        refuse(f"{frame[0]}-bit samples")
+    H, W, nc = int.from_bytes(frame[1:3], "big"), int.from_bytes(frame[3:5], "big"), frame[5]
+    if nc != 3 or len(frame) < 15:
+        refuse(f"{nc} component(s): only three (YCbCr) are decoded")
+    from .frames import MAX_DIM
+
+    if not (1 <= H <= MAX_DIM and 1 <= W <= MAX_DIM):
+        refuse(f"{H} x {W} is outside 1..{MAX_DIM}")
+    comps = [(frame[6 + 3 * c], frame[7 + 3 * c], frame[8 + 3 * c]) for c in range(3)]
+    sampling = tuple(c[1] for c in comps)
+    if sampling not in ((0x22, 0x11, 0x11), (0x11, 0x11, 0x11)):
+        refuse("sampling factors " + ", ".join(f"{s >> 4}x{s & 15}" for s in sampling) + ": only 4:2:0 and 4:4:4 are decoded")
+    if len(body) != 10 or body[0] != 3:
+        refuse(f"a scan of {body[0] if body else 0} component(s): several scans")
+    if tuple(body[7:10]) != (0, 63, 0):
+        refuse("a scan with Ss, Se, Ah / Al other than 0, 63, 0")
+    selectors, tables = 0, np.zeros(TABLE_BLOCK_BYTES, np.uint8)
+    for c in range(3):
+        cid, tdta = body[1 + 2 * c], body[2 + 2 * c]
+        td, ta = tdta >> 4, tdta & 15
+        if cid != comps[c][0]:
+            refuse("scan components in another order than the frame's")
+        if comps[c][2] not in quant:
+            refuse(f"missing quantisation table {comps[c][2]}")
+        if td > 1 or ta > 1 or td not in dht or (0x10 | ta) not in dht:
+            refuse(f"missing Huffman table (DC {td} / AC {ta})")
+        selectors |= (td | ta << 1) << (2 * c)
+        tables[128 * c:128 * c + 128] = quant[comps[c][2]].view(np.uint8)
+    for slot, tid in enumerate((0x00, 0x01, 0x10, 0x11)):
+        if tid in dht:
+            tables[384 + slot * DHT_BYTES:384 + (slot + 1) * DHT_BYTES] = dht[tid]
+    start = at + 2 + n
+    eoi = raw.rfind(b"\xff\xd9")
+    end = eoi + 2 if eoi >= start else len(raw)
+    if not 1 <= end - start <= MAX_SCAN_BYTES:
+        refuse("an empty scan" if end <= start else "a scan above 2^27 bytes")
+    return JpegInfo(H, W, "420" if sampling[0] == 0x22 else "444", restart, selectors, data[start:end], tables)
+
+
+class DeviceJpegDecoder:
+    """The device side of ``FrameBatch.from_jpeg`` on one device: ``decode`` parses the files on the host, packs descriptors, tables and scans
+    into one staging buffer, uploads it once and runs fx_jpeg_decode (csrc/jpeg_decode.hip)."""
+
+    def __init__(self, device):
+        import torch
+
+        from ._lib import load
+
+        self.lib = load("bf16")   # inference surface: the bf16 product library whatever a training step pinned
+        self.device = torch.device(device)
+        self.status = None        # int32 [files] on the device: the FX_JPEG_ST_* bits of the last call
+        self._last = None
+
+    def decode(self, files, check: bool = True):
+        import ctypes
+
+        import torch
+
+        from . import _lib
+        from .frames import _STAGING, Frame, FrameBatch, _align, _pack
+
+        files = list(files) if not isinstance(files, (bytes, bytearray, memoryview, np.ndarray)) else [files]
+        if not files:
+            raise ValueError("from_jpeg: files must hold at least one file")
+        infos = [parse_jpeg(f, i) for i, f in enumerate(files)]
+        n = len(infos)
+        host = (_lib.FxJpegFile * n)()
+        off, out_off, subs, blocks, copies = _align(128 * n), 0, 0, 0, []
+        for d, info in zip(host, infos):
+            s420 = info.subsampling == "420"
+            mcu, bpm = (16, 6) if s420 else (8, 3)
+            mw, mh = -(-info.width // mcu), -(-info.height // mcu)
+            d.height, d.width, d.subsampling, d.restart, d.selectors = info.height, info.width, int(s420), info.restart, info.selectors
+            d.tab_off, d.scan_off, d.scan_len = off, off + _align(TABLE_BLOCK_BYTES), int(info.scan.size)
+            off = _align(d.scan_off + d.scan_len)
+            d.sub_first, d.n_sub, d.blk_first, d.n_blk = subs, -(-d.scan_len // SUBSEQ_BYTES), blocks, mw * mh * bpm
+            subs, blocks = subs + d.n_sub, blocks + d.n_blk
+            for p, (row, rows) in enumerate(((mw * 16, mh * 16), (mw * 8, mh * 8), (mw * 8, mh * 8)) if s420 else ((mw * 24, mh * 8),)):
+                d.out_off[p], d.pitch[p], out_off = out_off, row, _align(out_off + row * rows)
+        if max(off, out_off) >= 2 ** 31 or max(subs, blocks) >= 2 ** 31:
+            raise ValueError(f"from_jpeg: {n} files of {off} scan bytes and {out_off} plane bytes exceed one call (2 GiB each): split the batch")
+        stage = _STAGING.get(off)
+        stage_np = stage.numpy()
+        for d, info in zip(host, infos):
+            copies.append((stage_np[d.tab_off:d.tab_off + TABLE_BLOCK_BYTES], info.tables))
+            copies.append((stage_np[d.scan_off:d.scan_off + d.scan_len], info.scan))
+        _pack(copies)
+        stage_np[:128 * n] = np.frombuffer(bytes(host), dtype=np.uint8)
+        dev = torch.empty(off, dtype=torch.uint8, device=self.device)
+        dev.copy_(stage, non_blocking=True)
+        _STAGING.uploaded(self.device)
+        need = int(self.lib.fx_jpeg_decode_workspace_bytes(subs, blocks))
+        if need == 0:
+            raise ValueError(f"from_jpeg: {subs} subsequences / {blocks} blocks are outside fx_jpeg_decode's limits")
+        work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        out = torch.empty(out_off, dtype=torch.uint8, device=self.device)
+        self.status = torch.empty(n, dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self.lib.fx_jpeg_decode(dev.data_ptr(), ctypes.addressof(host), n, dev.data_ptr(), off, work.data_ptr(), need, out.data_ptr(),
+                                           out_off, self.status.data_ptr(), ctypes.c_void_p(stream)), "fx_jpeg_decode")
+        self._last = (host, dev, work, out)      # held until the next call (scripts/bench_jpeg_decode.py replays it under events)
+        if check:
+            for i, st in enumerate(self.status.tolist()):
+                if st:
+                    raise ValueError(f"from_jpeg: file {i}: invalid entropy-coded data (status {st}: "
+                                     + "; ".join(why for bit, why in STATUS_BITS.items() if st & bit) + ")")
+        frames = []
+        for d in host:
+            H, W = d.height, d.width
+            if d.subsampling:
+                ch, cw = (H + 1) // 2, (W + 1) // 2
+                planes = [out[d.out_off[p]:].as_strided(shape, (d.pitch[p], 1)) for p, shape in enumerate(((H, W), (ch, cw), (ch, cw)))]
+                frames.append(Frame("i420", planes, H, W, "bt601", "full"))
+            else:
+                frames.append(Frame.from_rgb(out[d.out_off[0]:].as_strided((H, W, 3), (d.pitch[0], 3, 1))))
+        return FrameBatch(frames)
+
+
+_DECODERS: dict = {}
+
+
+def decoder_for(device) -> DeviceJpegDecoder:
+    """One decoder per device."""
+    import torch
+
+    key = str(torch.device(device))
+    if key not in _DECODERS:
+        _DECODERS[key] = DeviceJpegDecoder(device)
+    return _DECODERS[key]

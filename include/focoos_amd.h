@@ -30,7 +30,7 @@ extern "C" {
 /* Bumped whenever a descriptor struct's layout OR the semantics the host relies on change (version 2: fx_conv_desc grew mask / ldm /
  * reserved0 and the library applies the ReLU mask the previous bottleneck skips; version 3: fx_pw_chain_desc grew pool / ldp / img_h / img_w);
  * focoos_amd/_lib.py refuses a library of another version. */
-#define FX_ABI_VERSION 32
+#define FX_ABI_VERSION 33
 
 enum { FX_OK = 0, FX_ERR_INVALID_ARGUMENT = -1, FX_ERR_LAUNCH = -2, FX_ERR_UNSUPPORTED = -3, FX_ERR_RUNTIME = -4 };
 enum { FX_ACT_NONE = 0, FX_ACT_RELU = 1, FX_ACT_SILU = 2, FX_ACT_GELU = 3 };
@@ -669,6 +669,75 @@ int fx_jpeg_scan_sizes(const uint8_t* frames, int B, int H, int W, int b0, int c
 int fx_jpeg_encode(const uint8_t* frames, int B, int H, int W, int b0, int count, int subsampling, int restart_mcus, const int32_t* tables,
                    const uint8_t* header, int header_bytes, const int64_t* interval_off, const int64_t* frame_off, uint8_t* out, int64_t out_bytes,
                    fx_stream_t stream);
+
+/* ---- Baseline JPEG files decoded on the device (ABI 33; csrc/jpeg_decode.hip): FrameBatch.from_jpeg.  The host
+ * (focoos_amd/jpeg.py: parse_jpeg) walks the markers of every file, refuses what is outside the accepted class and packs, into ONE staging
+ * buffer that is uploaded once, a table block and the scan bytes of every file; the device does everything from the first scan bit on.
+ * Accepted: SOF0, 8 bit, three components with sampling (2x2, 1x1, 1x1) = subsampling 1 ("420", MCU 16 x 16: Y0 Y1 Y2 Y3 Cb Cr, Y in raster
+ * order) or all 1x1 = subsampling 0 ("444", MCU 8 x 8: Y Cb Cr), one interleaved scan (Ss 0, Se 63, Ah = Al = 0), any DHT, any DRI.
+ *
+ * fx_jpeg_file (128 bytes, one per file; the device array holds the same bytes as the host array, which is what the library validates):
+ * height, width; subsampling; restart = Ri, the MCUs of a restart interval (0: no DRI); scan_off / scan_len: the scan bytes in `staging`, from
+ * the first byte behind the SOS segment to the end of the file's EOI marker (or of the file); tab_off: the table block; selectors: bit 2c =
+ * the DC table (0 / 1) and bit 2c + 1 = the AC table of component c; sub_first: the file's first subsequence in the workspace, n_sub =
+ * ceil(scan_len / FX_JPEG_SUBSEQ_BYTES); blk_first: its first block in the coefficient workspace, n_blk = MCUs x (6 or 3); out_off[3] /
+ * pitch[3]: where the planes go in `out`.  "420": planes Y, Cb, Cr, each padded to whole MCUs (mh x 16 rows of pitch[0] >= mw x 16 bytes; mh x 8
+ * rows of pitch[1], pitch[2] >= mw x 8).  "444": one RGB plane, mh x 8 rows of pitch[0] >= mw x 24 bytes.  Offsets and pitches are multiples of 8.
+ * Table block (tab_off a multiple of 16): uint16 q[3][64], the quantiser of each component in NATURAL order (v * 8 + u); then four tables
+ * DC0, DC1, AC0, AC1 of FX_JPEG_DHT_BYTES each: uint16 look[512], indexed by the next 9 bits: length << 8 | symbol of the code that starts
+ * there, 0 when it is longer than 9 bits; int32 maxcode[17], the largest code of length l (T.81 F.2.2.3), -1 when there is none; int32
+ * valoff[17] = valptr[l] - mincode[l]; uint8 huffval[256].  A code of length l in 10 .. 16: the smallest l with code <= maxcode[l]; its symbol is
+ * huffval[(code + valoff[l]) & 255].  No such l: the code is invalid.
+ *
+ * Entropy decoding, T.81 F.2.2.  The scan is read as bits, most significant first.  Byte FF followed by 00 is the data byte FF (the 00 is
+ * skipped); FF followed by D0 .. D7 in a file with Ri > 0 is a restart marker; FF followed by anything else (or by the end of the scan)
+ * ends the data, and unless that byte is D9 (EOI) it sets FX_JPEG_ST_MARKER.  The end of the scan bytes ends the data too.  A codeword is a
+ * Huffman code and the value bits behind it.  DC (first codeword of a block): symbol s in 0 .. 15 (above: invalid) is the category, s value bits
+ * e follow, the difference is e when e >= 2^(s-1) and e - 2^s + 1 otherwise.  AC at zigzag position z (1 .. 63): symbol r << 4 | s; s = 0 and
+ * r = 15 is ZRL (k = z + 15, value 0), any other s = 0 is EOB (the block is complete); otherwise k = z + r and coefficient k of the zigzag order is the
+ * value of the s bits, as for DC.  k > 63 is invalid; then z = k + 1 and the block is complete when z = 64.  The code is looked up in the next 16 bits, zeros
+ * standing for bits behind the data.  When no code matches and fewer than 16 data bits are left, or a code matches and the codeword is longer
+ * than the data bits left in front of the next marker (or the end of the data), nothing is decoded: at a restart marker the decoder continues behind the marker's
+ * two bytes with block 0 of an MCU, coefficient 0 and a new interval (what it had of an unfinished block stays); at the end of the data it
+ * stops.  Otherwise an invalid code, a DC symbol above 15 or k > 63 sets FX_JPEG_ST_CODE and stops the decoder for good.  The blocks decoded so far stand.
+ * Block j (0-based, in decoding order) of interval i is block i x Ri x (blocks per MCU) + j of the file (Ri = 0: one interval); a block with
+ * j >= Ri x (blocks per MCU), or beyond n_blk, is decoded and dropped.  Blocks never decoded are zero.  When the decoder stops, the
+ * index of its next block must be n_blk: otherwise FX_JPEG_ST_SHORT.  The DC value of a block is the sum, in wrapping int32, of the differences
+ * of the blocks of its component up to it within its interval, then clamped to int16.
+ * Dequantisation: F'[v][u] = clamp(coefficient x q[v][u], -16384, 16384).
+ * Inverse DCT, integer, >> arithmetic, A[u][x] = round(2^13 c(u) cos((2 x + 1) u pi / 16)) as in section 32:
+ *   columns t[y][u] = clamp((sum_v A[v][y] F'[v][u] + 1024) >> 11, -32768, 32767), rows s[y][x] = (sum_u A[u][x] t[y][u] + 65536) >> 17,
+ *   sample = clamp(s + 128, 0, 255).
+ * "420" stores the samples of Y, Cb, Cr; "444" stores R, G, B of fx_frames_ingest's FX_FRAME_BT601_FULL conversion of (Y, Cb, Cr).
+ * status int32 [n_files]: 0, or an OR of the FX_JPEG_ST_* bits; every element is written.
+ *
+ * Kernels: every thread decodes one subsequence of FX_JPEG_SUBSEQ_BYTES scan bytes from a guessed state (bit position, block of the MCU,
+ * zigzag position), FX_JPEG_SEQ_SUBSEQS of them exchange their end states through LDS until nothing changes (a decoder started at a
+ * wrong bit falls into step with the code boundaries), one wave per file corrects the states across the workgroups' seams and scans the
+ * block counts, every thread then decodes once more and stores its nonzero coefficients; a segmented scan of the DC differences and the
+ * IDCT / store kernel finish.  Plain stores, no global atomics, no waiting on other workgroups: the output is a pure function of the input.
+ * Every read is bounded by scan_len, every coefficient store by n_blk, every loop by a constant or scan_len.
+ * fx_jpeg_decode_workspace_bytes(total subsequences, total blocks): the bytes of `workspace` (256-byte aligned); 0 outside the limits.
+ * Limits: 1 <= n_files <= 65535; 1 <= height, width <= 16384; subsampling 0 / 1; 0 <= restart <= 65535; 1 <= scan_len <= 2^27; scan_off and
+ * tab_off multiples of 16 with the scan (rounded up to 16 bytes) and the table block inside staging_bytes; sub_first / blk_first = the sums of the
+ * files before; n_sub, n_blk as defined; planes inside out_bytes; the workspace at least what the function above returns for the totals.
+ * A null or misaligned pointer (16 bytes) or anything else outside the contract: FX_ERR_INVALID_ARGUMENT, nothing launched or written.  The
+ * same in both libraries. */
+#define FX_JPEG_SUBSEQ_BYTES 128
+#define FX_JPEG_SEQ_SUBSEQS 256
+#define FX_JPEG_DHT_BYTES 1416
+#define FX_JPEG_TABLE_BLOCK_BYTES (384 + 4 * FX_JPEG_DHT_BYTES)
+enum { FX_JPEG_ST_MARKER = 1, FX_JPEG_ST_CODE = 2, FX_JPEG_ST_SHORT = 4 };
+typedef struct fx_jpeg_file {
+  int32_t height, width, subsampling, restart;
+  int32_t scan_off, scan_len, tab_off, selectors;
+  int32_t sub_first, n_sub, blk_first, n_blk;
+  int32_t out_off[3], pitch[3];
+  int32_t reserved[14];
+} fx_jpeg_file; /* 128 bytes */
+size_t fx_jpeg_decode_workspace_bytes(int64_t subsequences, int64_t blocks);
+int fx_jpeg_decode(const fx_jpeg_file* files, const fx_jpeg_file* files_host, int n_files, const uint8_t* staging, int64_t staging_bytes,
+                   void* workspace, size_t workspace_bytes, uint8_t* out, int64_t out_bytes, int32_t* status, fx_stream_t stream);
 
 /* ---- Zone and line counting on the device (ABI 21; csrc/zone_ops.hip): FocoosModel.infer_stream(zones=...).
  * Input: the packed results (det_labels i32 [B][T], det_boxes i32 xyxy [B][T][4], 16-byte aligned, det_count i32 [B]; slot j of stream b is a
